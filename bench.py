@@ -21,7 +21,11 @@ region.  Default (weak): every GPU holds `--scenes` scenes.  `--total-scenes T` 
 `--goals 128`): T scenes in all, rank r plans the contiguous block shard_range(T, r, N); whole scenes per GPU, the
 (scene, goal) items of a GPU are dealt to its 8 XCDs by work (ChompEngine.build_schedule).
 
-Prints ONE JSON line (rank 0) with the driver's contract keys + "roofline", "cpu_baseline" and "parity_sample".
+A plain run does only what the headline figure needs: set-up, --warmup steps, ONE timed region of exactly --steps steps, the
+outputs of its last step when --dump-outputs DIR is given, and ONE JSON line (rank 0) with the driver's contract keys
+(`ms_per_step` = the timed region / --steps).  `--full` adds everything else the line has carried: the roofline block (HIP events
+on the timed launches), more timed regions for the spread, the oracle's "parity_sample", whole-plan timings, the other BASELINE
+shapes, the scene update, the drop-in classes, the collective's cost and the "cpu_baseline".
 """
 from __future__ import annotations
 
@@ -474,6 +478,35 @@ def drop_in_plan_timing(dev, ol_alg="MD", reps=8):
                     f"(64 goals, {ol_alg}), {iters} iterations + the closing info-only call, best of {reps} on a warm Cost"}
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir: Path, eng, final_costs) -> dict:
+    """--dump-outputs: what the timed step leaves its caller after the LAST timed step — per scene the trajectory, its gradient and
+    cost, the step's info record, the chosen goal (index and end configuration), the goal-set costs, the learner's cost vector and
+    state — and the gathered final costs of all scenes, as out_dir/<name>.npy (float32 stays float32, everything else float64).
+    Beyond DUMP_LIMIT_BYTES in all, the per-scene arrays keep a fixed, seeded sample of scenes (its indices: scene_index.npy).
+    -> {name: shape}."""
+    eng.join()  # (the pipeline's side streams; the copies below wait for the current stream)
+    arrays = {"traj": eng.traj, "grad": eng.grad, "cost_traj": eng.cost_traj, "info": eng.info, "goal_idx": eng.goal_idx, "end": eng.end,
+              "goal_cost": eng.goal_cost_total(), "cost_vec": eng.cost_vec, "learner_state": eng.learner_state}
+    arrays = {k: v.detach().cpu().numpy() for k, v in arrays.items()}
+    arrays = {k: v.astype(np.float32 if v.dtype == np.float32 else np.float64) for k, v in arrays.items()}
+    S = eng.S
+    per_scene = sum(v.nbytes for v in arrays.values()) / S
+    costs = final_costs.detach().cpu().numpy().astype(np.float64)
+    if per_scene * S + costs.nbytes > DUMP_LIMIT_BYTES:
+        keep = max(1, int((DUMP_LIMIT_BYTES - costs.nbytes - 8 * S) // per_scene))
+        rows = np.sort(np.random.RandomState(0).choice(S, size=min(S, keep), replace=False))
+        arrays = {k: v[rows] for k, v in arrays.items()}
+        arrays["scene_index"] = rows.astype(np.float64)
+    arrays["final_costs"] = costs
+    out_dir.mkdir(parents=True, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(out_dir / f"{k}.npy", np.ascontiguousarray(v))
+    return {k: list(v.shape) for k, v in arrays.items()}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -486,18 +519,25 @@ def main():
     ap.add_argument("--grid", type=int, default=64)
     ap.add_argument("--objects", type=int, default=4, help="obstacles per scene besides the table (BASELINE config 5's clutter: 12 with --waypoints 50)")
     ap.add_argument("--share-grids", action="store_true", help="store identical SDF volumes once (model library)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the oracle's CPU timing (cpu_baseline)")
     ap.add_argument("--host-pack", action="store_true", help="build the scene table with scenes.pack_table on the host (round 1-4) instead of on the device")
     ap.add_argument("--pipeline", type=int, default=0, help="parts of the engine's software pipeline (0: ChompEngine.layout's choice)")
     ap.add_argument("--layout-scenes", type=int, default=0, help="scene count ChompEngine.layout is evaluated for (0: the largest shard, ceil(total / world)); "
                     "a single-process run given a multi-rank job's number computes the same bits as that job")
     ap.add_argument("--goal-parts", type=int, default=0, help="workgroups per goal in the batch layout (0: the layout rule's choice)")
-    ap.add_argument("--regions", type=int, default=0, help="timed regions of --steps steps each (0: 1, or 5 when a region is shorter than 50 ms); ms_per_step is their median")
-    ap.add_argument("--no-plan", action="store_true", help="skip timing a full 70-iteration plan (ms_per_plan)")
-    ap.add_argument("--no-parity", action="store_true", help="skip the oracle check of three scenes after the timed region")
+    ap.add_argument("--regions", type=int, default=0, help="--full: timed regions of --steps steps each in all, the first being the headline's "
+                    "(0: 1, or 5-15 when a region is shorter than 50 ms); their median and spread ride beside ms_per_step")
+    ap.add_argument("--no-plan", action="store_true", help="--full: skip timing whole plans and the other shapes (ms_per_plan*)")
+    ap.add_argument("--no-parity", action="store_true", help="--full: skip the oracle check of three scenes after the timed region")
     ap.add_argument("--ol-alg", default="MD", help="goal-selection rule (reference default: MD, omg/config.py:67)")
     ap.add_argument("--dump-costs", default=None, help="rank 0 writes the gathered final per-scene costs to this .npy file (tests)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="rank 0 writes what the last timed step left (its scenes' trajectories, "
+                    "goal choice and costs, learner state, step info, the gathered final costs) as DIR/<name>.npy, float32 / float64")
+    ap.add_argument("--full", action="store_true", help="besides the headline: roofline, more regions, parity sample, plan timings, other "
+                    "shapes, CPU baseline (--no-plan / --no-parity / --no-cpu-baseline leave parts out)")
     args = ap.parse_args()
+    if args.regions and not args.full:
+        raise SystemExit("--regions belongs to --full: a plain run times exactly one region of --steps steps")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` typed plainly: start the N ranks as a CHILD process group (torch.distributed.run, one rank per
@@ -627,7 +667,8 @@ def main():
     # every 5th launch of the dominant kernel is bracketed by HIP events attached to the dispatch (all of them would cost
     # 1.7 % of the step time, a fifth 0.3 %); an odd stride, so that the samples alternate between the pipeline's parts
     stride = 5 if args.steps * parts >= 25 else 1  # a very short run still gets its launches timed
-    lib.omgx_timing_enable(stride)
+    if args.full:  # (the events feed the roofline block only)
+        lib.omgx_timing_enable(stride)
 
     def region():
         """EXACTLY --steps steps + the job's one collective, bracketed by barrier + synchronize on both sides; -> (this rank's
@@ -649,53 +690,57 @@ def main():
             mx = float(tmax.item())
         return el, mx, allc
 
-    # A region of the driver's size (20 steps of ~0.2 ms) is a few milliseconds: one such interval says little — and the first ones
-    # run while the GPU's clocks are still coming up (the goal-set launches of five successive 20-step regions: 179, 174, 173, 168,
-    # 166 us in the median; tools/trace_regions.py).  When the first region is shorter than 50 ms, more regions of the same --steps
-    # are timed — as many as it takes to time ~60 ms, between 5 and 15 — and ms_per_step is the MEDIAN region (the spread is
-    # reported beside it); `steps` stays what was asked for.
+    # The headline is ONE region of exactly --steps steps: ms_per_step = its wall time / --steps (the MAX over the ranks).
     first = region()
-    n_regions = args.regions if args.regions > 0 else (max(5, min(15, int(np.ceil(0.060 / max(first[1], 1e-6))))) if first[1] < 0.050 else 1)
-    # (first[1] is the MAX over the ranks: every rank computes the same number)
-    regs = [first] + [region() for _ in range(n_regions - 1)]
-    order = sorted(range(len(regs)), key=lambda i: regs[i][1])
-    mid = order[len(order) // 2]
-    elapsed_local, elapsed, allc = regs[mid]
-    region_ms = [r[1] / args.steps * 1e3 for r in regs]
+    elapsed_local, elapsed, allc = first
     if args.dump_costs and rank == 0:
-        np.save(args.dump_costs, regs[0][2].cpu().numpy())  # the FIRST region's costs: which region is the median depends on the clock
-    buf = (C.c_float * 4096)()
-    kinds = (C.c_int32 * 4096)()
-    nrec = lib.omgx_timing_collect(buf, kinds, 4096)
-    lib.omgx_timing_enable(0)
-
-    # every rank's own roofline block: its launch durations (HIP events), its scenes, its wall time — gathered so that an N-GPU
-    # line carries the achieved rates per GPU (north_star: "achieved ... vs roofline reported at 1/2/4/8")
-    durs = np.array([buf[i] for i in range(nrec)], dtype=np.float64)
-    kind = np.array([kinds[i] for i in range(nrec)])
-    goal_ms = durs[kind == 0]  # the goal-set launch (goal-set batch + trajectory layer) = the dominant kernel
-    avg_ms = float(goal_ms.mean()) if len(goal_ms) else elapsed_local / args.steps * 1e3  # no goal-set launch recorded (rules without a goal-set batch)
+        np.save(args.dump_costs, allc.cpu().numpy())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(Path(args.dump_outputs), eng, allc)
     P = model.points_per_link
     O_active = args.objects + 1
-    # N (32 + 128 O_active) algorithmic bytes for the N points of one launch — the goal-set batch
-    # plus the S x n x 150 points of the trajectory layer.  NOT a measure of what the kernel moves: 85 % of the (point,
-    # object) pairs retire in registers before any load and the rest hit L2.
-    pts_per_launch = (S * G * n * 10 * P + S * n * 10 * P) / parts  # a launch handles one part of the pipeline
-    alg_bytes = pts_per_launch * (32 + 128 * O_active)
-    from tools.roofline import roofline_block
-    roof = roofline_block(ROOT / "profiles" / "roofline_inputs.json", avg_ms, int(len(goal_ms)), stride, alg_bytes,
-                          {"scenes": S, "goals": G, "waypoints": n, "points_per_link": P, "grid": args.grid, "pipeline": parts, "objects": O_active},
-                          launches_per_step=parts, ms_per_step=elapsed_local / args.steps * 1e3)
-    per_rank = None
-    if dist_on:
-        import torch.distributed as dist
-        mine = {"rank": rank, "scenes": S, "ms_per_step": elapsed_local / args.steps * 1e3, "avg_launch_ms": avg_ms, "launches": int(len(goal_ms)),
-                "achieved": roof["achieved"], "frac": roof["frac"], "hbm_GBs": None if roof["hbm_real"] is None else roof["hbm_real"]["GBs"],
-                "algorithmic_equiv_GBs": roof["algorithmic_equiv_GBs"]}
-        per_rank = [None] * world
-        dist.all_gather_object(per_rank, mine)
-    parity = None
-    if not args.no_parity and rank == 0:
+
+    roof = per_rank = region_ms = parity = None
+    if args.full:
+        # A region of the driver's size (20 steps of ~0.2 ms) is a few milliseconds: one such interval says little — and the first ones
+        # run while the GPU's clocks are still coming up (the goal-set launches of five successive 20-step regions: 179, 174, 173, 168,
+        # 166 us in the median; tools/trace_regions.py).  When the first region is shorter than 50 ms, more regions of the same --steps
+        # are timed after it — as many as it takes to time ~60 ms, between 5 and 15 — and their median and spread are reported beside
+        # the headline.
+        n_regions = args.regions if args.regions > 0 else (max(5, min(15, int(np.ceil(0.060 / max(first[1], 1e-6))))) if first[1] < 0.050 else 1)
+        # (first[1] is the MAX over the ranks: every rank computes the same number)
+        regs = [first] + [region() for _ in range(n_regions - 1)]
+        region_ms = [r[1] / args.steps * 1e3 for r in regs]
+        mid = sorted(range(len(regs)), key=lambda i: regs[i][1])[len(regs) // 2]
+        mid_local_ms = regs[mid][0] / args.steps * 1e3  # this rank's step in the median region: what the launches sampled over all regions pair with
+        buf = (C.c_float * 4096)()
+        kinds = (C.c_int32 * 4096)()
+        nrec = lib.omgx_timing_collect(buf, kinds, 4096)
+        lib.omgx_timing_enable(0)
+
+        # every rank's own roofline block: its launch durations (HIP events), its scenes, its wall time — gathered so that an N-GPU
+        # line carries the achieved rates per GPU (north_star: "achieved ... vs roofline reported at 1/2/4/8")
+        durs = np.array([buf[i] for i in range(nrec)], dtype=np.float64)
+        kind = np.array([kinds[i] for i in range(nrec)])
+        goal_ms = durs[kind == 0]  # the goal-set launch (goal-set batch + trajectory layer) = the dominant kernel
+        avg_ms = float(goal_ms.mean()) if len(goal_ms) else mid_local_ms  # no goal-set launch recorded (rules without a goal-set batch)
+        # N (32 + 128 O_active) algorithmic bytes for the N points of one launch — the goal-set batch
+        # plus the S x n x 150 points of the trajectory layer.  NOT a measure of what the kernel moves: 85 % of the (point,
+        # object) pairs retire in registers before any load and the rest hit L2.
+        pts_per_launch = (S * G * n * 10 * P + S * n * 10 * P) / parts  # a launch handles one part of the pipeline
+        alg_bytes = pts_per_launch * (32 + 128 * O_active)
+        from tools.roofline import roofline_block
+        roof = roofline_block(ROOT / "profiles" / "roofline_inputs.json", avg_ms, int(len(goal_ms)), stride, alg_bytes,
+                              {"scenes": S, "goals": G, "waypoints": n, "points_per_link": P, "grid": args.grid, "pipeline": parts, "objects": O_active},
+                              launches_per_step=parts, ms_per_step=mid_local_ms)
+        if dist_on:
+            import torch.distributed as dist
+            mine = {"rank": rank, "scenes": S, "ms_per_step": mid_local_ms, "avg_launch_ms": avg_ms, "launches": int(len(goal_ms)),
+                    "achieved": roof["achieved"], "frac": roof["frac"], "hbm_GBs": None if roof["hbm_real"] is None else roof["hbm_real"]["GBs"],
+                    "algorithmic_equiv_GBs": roof["algorithmic_equiv_GBs"]}
+            per_rank = [None] * world
+            dist.all_gather_object(per_rank, mine)
+    if args.full and not args.no_parity and rank == 0:
         # the timed workload against the oracle: three scenes of this rank, the first three iterations of the plan the timed
         # region repeats (same pinned window), trajectories / final costs / chosen goals
         from oracle.check import engine_vs_oracle
@@ -710,7 +755,7 @@ def main():
 
     ms_per_plan = ms_plan_early = ms_single = ms_single_batch_layout = terminated = ms_graph_early = ms_graph_single = None
     share4 = scene_upd = drop_in = cfg5 = scaling = coll = persist = plans_other = None
-    if not args.no_plan and rank == 0 and world == 1:
+    if args.full and not args.no_plan and rank == 0 and world == 1:
         share4 = rank_share_config4(dev, args.ol_alg)
         cfg5 = config5_shape(dev, args.ol_alg)
         plans_other = (shape_plan_timing(dev, args.ol_alg, 13, 128), shape_plan_timing(dev, args.ol_alg, 16, 64, n=50, objects=12))
@@ -718,7 +763,7 @@ def main():
         persist = persistent_launch_timing(dev, cfg, model, batch, start, goals, args.ol_alg)
         scene_upd = scene_update_timing(dev, cfg, model, host_batch(), start, goals, args.ol_alg)
         drop_in = drop_in_plan_timing(dev, args.ol_alg)
-    if not args.no_plan and rank == 0:
+    if args.full and not args.no_plan and rank == 0:
         ms_per_plan = float("inf")
         for _ in range(2):  # best of 2: the first plan pays one-off costs (code-object load of the 30 window sizes)
             eng2 = ChompEngine.auto(model, batch, copy.deepcopy(cfg), start, goals, layout_scenes=layout_scenes, device=dev, ol_alg=args.ol_alg)
@@ -789,8 +834,6 @@ def main():
             "steps": args.steps,
             "warmup": args.warmup,
             "ms_per_step": elapsed / args.steps * 1e3,
-            "ms_per_step_spread": [min(region_ms), max(region_ms)],  # over the timed regions of --steps steps each; ms_per_step / value = the median region
-            "regions": len(region_ms),
             "higher_is_better": True,
             "scaling": "strong" if strong else "weak",
             "vs_baseline": None,
@@ -803,8 +846,12 @@ def main():
                        "goal_selection": f"{args.ol_alg} on device (omgx_goal_update_optimize)", "launches_per_iteration": 2 * parts,
                        "pipeline_parts": parts, "layout": layout,
                        "top_k_collision": cfg.top_k_collision, "plan_restart_every_steps": cfg.optim_steps},
-            "roofline": roof,
         }
+        if args.full:
+            out["ms_per_step_median_region"] = sorted(region_ms)[len(region_ms) // 2]  # over the timed regions of --steps steps each, the headline's first
+            out["ms_per_step_spread"] = [min(region_ms), max(region_ms)]
+            out["regions"] = len(region_ms)
+            out["roofline"] = roof
         if parity is not None:
             out["parity_sample"] = parity
         out["setup_ms"] = dict(setup, what=("pack_table_ms: the scene table (records, SDF pool, fitted influence regions) — " + ("scenes.pack_table on the host" if args.host_pack else "built on the device, see scene_table") +
@@ -839,9 +886,9 @@ def main():
             out["ms_per_plan_single_scene_batch_layout"] = ms_single_batch_layout  # the same plan with the launches of the batched path
             out["ms_per_plan_early_stop_graph"] = ms_graph_early  # the early-stop plan replayed as one HIP graph (capture_plan)
             out["ms_per_plan_single_scene_graph"] = ms_graph_single
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(cfg, model, host_batch(), start, goals, n)
-        if world == 1 and not dist_on and not args.no_plan:
+        if args.full and world == 1 and not dist_on and not args.no_plan:
             coll = collective_cost(dev, S)
             if coll is not None:
                 out["collective"] = coll  # the job's one collective (final costs): what weak scaling pays on top of the ranks' own steps

@@ -70,3 +70,57 @@ def test_issue_price_list_comes_from_the_residency_checked_calibration():
     cycles, parts = issue_cycles(mix, 20.0e6, cal)
     assert parts["OTHER"]["count"] == 20.0e6 - len(MIX_CLASSES) * 1.0e6
     assert cycles == sum(p["count"] * p["cycles_each"] for p in parts.values()) and 2.0 * 20.0e6 < cycles < 4.0 * 20.0e6
+
+
+def test_dump_outputs_writes_float_arrays_and_samples_scenes_beyond_the_limit(tmp_path, monkeypatch):
+    """bench.dump_outputs (--dump-outputs): one .npy per output of the timed step, float32 kept, everything else float64; beyond
+    the size limit a fixed, seeded sample of scenes — the same rows on every call — with their indices beside them."""
+    import torch
+    import bench
+
+    class Engine:  # the attributes the timed step leaves behind, on the host
+        S, G, n = 5, 4, 30
+
+        def __init__(self):
+            g = torch.Generator().manual_seed(0)
+            S, G, n = self.S, self.G, self.n
+            self.traj, self.grad = torch.rand((S, n, 9), generator=g, dtype=torch.float64), torch.rand((S, n, 9), generator=g, dtype=torch.float64)
+            self.cost_traj, self.info = torch.rand((S, n), generator=g, dtype=torch.float64), torch.rand((S, 16), generator=g, dtype=torch.float64)
+            self.goal_idx, self.end = torch.arange(S, dtype=torch.int32), torch.rand((S, 9), generator=g, dtype=torch.float64)
+            self.goal_cost, self.cost_vec = torch.rand((S, G), generator=g), torch.rand((S, G), generator=g, dtype=torch.float64)
+            self.learner_state = torch.rand((S, 7 * G + 10), generator=g, dtype=torch.float64)
+
+        def join(self):
+            pass
+
+        def goal_cost_total(self):
+            return self.goal_cost
+
+    eng, costs = Engine(), torch.arange(5, dtype=torch.float64)
+    shapes = bench.dump_outputs(tmp_path / "all", eng, costs)
+    assert shapes["traj"] == [5, 30, 9] and shapes["goal_cost"] == [5, 4] and shapes["final_costs"] == [5] and "scene_index" not in shapes
+    for name in shapes:
+        a = np.load(tmp_path / "all" / f"{name}.npy")
+        assert a.dtype == (np.float32 if name == "goal_cost" else np.float64), name
+    assert np.array_equal(np.load(tmp_path / "all" / "goal_idx.npy"), np.arange(5.0))
+    assert np.array_equal(np.load(tmp_path / "all" / "traj.npy"), eng.traj.numpy())
+    one_scene = sum(t.numel() * t.element_size() * (2 if t.dtype == torch.int32 else 1)
+                    for t in (eng.traj, eng.grad, eng.cost_traj, eng.info, eng.goal_idx, eng.end, eng.goal_cost, eng.cost_vec, eng.learner_state)) / 5
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", int(3.5 * one_scene))
+    a = bench.dump_outputs(tmp_path / "a", eng, costs)
+    b = bench.dump_outputs(tmp_path / "b", eng, costs)
+    assert a == b and a["traj"][0] == a["scene_index"][0] < 5 and a["final_costs"] == [5]
+    rows = np.load(tmp_path / "a" / "scene_index.npy").astype(int)
+    assert np.array_equal(rows, np.load(tmp_path / "b" / "scene_index.npy")) and np.all(np.diff(rows) > 0)
+    assert np.array_equal(np.load(tmp_path / "a" / "traj.npy"), eng.traj.numpy()[rows])
+    assert sum((tmp_path / "a" / f"{k}.npy").stat().st_size - 128 for k in a) <= bench.DUMP_LIMIT_BYTES
+
+
+def test_regions_belong_to_the_full_run():
+    """A plain run times exactly one region of --steps steps: --regions without --full is refused before any GPU work."""
+    import subprocess
+    import sys
+    from pathlib import Path
+    root = Path(__file__).resolve().parents[1]
+    r = subprocess.run([sys.executable, str(root / "bench.py"), "--steps", "3", "--regions", "4"], capture_output=True, text=True, timeout=120)
+    assert r.returncode != 0 and "--full" in r.stderr and not r.stdout.strip()

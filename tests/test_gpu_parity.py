@@ -1552,7 +1552,7 @@ def test_bench_two_ranks_on_the_config4_share_shape(tmp_path):
     import subprocess
     import sys
     root = Path(__file__).resolve().parents[1]
-    common = ["--total-scenes", "25", "--goals", "128", "--steps", "6", "--warmup", "2", "--no-plan", "--no-cpu-baseline", "--no-parity"]
+    common = ["--total-scenes", "25", "--goals", "128", "--steps", "6", "--warmup", "2", "--full", "--no-plan", "--no-cpu-baseline", "--no-parity"]
     env = dict(os.environ, OMGX_BENCH_BACKEND="gloo", MASTER_ADDR="127.0.0.1")
     one, two = tmp_path / "one.npy", tmp_path / "two.npy"
     r1 = subprocess.run([sys.executable, str(root / "bench.py"), "--gpus", "1", *common, "--layout-scenes", "13", "--dump-costs", str(one)], env=env,
@@ -1581,9 +1581,10 @@ def test_bench_two_ranks_on_the_config4_share_shape(tmp_path):
     assert j["roofline"]["profiled_workload"]["goals"] == 128 and j["roofline"]["profiled_workload"]["scenes"] == 13
     assert j["roofline"]["counts_scaled"] == pytest.approx(1.0) and j1["roofline"]["frac"] is not None
     assert "cpu_baseline" not in j  # an N = 1 field
-    # the timed regions: `steps` is what was asked for, ms_per_step the median region, the spread beside it
+    # the timed regions: `steps` is what was asked for, ms_per_step the first region (the headline), the median and spread beside it
     for line in (j, j1):
         lo, hi = line["ms_per_step_spread"]
         assert 5 <= line["regions"] <= 15 and lo <= line["ms_per_step"] <= hi and line["steps"] == 6
+        assert lo <= line["ms_per_step_median_region"] <= hi
         assert abs(line["value"] - 25 * 6 / (line["ms_per_step"] * 6e-3)) <= 1e-6 * line["value"]
         assert line["setup_ms"]["pack_table_ms"] > 0 and line["setup_ms"]["engine_init_ms"] > 0

@@ -281,7 +281,7 @@ def test_bench_collective_path_runs_over_rccl_with_one_rank(tmp_path):
     all_gather_into_tensor of the final costs on DEVICE tensors and the MAX all-reduce of the timing all run for real (the
     2-rank test shares the one GPU over gloo and never touches RCCL).  Costs equal the plain single-process run bit for bit;
     the line carries the per-rank roofline list of an N-GPU line."""
-    common = ["--total-scenes", "6", "--goals", "8", "--grid", "24", "--steps", "4", "--warmup", "1", "--no-plan", "--no-cpu-baseline", "--no-parity"]
+    common = ["--total-scenes", "6", "--goals", "8", "--grid", "24", "--steps", "4", "--warmup", "1", "--full", "--no-plan", "--no-cpu-baseline", "--no-parity"]
     env = {k: v for k, v in os.environ.items() if k not in ("OMGX_BENCH_BACKEND", "RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT")}
     env["MASTER_ADDR"] = "127.0.0.1"
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
@@ -311,7 +311,7 @@ def test_bench_launches_its_own_ranks_when_typed_plainly(tmp_path):
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT")}
     env["OMGX_BENCH_BACKEND"] = "gloo"
     r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "2", "--total-scenes", "5", "--goals", "8", "--grid", "24", "--steps", "3",
-                        "--warmup", "1", "--no-plan", "--no-cpu-baseline", "--no-parity"], env=env, capture_output=True, text=True, timeout=900)
+                        "--warmup", "1", "--full", "--no-plan", "--no-cpu-baseline", "--no-parity"], env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, (r.stdout[-1000:], r.stderr[-3000:])
     j = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
     assert j["n_gpus"] == 2 and j["steps"] == 3 and len(j["roofline"]["per_rank"]) == 2

@@ -2,7 +2,7 @@
 # Collect the rocprofv3 evidence for bench.py on the GPU box (run through gpurun from the repo root):
 #   gpurun --timeout 1500 -- 'bash tools/collect_profiles.sh r02h'
 # Writes into gpurun_out/ (copy what is to be judged into profiles/, then `python tools/roofline.py --tag <tag>`):
-#   <tag>_bench.json            the unprofiled default bench.py line (run LAST: its roofline block uses this collection's counts)
+#   <tag>_bench.json            the unprofiled bench.py --full line (run LAST: its roofline block uses this collection's counts)
 #   <tag>_kernel_stats.csv      rocprofv3 --kernel-trace --stats of the same command
 #   <tag>_pmc_<SET>.csv         per-kernel means of every counter set (separate --pmc passes, kernel-trace only; MEM_* = TA / TCP / TD)
 #   <tag>_workload.json         the workload the counts belong to
@@ -64,8 +64,8 @@ fi
 # the unprofiled bench line LAST, with the per-launch counts of THIS collection behind its roofline block
 cp $O/${TAG}_*.csv $O/${TAG}_*.json $R/profiles/ 2>/dev/null
 (cd $R && python3 tools/roofline.py --tag $TAG ${OTHER:+--other} > $O/${TAG}_roofline_inputs.log 2>&1; cp profiles/roofline_inputs.json $O/${TAG}_roofline_inputs.json)
-if [ -z "$BENCH_ARGS" ]; then python3 $R/bench.py > $O/${TAG}_bench.json 2> $O/${TAG}_bench.log
-else python3 $R/bench.py $BENCH_ARGS --no-plan --no-cpu-baseline > $O/${TAG}_bench.json 2> $O/${TAG}_bench.log; fi
+if [ -z "$BENCH_ARGS" ]; then python3 $R/bench.py --full > $O/${TAG}_bench.json 2> $O/${TAG}_bench.log
+else python3 $R/bench.py $BENCH_ARGS --full --no-plan --no-cpu-baseline > $O/${TAG}_bench.json 2> $O/${TAG}_bench.log; fi
 head -4 $O/${TAG}_kernel_stats.csv | cut -c1-160
 grep goalset $O/${TAG}_pmc_*.csv | cut -c1-200
 cut -c1-1200 $O/${TAG}_bench.json

@@ -3,7 +3,7 @@
 # ChompEngine.layout chose, parity sample ok.   gpurun -- 'bash tools/sensitivity.sh > gpurun_out/<tag>_sensitivity.txt'
 cd ${GRAFT_REPO_ROOT:-$(pwd)}
 while IFS= read -r a; do
-  python3 bench.py $a --steps 100 --no-plan --no-cpu-baseline 2>/dev/null | python3 -c "
+  python3 bench.py $a --full --steps 100 --no-plan --no-cpu-baseline 2>/dev/null | python3 -c "
 import sys, json
 d = json.loads(sys.stdin.read().strip().splitlines()[-1])
 print('sens $a:', round(d['ms_per_step'], 4), round(d['value']), d['config'].get('layout'), d['parity_sample']['ok'])"

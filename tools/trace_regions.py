@@ -1,5 +1,5 @@
 """Where does a timed region of bench.py spend what it costs besides its steps?  From a rocprofv3 --kernel-trace CSV of a short-region run
-(e.g. --steps 20 --regions 5): the regions (separated by idle gaps > --gap us), each one's GPU span, and the durations / start
+(e.g. --full --steps 20 --regions 5): the regions (separated by idle gaps > --gap us), each one's GPU span, and the durations / start
 offsets of its first goal-set and update launches beside the steady state's.
     python tools/trace_regions.py <kernel_trace.csv> [--gap 150]"""
 import argparse
