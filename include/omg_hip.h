@@ -617,6 +617,36 @@ int omgx_plan_persistent(const double* robot, int32_t n_points, const omgx_objec
 int omgx_plan_persistent_status(const void* workspace, int32_t num_scenes, int32_t* h_status, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * (10) omgx_goal_ik (ABI 12)
+ * Replaces the IK stage of Planner.solve_goal_set_ik (omg/planner.py:17-86, 296-455): per chain (grasp n, seed k) the
+ * reference's solve_one_pose_ik, with robot_kinematics.inverse_kinematics (ycb_render/robotPose/robot_pykdl.py:257-290) =
+ * KDL ChainIkSolverPos_NR_JL (maxiter, eps) over ChainIkSolverVel_pinv (singular values < pinv_eps dropped), panda_link0 ->
+ * panda_hand (link 7 before center_offset), radians, the arm limits of the blob (padded).  One lane per chain, float64.
+ *   targets      [N][T][12]  hand poses (rotation rows, translation: the omgx_pose_table layout) of standoff k = 0..T-1 of each
+ *                grasp (k = 0: the grasp itself); without standoff T must be 1
+ *   grasp_begin  [S+1] device, h_grasp_begin [S+1] host, same values: scene s owns grasps [grasp_begin[s], grasp_begin[s+1]);
+ *                0 = grasp_begin[0] <= ... <= grasp_begin[S] = N (checked on the host copy)
+ *   seeds        [S][K][7]   the seeds of scene s in the order they are tried (traj.start[:7], then the anchor seeds)
+ *   use_standoff 1: solve pose T-1 from the seed, then poses 0..T-1 in turn, each from the previous solution; accept the chain when
+ *                the Frobenius norm of the [T-1][7] difference of the T solutions is < accept_diff.  0: one solve of pose 0.
+ *   attached     0 / 1, the reference's flag: it only reverses the order of the T solutions, which the caller does (the Frobenius
+ *                test does not depend on the order), so the device results are the same either way
+ *   status       [N][K] int32 out: 0 accepted, -1 solved but rejected by accept_diff, j > 0: solve j - 1 failed (j = 1: the first
+ *                solve, i.e. the standoff pre-solve or the only solve; j = 2 + k: the chained solve of pose k)
+ *   solutions    [N][K][T][7] out: the solution of pose k in slot k (in pose order, not reversed); the joint vector a failed solve
+ *                ended with in its slot; slots not reached are 0.  Without standoff, slot 0 holds the only solve's result.
+ *   iterations   optional [N][K][1+T] int32 out (with standoff; [N][K][1] without): updates each solve made (max_iter = failed,
+ *                -1 = not run), entry 0 the first solve.
+ * Limits: 1 <= T <= OMGX_IK_MAX_TAIL, 1 <= K <= OMGX_IK_MAX_SEEDS, 1 <= max_iter <= 100000, eps, pinv_eps >= 0.
+ * ------------------------------------------------------------------------------------------- */
+#define OMGX_IK_MAX_TAIL 16
+#define OMGX_IK_MAX_SEEDS 64
+int omgx_goal_ik(const double* robot, int32_t n_points, const double* targets, const int32_t* grasp_begin,
+                 const int32_t* h_grasp_begin, int32_t num_scenes, int32_t num_grasps, const double* seeds, int32_t num_seeds,
+                 int32_t T, int32_t use_standoff, int32_t attached, int32_t max_iter, double eps, double pinv_eps,
+                 double accept_diff, int32_t* status, double* solutions, int32_t* iterations, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Diagnostics
  * ------------------------------------------------------------------------------------------- */
 const char* omgx_last_error(void); /* thread-local text of the last OMGX_ERR_LAUNCH               */

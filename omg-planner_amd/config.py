@@ -59,6 +59,16 @@ class Config:
         self.traj_max_step = 50           # config.py:98
         self.traj_min_step = 2            # config.py:99
         self.base_link = "panda_link0"
+        # -- goal-set IK (config.py:71-102; goal_ik.py)
+        self.ik_seed_num = 12             # anchor seeds tried after traj.start
+        self.standoff_dist = 0.08
+        self.ik_parallel = True           # the reference's default path (it never solves the last grasp)
+        self.increment_iks = False        # not supported (draws from np.random)
+        self.augment_flip_grasp = True
+        self.remove_flip_grasp = True
+        self.target_hand_filter_angle = 120
+        self.y_upsample = False
+        self.z_upsample = True            # read by load_grasp_set for placements only
         # -- scheduled by Optimizer.update (optimizer.py:68-80)
         self.obstacle_weight = self.base_obstacle_weight
         self.smoothness_weight = self.smoothness_base_weight

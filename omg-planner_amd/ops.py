@@ -576,6 +576,34 @@ def pose_table(robot, P, configs: torch.Tensor, out: "torch.Tensor | None" = Non
     return out
 
 
+def goal_ik(robot, P, targets: torch.Tensor, grasp_begin, seeds: torch.Tensor, use_standoff: bool = True, attached: bool = False,
+            max_iter: int = 100, eps: float = 1e-6, pinv_eps: float = 1e-5, accept_diff: float = 2.0, want_iterations: bool = False):
+    """omgx_goal_ik: targets [N,T,12] f64 (omgx_pose_table layout; T = 1 without standoff), grasp_begin [S+1] (host ints: scene s owns
+    grasps grasp_begin[s]:grasp_begin[s+1]), seeds [S,K,7] f64 -> (status [N,K] int32, solutions [N,K,T,7] f64 in pose order,
+    iterations [N,K,1+T] / [N,K,1] int32 | None).  Enqueued on the current stream."""
+    _need(targets, torch.float64, "targets")
+    _need(seeds, torch.float64, "seeds")
+    dev = targets.device
+    if targets.dim() != 3 or targets.shape[2] != 12:
+        raise _lib.OmgHipError("targets must be [N, T, 12]")
+    N, T = int(targets.shape[0]), int(targets.shape[1])
+    h_begin = np.ascontiguousarray(np.asarray(grasp_begin, dtype=np.int32))
+    S = h_begin.size - 1
+    if S < 0 or seeds.dim() != 3 or seeds.shape[0] != S or seeds.shape[2] != 7:
+        raise _lib.OmgHipError("seeds must be [S, K, 7] with S = len(grasp_begin) - 1")
+    K = int(seeds.shape[1])
+    d_begin = torch.from_numpy(h_begin).to(dev)
+    status = torch.empty((N, K), dtype=torch.int32, device=dev)
+    sols = torch.empty((N, K, T, 7), dtype=torch.float64, device=dev)
+    its = torch.empty((N, K, 1 + T if use_standoff else 1), dtype=torch.int32, device=dev) if want_iterations else None
+    with torch.cuda.device(dev):
+        check(_lib.lib().omgx_goal_ik(_ptr(robot), P, _ptr(targets), _ptr(d_begin), h_begin.ctypes.data_as(C.POINTER(C.c_int32)), S, N,
+                                      _ptr(seeds), K, T, int(bool(use_standoff)), int(bool(attached)), int(max_iter), float(eps),
+                                      float(pinv_eps), float(accept_diff), _ptr(status), _ptr(sols), _ptr(its), _stream()),
+              "omgx_goal_ik")
+    return status, sols, its
+
+
 def chomp_optimize(robot, params: ChompParams, traj, start, end, goal, goal_point, pot, pgrad, col, active=None, out=None,
                    aux=None, stop_on_terminate=False):
     """In-place step on traj [S,n,9] f64 -> grad [S,n,9], cost_traj [S,n], info [S,16] (f64).

@@ -1,0 +1,241 @@
+"""Goal-set IK without a GPU: the CPU restatement (tests/ik_restatement.py) against independent kinematics and the reference's
+own pipeline (tests/golden/ik_*.npz, tests/golden/make_ik_golden.py), goal_ik.py's pose preparation against the fixtures'
+prepared targets, omgx_goal_ik's argument checks, and the IK kernel's register budget."""
+from __future__ import annotations
+
+import ctypes as C
+import re
+import shutil
+import subprocess
+from pathlib import Path
+
+import numpy as np
+import pytest
+
+import ik_restatement as ikr
+from omg_planner_amd import robot as rb
+from omg_planner_amd import scenes as sc
+
+ROOT = Path(__file__).resolve().parents[1]
+GOLDEN = ROOT / "tests" / "golden"
+FIXTURES = sorted(GOLDEN.glob("ik_*.npz"))
+HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+
+
+def load(path):
+    with np.load(path, allow_pickle=False) as d:
+        return {k: d[k] for k in d.files}
+
+
+@pytest.fixture(scope="module")
+def model():
+    return rb.PandaModel()
+
+
+def reachable_targets(model, B, seed):
+    rng = np.random.RandomState(seed)
+    lo, hi = ikr.limits(model)
+    q = rng.uniform(lo, hi, (B, 7))
+    R, t, _, _ = ikr.hand_kinematics(model, q)
+    return q, R, t
+
+
+def test_jacobian_matches_central_differences(model):
+    q, R, t = reachable_targets(model, 256, 1)
+    _, _, z, p = ikr.hand_kinematics(model, q)
+    J = ikr.jacobian(t, z, p)
+    h = 1e-5
+    for i in range(7):
+        qp, qm = q.copy(), q.copy()
+        qp[:, i] += h
+        qm[:, i] -= h
+        Rp, tp, _, _ = ikr.hand_kinematics(model, qp)
+        Rm, tm, _, _ = ikr.hand_kinematics(model, qm)
+        np.testing.assert_allclose(J[:, :3, i], (tp - tm) / (2 * h), rtol=0, atol=1e-7)
+        W = np.einsum("bij,bkj->bik", (Rp - Rm) / (2 * h), R)  # dR/dq R^T = [w]x
+        np.testing.assert_allclose(J[:, 3:, i], np.stack([W[:, 2, 1], W[:, 0, 2], W[:, 1, 0]], -1), rtol=0, atol=1e-7)
+
+
+def test_solver_arithmetic_is_the_definition(model):
+    """The solver's own FK / Jacobian (fk_jacobian, in omg_ik.hip's order through the blob's tables) equals the 4x4 definition, and
+    its one-sided Jacobi pseudo-inverse equals the truncated SVD pseudo-inverse (KDL's ChainIkSolverVel_pinv), dropping the same
+    singular values."""
+    q, R, t = reachable_targets(model, 512, 4)
+    _, _, z, p = ikr.hand_kinematics(model, q)
+    R2, t2, W = ikr.fk_jacobian(model, q)
+    assert np.abs(R2.reshape(-1, 3, 3) - R).max() <= 1e-15 and np.abs(t2 - t).max() <= 1e-15
+    J = ikr.jacobian(t, z, p)
+    assert np.abs(W - J).max() <= 1e-15
+    rng = np.random.RandomState(5)
+    d = rng.normal(size=(512, 6))
+    S = np.linalg.svd(J, compute_uv=False)
+    good = S.min(axis=1) > 1e-2
+    np.testing.assert_allclose(ikr.pinv_step_jacobi(J[good], d[good]), ikr.pinv_step(J[good], d[good]), rtol=0, atol=1e-11)
+    # a rank-deficient J (two equal rows, one row scaled below pinv_eps): the same truncation
+    Jd = J[:64].copy()
+    Jd[:, 5] = Jd[:, 4]
+    Jd[:, 3] *= 1e-7
+    np.testing.assert_allclose(ikr.pinv_step_jacobi(Jd, d[:64]), ikr.pinv_step(Jd, d[:64]), rtol=0, atol=1e-9)
+
+
+def test_reproducible_transcendentals_are_faithful():
+    """ik_sincos / ik_atan2 (the plain-IEEE sin, cos and atan2 omg_ik.hip and the restatement share) agree with the C library's to
+    an ulp or two: they exist for bit-reproducibility, not as an approximation."""
+    rng = np.random.RandomState(6)
+    x = np.concatenate([rng.uniform(-8, 8, 400000), rng.uniform(-1e-3, 1e-3, 1000), [0.0, np.pi, -np.pi / 2, 2.8973, -3.0718]])
+    s, c = ikr.ik_sincos(x)
+    assert np.abs(s - np.sin(x)).max() <= 2.3e-16 and np.abs(c - np.cos(x)).max() <= 2.3e-16
+    y, xx = np.abs(rng.normal(size=400000)), rng.normal(size=400000)
+    a, r = ikr.ik_atan2(y, xx), np.arctan2(y, xx)
+    assert np.abs(a - r).max() <= 2 * np.spacing(np.pi)
+    edge_y, edge_x = np.array([0.0, 0.0, 1.0, 1e-300, 1.0, 0.0]), np.array([1.0, -1.0, 0.0, -1.0, 1e-300, 0.0])
+    np.testing.assert_allclose(ikr.ik_atan2(edge_y, edge_x), np.arctan2(edge_y, edge_x), rtol=0, atol=1e-15)
+
+
+def test_rotvec_branches():
+    rng = np.random.RandomState(2)
+    # general angles: exp(rotvec) reproduces R
+    w = rng.normal(size=(64, 3))
+    w *= (rng.uniform(0.1, 3.0, 64) / np.linalg.norm(w, axis=1))[:, None]
+    th = np.linalg.norm(w, axis=1)
+    k = w / th[:, None]
+    Kx = np.zeros((64, 3, 3))
+    Kx[:, 0, 1], Kx[:, 0, 2], Kx[:, 1, 2] = -k[:, 2], k[:, 1], -k[:, 0]
+    Kx -= Kx.transpose(0, 2, 1)
+    R = np.eye(3) + np.sin(th)[:, None, None] * Kx + (1 - np.cos(th))[:, None, None] * Kx @ Kx
+    np.testing.assert_allclose(ikr.rotvec(R), w, atol=1e-12)
+    # identity -> 0; a half turn -> pi times the axis
+    assert np.array_equal(ikr.rotvec(np.eye(3)[None]), np.zeros((1, 3)))
+    np.testing.assert_allclose(ikr.rotvec(np.diag([1.0, -1.0, -1.0])[None]), [[np.pi, 0, 0]], atol=1e-15)
+    np.testing.assert_allclose(ikr.rotvec(np.diag([-1.0, -1.0, 1.0])[None]), [[0, 0, np.pi]], atol=1e-15)
+
+
+def test_restatement_successes_converge_within_limits(model):
+    _, R, t = reachable_targets(model, 200, 3)
+    seeds = np.concatenate([rb.HOME_CONFIG[None, :7], ikr.ANCHOR_SEEDS[:12]])
+    TR, Tt, S = np.repeat(R, 13, 0), np.repeat(t, 13, 0), np.tile(seeds, (200, 1))
+    q, ok, it = ikr.solve(model, TR, Tt, S)
+    assert 0.2 < ok.mean() < 1.0 and (it[ok] < ikr.MAX_ITER).all() and (it[~ok] == ikr.MAX_ITER).all()
+    lo, hi = ikr.limits(model)
+    qs = q[ok]
+    assert (qs >= lo).all() and (qs <= hi).all()
+    # an independent FK (scenes.hand_pose: position and approach axis)
+    pos, zax = sc.hand_pose(model, np.concatenate([qs, np.full((len(qs), 2), 0.04)], axis=1))
+    assert np.abs(pos - Tt[ok]).max() <= 1e-6
+    assert np.abs(zax - TR[ok][:, :, 2]).max() <= 2e-6
+
+
+def _post_process(model, goals, reach, start, d):
+    """solve_and_process_ik's flip augmentation and filter (planner.py:249-294), numpy, on the restatement's kinematics."""
+    if len(goals) == 0 or d["attached"]:
+        return goals, reach
+    goals, reach = np.array(goals), np.array(reach)
+    pad = 0.2
+
+    def flip(g):
+        g = g.copy()
+        j = g[..., -3]
+        g[..., -3] = np.where(j < 0, j + np.pi, np.where(j > 0, j - np.pi, j))
+        return g, (g[..., -3] < 2.8973 - pad) & (g[..., -3] > -2.8973 + pad)
+
+    fg, m = flip(goals)
+    fr, _ = flip(reach)
+    goals, reach = np.concatenate([goals, fg[m]]), np.concatenate([reach, fr[m]])
+    Rs = ikr.hand_kinematics(model, start[None, :7])[0][0]
+    if d["use_standoff"]:
+        t = np.linspace(0, 1, 7)[1:-1]
+        pts = (reach[:, -1][:, None] - start[None, None]) * t[None, :, None] + start[None, None]
+    else:
+        pts = goals[:, None]
+    R = ikr.hand_kinematics(model, pts.reshape(-1, 9)[:, :7])[0].reshape(len(goals), -1, 3, 3)
+    tr = np.trace(R @ Rs.T, axis1=2, axis2=3)
+    with np.errstate(invalid="ignore"):
+        ang = np.abs(np.arccos((tr - 1) / 2)) * 180 / np.pi
+    xz = R[..., 2, 0] / np.linalg.norm(R[..., :, 0], axis=-1)
+    keep = ~((ang > 120) | (xz < -0.3)).any(-1)
+    return goals[keep], reach[keep]
+
+
+@pytest.mark.parametrize("path", FIXTURES, ids=[p.stem for p in FIXTURES])
+def test_restatement_reproduces_reference_fixture(model, path):
+    d = load(path)
+    T = int(d["reach_tail_length"])
+    start = d["start"]
+    seeds = start[None, :7] if d["one_trial"] else np.concatenate([start[None, :7], ikr.ANCHOR_SEEDS[:int(d["ik_seed_num"])]])
+    targets = d["targets"]  # the grasps the reference solved (its parallel path never solves the last one)
+    tg = (targets if d["use_standoff"] else targets[:, :1]).copy()
+    for g in range(tg.shape[0]):
+        for k in range(tg.shape[1]):  # as the reference hands them to KDL (pack_pose -> quaternion)
+            tg[g, k, :3, :3] = ikr.kdl_target(tg[g, k])
+    reach, goals = ikr.solve_grasps(model, tg, seeds, bool(d["use_standoff"]), bool(d["attached"]))
+    if str(d["stage"]) == "process":
+        goals, reach = _post_process(model, goals, reach, start, d)
+    goals = np.array(goals).reshape(-1, 9)
+    reach = np.array(reach).reshape((-1, T, 9) if d["use_standoff"] else (-1, 9))
+    assert goals.shape == d["grasps"].shape and reach.shape == d["reach_grasps"].shape
+    np.testing.assert_allclose(goals, d["grasps"], rtol=0, atol=1e-9)
+    np.testing.assert_allclose(reach, d["reach_grasps"], rtol=0, atol=1e-9)
+
+
+def test_fixtures_cover_the_issue_cases():
+    names = {p.stem for p in FIXTURES}
+    assert len(names) >= 8
+    ds = [load(p) for p in FIXTURES]
+    for key in ("use_standoff", "attached", "ik_parallel", "z_upsample", "y_upsample", "one_trial", "obj_coord"):
+        assert {int(d[key]) for d in ds} == {0, 1}, key
+    assert any(len(d["grasps"]) > 0 for d in ds) and all(d["grasps"].size < 20000 for d in ds)
+
+
+@pytest.mark.parametrize("path", FIXTURES, ids=[p.stem for p in FIXTURES])
+def test_pose_preparation_matches_fixture(path):
+    from omg_planner_amd import goal_ik
+    d = load(path)
+    p = goal_ik.prepare_poses(d["pose_grasp"], d["object_pose"], bool(d["obj_coord"]), bool(d["z_upsample"]), bool(d["y_upsample"]),
+                              int(d["reach_tail_length"]), float(d["standoff_dist"]), bool(d["use_standoff"]), device="cpu").numpy()
+    tg = d["targets"] if d["use_standoff"] else d["targets"][:, :1]  # without standoff the reference's T poses are the grasp
+    assert p.shape[0] == tg.shape[0] + int(d["ik_parallel"])  # the parallel path never hands the last grasp to a solver
+    np.testing.assert_allclose(p[:tg.shape[0]], tg, rtol=0, atol=1e-12)
+
+
+def test_increment_iks_is_refused():
+    from omg_planner_amd import goal_ik
+    from omg_planner_amd.config import Config
+    with pytest.raises(ValueError, match="increment_iks"):
+        goal_ik.solve_raw(rb.PandaModel(), [np.eye(4)[None]], np.eye(4)[None], rb.HOME_CONFIG[None], Config(increment_iks=True),
+                          device="cpu")
+
+
+def test_goal_ik_argument_checks_without_gpu():
+    from omg_planner_amd import _lib
+    lib = _lib.lib()
+    d = C.c_void_p(4096)  # never dereferenced: every call below fails its checks first
+
+    def call(S=2, N=4, begin=(0, 2, 4), K=13, T=5, standoff=1, attached=0, max_iter=100, eps=1e-6, out=d, sols=d, seeds=d):
+        hb = (C.c_int32 * len(begin))(*begin) if begin is not None else None
+        return lib.omgx_goal_ik(d, 15, d, d, hb, S, N, seeds, K, T, standoff, attached, max_iter, eps, 1e-5, 2.0, out, sols, None, None)
+
+    INV = _lib.OMGX_ERR_INVALID
+    assert call(S=-1) == INV and call(N=-1) == INV
+    assert call(T=0) == INV and call(T=17) == INV and call(T=5, standoff=0) == INV
+    assert call(begin=(0, 3, 2), N=2) == INV and call(begin=(0, 2, 3)) == INV and call(begin=(1, 2, 4)) == INV
+    assert call(begin=None) == INV
+    assert call(out=None) == INV and call(sols=None) == INV and call(seeds=None) == INV
+    assert call(K=0) == INV and call(max_iter=0) == INV and call(eps=-1.0) == INV and call(attached=2) == INV
+    assert call(S=2, N=0, begin=(0, 0, 0)) == _lib.OMGX_OK  # nothing to solve: nothing launched
+
+
+@pytest.mark.skipif(not Path(HIPCC).exists(), reason="hipcc not installed")
+def test_ik_kernel_does_not_spill(tmp_path):
+    """k_goal_ik keeps a chain's whole state (the Jacobian's rows, the rotated residual, q, the target) in registers: the
+    compiled kernel has no scratch (256 VGPRs + AGPRs, one wave per SIMD)."""
+    out = tmp_path / "omg_ik.s"
+    flags = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", f"-I{ROOT / 'include'}",
+             f"-I{ROOT / 'omg-planner_amd' / 'csrc'}", "--cuda-device-only", "-S"]
+    subprocess.run([HIPCC, *flags, str(ROOT / "omg-planner_amd" / "csrc" / "omg_ik.hip"), "-o", str(out)], check=True,
+                   stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
+    text = out.read_text()
+    name = re.search(r"^(\S*k_goal_ik\S*):", text, re.M).group(1)
+    start = text.index(name + ":")
+    block = text[start: text.index("; Occupancy:", start) + 40]
+    assert int(re.search(r"; ScratchSize: (\d+)", block).group(1)) == 0
+    assert int(re.search(r"; Occupancy: (\d+)", block).group(1)) >= 1
