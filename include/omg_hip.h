@@ -647,6 +647,31 @@ int omgx_goal_ik(const double* robot, int32_t n_points, const double* targets, c
                  double accept_diff, int32_t* status, double* solutions, int32_t* iterations, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * (11) omgx_select_goals (ABI 13)
+ * Replaces the selection of Planner.setup_goal_set (omg/planner.py:526-575: collision threshold + greedy diversity filter) for
+ * S scenes at once, one workgroup per scene; the random draw that follows stays with the caller (it consumes np.random).
+ *   goals          [S][G][9] f64, row stride G: scene s owns rows [0, goal_count[s]); the rest is padding, never read
+ *   goal_count     [S] int32 device; h_goal_count [S] host copy with the same values, or NULL.  With the host copy every count
+ *                  must lie in [0, G] (checked before the launch); without it a scene whose count does not is skipped and
+ *                  reports -1 in num_candidates and num_free
+ *   collides       [S][G] f32 (colliding lookups per goal, goalset.goal_collision_stats), or NULL: no collision filter
+ *   free           = the rows i < goal_count[s] with collides[i] <= allow_collision_point, in order (all rows without collides)
+ *   filter_diversity 0: the candidates are `free`.  1: free[0] seeds the kept set; free[p] (p >= 1) is kept iff no kept row u
+ *                  has ||g[u] - g[free[p]]|| < 0.5, decided as s < 0.25 with s = (((d0²+d1²)+(d2²+d3²))+((d4²+d5²)+(d6²+d7²)))+d8²
+ *                  (numpy's order for a 9-vector; exact for a correctly rounded sqrt); each kept p emits free[p - 1] (the
+ *                  reference's `indexes.append(j)`)
+ *   candidates     [S][G] int32 out: the emitted rows in order, valid in [0, num_candidates[s]); the rest is left as it was
+ *   num_candidates [S] int32 out (0: the reference's "IK FAIL"); num_free [S] int32 out: len(free)
+ *   workspace      omgx_select_goals_workspace_bytes(S, G) bytes of device memory (with filter_diversity; may be NULL without)
+ * Limits: 0 <= G <= OMGX_SELECT_MAX_GOALS; allow_collision_point not NaN.
+ * ------------------------------------------------------------------------------------------- */
+#define OMGX_SELECT_MAX_GOALS (1 << 24)
+int64_t omgx_select_goals_workspace_bytes(int32_t num_scenes, int32_t num_goals);
+int omgx_select_goals(const double* goals, const int32_t* goal_count, const int32_t* h_goal_count, int32_t num_scenes,
+                      int32_t num_goals, const float* collides, double allow_collision_point, int32_t filter_diversity,
+                      int32_t* candidates, int32_t* num_candidates, int32_t* num_free, void* workspace, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Diagnostics
  * ------------------------------------------------------------------------------------------- */
 const char* omgx_last_error(void); /* thread-local text of the last OMGX_ERR_LAUNCH               */

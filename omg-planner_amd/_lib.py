@@ -17,13 +17,15 @@ NUM_DOF, INFO_STRIDE = 9, 16
 SCHEDULE_MAX_SCENES = 1792  # OMGX_SCHEDULE_MAX_SCENES
 SCHEDULE_SCENE_MAJOR, SCHEDULE_LONGEST_FIRST = 0, 1  # OMGX_SCHEDULE_*: the order inside an XCD (omgx_goalset_schedule_ordered)
 SCHEDULE_LONGEST_FIRST_MAX_ITEMS = 8192
-ABI_VERSION = 12  # omgx_abi_version() of the library these argtypes describe
+SELECT_MAX_GOALS = 1 << 24  # OMGX_SELECT_MAX_GOALS
+ABI_VERSION = 13  # omgx_abi_version() of the library these argtypes describe
 
 # every symbol include/omg_hip.h declares
 EXPORTS = ["omgx_sdf_loss_forward", "omgx_fk_sdf_workspace_bytes", "omgx_fk_sdf", "omgx_forward_kinematics", "omgx_pose_table",
            "omgx_goalset_workspace_bytes", "omgx_goalset_cost", "omgx_goalset_cost_layer", "omgx_goalset_parts", "omgx_goalset_cost_layer_tiled", "omgx_goalset_cost_layer_parts", "omgx_goalset_schedule_len", "omgx_goalset_schedule", "omgx_goalset_schedule_parts", "omgx_goalset_schedule_ordered", "omgx_region_scratch_bytes", "omgx_object_set_grid", "omgx_fit_influence_region", "omgx_regions_scratch_bytes", "omgx_fit_influence_regions", "omgx_volume_hashes", "omgx_chomp_aux_doubles", "omgx_chomp_optimize",
            "omgx_learner_state_doubles", "omgx_goal_update", "omgx_goal_update_optimize", "omgx_point_cloud_sdf", "omgx_last_error", "omgx_abi_version", "omgx_device_arch", "omgx_device_cu_count", "omgx_download_sync",
-           "omgx_timing_enable", "omgx_timing_collect", "omgx_plan_persistent_workspace_bytes", "omgx_plan_persistent", "omgx_plan_persistent_status", "omgx_goal_ik"]
+           "omgx_timing_enable", "omgx_timing_collect", "omgx_plan_persistent_workspace_bytes", "omgx_plan_persistent", "omgx_plan_persistent_status", "omgx_goal_ik",
+           "omgx_select_goals_workspace_bytes", "omgx_select_goals"]
 
 
 class OmgHipError(RuntimeError):
@@ -149,6 +151,10 @@ def lib() -> C.CDLL:
         l.omgx_plan_persistent_status.restype = C.c_int
         l.omgx_goal_ik.argtypes = [vp, i32, vp, vp, C.POINTER(i32), i32, i32, vp, i32, i32, i32, i32, i32, f64, f64, f64, vp, vp, vp, vp]
         l.omgx_goal_ik.restype = C.c_int
+        l.omgx_select_goals_workspace_bytes.argtypes = [i32, i32]
+        l.omgx_select_goals_workspace_bytes.restype = i64
+        l.omgx_select_goals.argtypes = [vp, vp, C.POINTER(i32), i32, i32, vp, f64, i32, vp, vp, vp, vp, vp]
+        l.omgx_select_goals.restype = C.c_int
         for name in ("omgx_sdf_loss_forward", "omgx_fk_sdf", "omgx_forward_kinematics", "omgx_pose_table", "omgx_goalset_cost", "omgx_chomp_optimize",
                      "omgx_abi_version", "omgx_device_arch", "omgx_timing_enable", "omgx_timing_collect"):
             getattr(l, name).restype = C.c_int

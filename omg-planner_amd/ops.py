@@ -604,6 +604,58 @@ def goal_ik(robot, P, targets: torch.Tensor, grasp_begin, seeds: torch.Tensor, u
     return status, sols, its
 
 
+def select_goals(goals: torch.Tensor, goal_count, collide: "torch.Tensor | None" = None, allow_collision_point=5,
+                 filter_diversity: bool = True):
+    """omgx_select_goals: the collision threshold and the greedy diversity filter of Planner.setup_goal_set (planner.py:526-575)
+    for S scenes.  goals [S,G,9] f64, scene s owning rows [0, goal_count[s]); goal_count: S host integers (checked here), or an
+    integer device tensor (checked on the device: a scene out of [0, G] reports -1 in both counts); collide [S,G] f32
+    (goalset.goal_collision_stats) or None: no collision filter.
+    -> (candidates [S,G] int32: the rows the reference's `indexes` name, in order, valid in [0, num_candidates[s]);
+    num_candidates [S] int32, 0 = "IK FAIL"; num_free [S] int32), on the device.  Enqueued on the current stream."""
+    if not isinstance(goals, torch.Tensor) or goals.dim() != 3 or goals.shape[2] != 9:
+        raise _lib.OmgHipError("goals must be a [S, G, 9] tensor")
+    if goals.dtype != torch.float64:
+        raise _lib.OmgHipError(f"goals must be torch.float64, got {goals.dtype}")
+    S, G = int(goals.shape[0]), int(goals.shape[1])
+    if G > _lib.SELECT_MAX_GOALS:
+        raise _lib.OmgHipError(f"at most {_lib.SELECT_MAX_GOALS} goals per scene")
+    h_count = d_count = None
+    if isinstance(goal_count, torch.Tensor) and goal_count.is_cuda:
+        if tuple(goal_count.shape) != (S,) or goal_count.dtype not in (torch.int32, torch.int64):
+            raise _lib.OmgHipError("goal_count must hold S integers")
+        d_count = goal_count.to(torch.int32).contiguous()
+    else:
+        gc = np.asarray(goal_count.numpy() if isinstance(goal_count, torch.Tensor) else goal_count)
+        if gc.shape != (S,) or (S and not np.issubdtype(gc.dtype, np.integer)):
+            raise _lib.OmgHipError("goal_count must hold S integers")
+        if S and (gc.min() < 0 or gc.max() > G):
+            raise _lib.OmgHipError(f"goal_count must lie in [0, {G}]")
+        h_count = np.ascontiguousarray(gc, dtype=np.int32)
+    if collide is not None:
+        if not isinstance(collide, torch.Tensor) or tuple(collide.shape) != (S, G):
+            raise _lib.OmgHipError("collide must be a [S, G] tensor")
+        if collide.dtype != torch.float32:
+            raise _lib.OmgHipError(f"collide must be torch.float32, got {collide.dtype}")
+    allow = float(allow_collision_point)
+    if allow != allow:
+        raise _lib.OmgHipError("allow_collision_point is NaN")
+    _need(goals, torch.float64, "goals")
+    if collide is not None:
+        _need(collide, torch.float32, "collide")
+    dev = goals.device
+    if d_count is None:
+        d_count = torch.from_numpy(h_count).to(dev)
+    cand = torch.empty((S, G), dtype=torch.int32, device=dev)
+    counts = torch.empty((2, S), dtype=torch.int32, device=dev)
+    l = _lib.lib()
+    with torch.cuda.device(dev):
+        ws = _workspace(l.omgx_select_goals_workspace_bytes(S, G), dev) if filter_diversity else None
+        check(l.omgx_select_goals(_ptr(goals), _ptr(d_count), None if h_count is None else h_count.ctypes.data_as(C.POINTER(C.c_int32)),
+                                  S, G, _ptr(collide), allow, int(bool(filter_diversity)), _ptr(cand), _ptr(counts[0]),
+                                  _ptr(counts[1]), _ptr(ws), _stream()), "omgx_select_goals")
+    return cand, counts[0], counts[1]
+
+
 def chomp_optimize(robot, params: ChompParams, traj, start, end, goal, goal_point, pot, pgrad, col, active=None, out=None,
                    aux=None, stop_on_terminate=False):
     """In-place step on traj [S,n,9] f64 -> grad [S,n,9], cost_traj [S,n], info [S,16] (f64).

@@ -1,0 +1,84 @@
+"""From grasp poses to plans for S grasping scenes on the device: the reference's PlanningScene.step (omg/core.py:694-699) after
+Planner.__init__'s goal pipeline (planner.py:104-115) — IK (`goal_ik.solve_goal_sets`), the scene table
+(`ops.DeviceScenes.from_scenes`), the goal-set set-up (`goalset.setup_goal_sets`), grasp_init's goal set (planner.py:188-199)
+and the batched planner (`ChompEngine`).
+
+Grasping only: the engine holds one robot blob for all scenes, so it cannot carry per-scene attached-object points; a scene
+whose objects include an attached one is refused.
+
+Deviation kept from the engine (not from this module): with ol_alg "Baseline" the initial goal is cfg.goal_idx (or goal 0),
+where the reference's Learner.__init__ (online_learner.py:94-102) takes argmin(cost_vector) whenever reach grasps exist.
+"""
+from __future__ import annotations
+
+from dataclasses import dataclass
+
+import numpy as np
+import torch
+
+from . import _lib, goal_ik, goalset, ops
+from .engine import ChompEngine
+
+
+@dataclass
+class GraspPlans:
+    """What plan_grasps returns (device tensors unless noted).  Rows of scenes that were not planned hold zeros (traj), NaN
+    (info) and -1 (goal_idx)."""
+    traj: torch.Tensor            # [S, n, 9] f64: the final trajectories
+    info: torch.Tensor            # [S, 16] f64: the final info rows (ChompEngine.plan)
+    goal_idx: torch.Tensor        # [S] int32: the goal each plan ends at, an index into goal_set
+    goal_set: torch.Tensor        # [S, K, 9] f64: the goal sets planned towards (grasp_init: reach[:, :, -1] under use_standoff)
+    grasps: torch.Tensor          # [S, K, 9] f64: the selected goals (setup_goal_sets), padded with zeros
+    reach_grasps: torch.Tensor    # [S, K, T, 9] f64
+    potentials: torch.Tensor      # [S, K] f32
+    goal_counts: np.ndarray       # [S] int64 (host): goals per scene after the draw
+    num_free: np.ndarray          # [S] (host): goals that passed the collision filter
+    num_candidates: np.ndarray    # [S] (host): goals the draw chose from (0: "IK FAIL")
+    planned: np.ndarray           # [S] bool (host): False for scenes without goals ("planning not run")
+    engine: "ChompEngine | None"  # the engine over the planned scenes (None when no scene was planned)
+
+
+def plan_grasps(model, scenes, grasp_poses, starts, cfg, ol_alg=None, rng=np.random, obj_coord=True, device="cuda:0",
+                layout_scenes: "int | None" = None) -> GraspPlans:
+    """Plans for S grasping scenes from their grasp poses.
+
+    model: PandaModel; scenes: S scenes.Scene (the target object of each gives the object pose); grasp_poses: S arrays [G_s,4,4]
+    (ragged, may be empty) in the target's frame (obj_coord) or the world's; starts [S,9]; cfg: Config.  ol_alg: default
+    cfg.ol_alg.  rng: the stream the goal draw consumes (np.random, as the reference).  Scenes whose goal sets come out empty are
+    not planned (the reference prints "planning not run"); the engine runs over the other scenes with its layout evaluated for
+    `layout_scenes` (default S), so a goal-less scene changes no other scene's bits."""
+    dev = torch.device(device)
+    S = len(scenes)
+    if any(ob.attached for sc_ in scenes for ob in sc_.objects):
+        raise ValueError("plan_grasps plans grasps only: a scene with an attached object needs per-scene robot points")
+    if len(grasp_poses) != S:
+        raise ValueError("grasp_poses must hold one array per scene")
+    starts = np.ascontiguousarray(np.asarray(starts, np.float64).reshape(S, 9))
+    objs = np.stack([np.asarray(sc_.objects[sc_.target_idx].pose_mat, np.float64) for sc_ in scenes]) if S else np.zeros((0, 4, 4))
+    gs, rs, counts, _ = goal_ik.solve_goal_sets(model, grasp_poses, objs, starts, cfg, attached=False, obj_coord=obj_coord, device=dev)
+    table = ops.DeviceScenes.from_scenes(scenes, cfg.layer_kwargs(), device=dev)
+    robot = ops.robot_blob(model, dev)
+    grasps, reach, pot, k, nfree, ncand = goalset.setup_goal_sets(robot, model.points_per_link, table, gs, rs, counts, cfg, rng=rng)
+    goals = reach[:, :, -1].contiguous() if (cfg.goal_set_proj and cfg.use_standoff) else grasps
+    planned = k > 0
+    idx = np.flatnonzero(planned)
+    if not getattr(cfg, "silent", False):
+        for s in np.flatnonzero(~planned):
+            print(f"scene {s}: planning not run...")
+    n = cfg.timesteps
+    traj = torch.zeros((S, n, 9), dtype=torch.float64, device=dev)
+    info = torch.full((S, _lib.INFO_STRIDE), float("nan"), dtype=torch.float64, device=dev)
+    goal_idx = torch.full((S,), -1, dtype=torch.int32, device=dev)
+    eng = None
+    if idx.size:
+        sub = table if idx.size == S else ops.DeviceScenes.from_scenes([scenes[i] for i in idx], cfg.layer_kwargs(), device=dev)
+        sel = torch.from_numpy(idx).to(dev)
+        kw = dict(reach_grasps=reach.index_select(0, sel).cpu().numpy()) if cfg.use_standoff else {}
+        eng = ChompEngine.auto(model, sub, cfg, starts[idx], goals.index_select(0, sel).cpu().numpy(),
+                               layout_scenes=S if layout_scenes is None else int(layout_scenes), for_plan=True,
+                               goal_counts=k[idx], device=dev, ol_alg=ol_alg or cfg.ol_alg, **kw)
+        out = eng.plan()
+        traj.index_copy_(0, sel, eng.traj)
+        info.index_copy_(0, sel, out)
+        goal_idx.index_copy_(0, sel, eng.goal_idx)
+    return GraspPlans(traj, info, goal_idx, goals, grasps, reach, pot, k, nfree, ncand, planned, eng)
