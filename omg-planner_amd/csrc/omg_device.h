@@ -133,7 +133,7 @@ struct Accum { float pot, gx, gy, gz, col; };
 //   1. conservative far-reject in object space (1.5 voxels of slack on a half-voxel requirement): the
 //      centre lookup is provably out of range -> value 1.0 -> nothing to add (when eps < 1, clr <= 1);
 //   2. exact grid coordinates (IEEE division, double -0.5 split) and the centre trilinear value;
-//   3. only when a gradient is requested AND value <= eps: the six +-1-voxel lookups.
+//   3. only when a gradient is requested AND value <= max(eps, 0): the six +-1-voxel lookups.
 // WANT_GRAD=false (goal-set cost: Learner.cost_vector never reads batch_obstacle_cost's gradient,
 // online_learner.py:134-148) therefore needs 4 row loads per in-range pair instead of the reference's 56.
 struct PairPrep { float tx, ty, tz; bool far; };
@@ -213,7 +213,7 @@ __device__ __forceinline__ void pair_exact(const ObjParams& o, const float* __re
         const F4 c11 = *reinterpret_cast<const F4*>(G.g + b + sx + sy - 1);
         value = trilerp(c00.b, c00.c, c01.b, c01.c, c10.b, c10.c, c11.b, c11.c, ax.f, ay.f, az.f);
         if (value < o.clr) acc.col += 1.0f;  // .cu:150-151
-        if (!(value <= o.eps)) return;       // .cu:170-171
+        if (!(value <= 0.0f || value <= o.eps)) return;  // .cu:172-173; value <= 0 contributes whatever eps is (.cu:158)
         // +-z: same rows shifted by one voxel
         fpz = trilerp(c00.c, c00.d, c01.c, c01.d, c10.c, c10.d, c11.c, c11.d, ax.f, ay.f, azp.f);
         fmz = trilerp(c00.a, c00.b, c01.a, c01.b, c10.a, c10.b, c11.a, c11.b, ax.f, ay.f, azm.f);
@@ -235,7 +235,7 @@ __device__ __forceinline__ void pair_exact(const ObjParams& o, const float* __re
         if (in_c) {
             value = sdf_value(G, ax, ay, az);
             if (value < o.clr) acc.col += 1.0f;
-            if (!(value <= o.eps)) return;
+            if (!(value <= 0.0f || value <= o.eps)) return;
         } else {
             value = 1.0f;  // only reachable when eps >= 1
         }

@@ -88,7 +88,7 @@ __device__ __forceinline__ void rg_need(const RegionArgs& a) {
     const int64_t N = (int64_t)a.X * a.Y * a.Z;
     const int64_t id = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const double margin = rg_margin(a.st);
-    const double eps_t = a.eps + margin, clr_t = a.clr + margin;
+    const double eps_t = (a.eps > 0.0 ? a.eps : 0.0) + margin, clr_t = a.clr + margin;  // value <= 0 contributes whatever epsilon is (.cu:158)
     bool need = false, neg = false;
     int x = 0, y = 0, z = 0;
     if (id < N) {
@@ -178,7 +178,7 @@ __device__ __forceinline__ void rg_boxes(const RegionArgs& a, double (*sc)[3], d
     const int lane = threadIdx.x & 63;
     const int64_t N = (int64_t)a.X * a.Y * a.Z;
     const double margin = rg_margin(st);
-    const double eps_t = a.eps + margin, clr_t = a.clr + margin;
+    const double eps_t = (a.eps > 0.0 ? a.eps : 0.0) + margin, clr_t = a.clr + margin;  // value <= 0 contributes whatever epsilon is (.cu:158)
     double r2[RG_CANDS];
 #pragma unroll
     for (int c = 0; c < RG_CANDS; ++c) r2[c] = 0.0;

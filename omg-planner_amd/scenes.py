@@ -67,8 +67,9 @@ def finish_records(rec: np.ndarray) -> np.ndarray:
 
 
 def _needed_windows(grid: np.ndarray, epsilon: float, clearance: float):
-    """(need, ge, margin): `need[w]` (shape = grid dims) says whether a lookup through WINDOW w can return a value <= epsilon
-    or < clearance (anything else adds neither potential, gradient nor collision, .cu:150-171).
+    """(need, ge, margin): `need[w]` (shape = grid dims) says whether a lookup through WINDOW w can return a value <= max(epsilon, 0)
+    or < clearance (anything else adds neither potential, gradient nor collision, .cu:150-173; a value <= 0 takes the first hinge
+    branch whatever epsilon is, .cu:158).
 
     Window w = (wx, wy, wz) is the trilinear polynomial of voxels w-1 .. w per axis, evaluated at fractions in [0, 1]; voxel -1 is
     the linear extension 2 v[0] - v[1].  A lookup with base index b and fractions f in [0,1)^3 uses window b + 1; on an axis
@@ -89,7 +90,7 @@ def _needed_windows(grid: np.ndarray, epsilon: float, clearance: float):
     for ax in range(3):
         n = m.shape[ax]
         m = np.minimum(np.take(m, range(0, n - 1), axis=ax), np.take(m, range(1, n), axis=ax))
-    need = (m <= float(np.float32(epsilon)) + margin) | (m < float(np.float32(clearance)) + margin)
+    need = (m <= max(float(np.float32(epsilon)), 0.0) + margin) | (m < float(np.float32(clearance)) + margin)
     return need, ge, margin
 
 
@@ -131,7 +132,7 @@ def influence_rbox(grid: np.ndarray, epsilon: float, clearance: float, vox: np.n
     need, ge, margin = _needed_windows(grid, epsilon, clearance)
     if not need.any():
         return None
-    eps_t, clr_t = float(np.float32(epsilon)) + margin, float(np.float32(clearance)) + margin
+    eps_t, clr_t = max(float(np.float32(epsilon)), 0.0) + margin, float(np.float32(clearance)) + margin
     # boundary windows: needed, with a face neighbour that is not (windows on the grid's faces: the outside is not needed)
     pad = np.pad(need, 1, constant_values=False)
     inner = pad[1:-1, 1:-1, 1:-1].copy()

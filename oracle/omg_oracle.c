@@ -13,10 +13,13 @@
  *   - The SDF op (orc_sdf_loss_forward): its interpolation helpers (orc_sdf_value = getValueInterpolated, the
  *     central differences = getGradientInterpolated, .cu:15-86) are PINNED against the reference's own source compiled
  *     for the host (oracle/_ref, `make -C oracle ref`; tests/test_oracle_ref_helpers.py: bit-exact against the
- *     FMA-contracted build).  The kernel BODY (.cu:96-181: pose transform, hinge, rotate-back, reduction) is PARITY
- *     UNPINNED by the reference: it needs nvcc + ATen + Eigen + Sophus, none present, and the reference holds no test
- *     vectors for it; it follows the source line by line and is checked by closed-form known-answer tests
- *     (tests/test_oracle_sdf.py).
+ *     FMA-contracted build).  The kernel BODY (.cu:96-195: pose transform, casts, hinge, rotate-back, reduction) is PINNED
+ *     the same way: the body's own text runs on the host behind stand-ins for the few Eigen / Sophus types it names
+ *     (oracle/ref_body_wrapper.cpp -> oracle/_ref/libsdf_ref_body.so; tests/test_oracle_ref_body.py: orc_sdf_loss_forward and
+ *     orc_fk_sdf bit-exact against it in both modes, outputs stored in tests/golden/ref_sdf_body.npz).  What REMAINS UNPINNED:
+ *     Eigen's and Sophus' own arithmetic (restated: float32 matrix product, or the quaternion round trip of SOPHUS MODE), what
+ *     nvcc would contract inside them, and the order of the atomic reduction over objects (index order here).  The launcher
+ *     (.cu:204-262) needs nvcc + ATen and stays unbuilt.  Closed-form known-answer tests: tests/test_oracle_sdf.py.
  *
  * Floating-point conventions, shared bit-for-bit with the HIP kernels (both are compiled with
  * -ffp-contract=off so only the explicit fma()s below fuse):
@@ -155,7 +158,9 @@ static void orc_sdf_pair(const float* T /*[3][4] rows of the inverse pose*/, con
     const float gz = (uz - lo[2]) / (hi[2] - lo[2]) * (float)d2;
     const float value = orc_sdf_value(gx, gy, gz, d0, d1, d2, grid); /* .cu:147 */
     if (value < clr) *col += 1.0f;                                      /* .cu:150-151 */
-    if (!(value <= eps)) return; /* .cu:170-171 `else continue` — the gradient below would be unused */
+    /* .cu:172-173 `else continue` — the gradient below would be unused.  `value <= 0` takes the first branch WHATEVER epsilon is
+     * (.cu:158), so with a negative epsilon values in (epsilon, 0] still contribute (tests/test_oracle_ref_body.py, epsilon_negative) */
+    if (!(value <= 0.0f || value <= eps)) return;
     /* getGradientInterpolated, .cu:66-86: central differences one VOXEL apart, divided by delta */
     const float fpx = orc_sdf_value(gx + 1.0f, gy, gz, d0, d1, d2, grid);
     const float fpy = orc_sdf_value(gx, gy + 1.0f, gz, d0, d1, d2, grid);

@@ -4,7 +4,7 @@
 // of /root/reference/layers/sdf_matching_loss_kernel.cu (lerp, float3 +/-, getValue, getValueInterpolated,
 // getGradientInterpolated: all `__device__ __host__`, no ATen / Eigen / Sophus), compiled here for the HOST.
 // Nothing of it is stored in the repository; only the resulting oracle/_ref/libsdf_ref_helpers.so exists (git-ignored).
-// The kernel body (.cu:96-181) and launcher need ATen + Eigen + Sophus + nvcc and stay unbuildable.
+// The kernel body (.cu:96-195) is built by oracle/ref_body_wrapper.cpp; the launcher needs ATen + nvcc and stays unbuilt.
 #include <hip/hip_runtime.h>
 
 #include REF_HELPERS_INC

@@ -6,8 +6,8 @@ records it from oracle/_ref): the oracle is checked against the stored outputs, 
 must reproduce them bit for bit.
 
 This pins the numerically delicate part of the SDF op (the -0.5 voxel-centre shift in double, truncation toward zero,
-out-of-range 1.0, one-voxel central differences divided by delta in double).  The kernel body (.cu:96-181: pose transform,
-hinge, rotate-back, reduction) needs ATen + Eigen + Sophus + nvcc and is covered by the known-answer tests instead."""
+out-of-range 1.0, one-voxel central differences divided by delta in double).  The kernel body (.cu:96-195: pose transform,
+hinge, rotate-back, reduction) is pinned by tests/test_oracle_ref_body.py, which runs the body's own text on the host."""
 import ctypes as C
 from pathlib import Path
 

@@ -1,6 +1,8 @@
 """CPU tests: known-answer checks of the oracle's SDF op (layers/sdf_matching_loss_kernel.cu:15-181).
 
-The reference has no CPU implementation and no test vectors for this op ("parity unpinned"), so the
+The op's own text is what tests/test_oracle_ref_helpers.py (helpers) and tests/test_oracle_ref_body.py (kernel body) run on
+the host; what stays unpinned there is Eigen's and Sophus' arithmetic, nvcc's contraction inside them and the atomic order.
+These tests are independent of any build of the reference: the
 restatement is checked against closed forms: trilinear interpolation reproduces a field that is
 linear in the grid coordinates exactly, which fixes value, central-difference gradient, both hinge
 branches, the rotate-back, the collides count, the -0.5 voxel-centre shift, truncation toward zero
