@@ -672,6 +672,51 @@ int omgx_select_goals(const double* goals, const int32_t* goal_count, const int3
                       int32_t* candidates, int32_t* num_candidates, int32_t* num_free, void* workspace, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * (12) omgx_mesh_sdf (ABI 14)
+ * Replaces the step the reference leaves to an external program: a mesh goes through the SDFGen binary
+ * (real_world/gen_sdf.py:13-37), its text .sdf file is read by SignedDensityField.from_sdf (omg/sdf_tools.py:169-185) and
+ * converted to the .pth file Model loads (real_world/convert_sdf.py:14-27).  Here ONE launch turns the triangles of M meshes
+ * (a ragged batch) into M signed distance grids, written where the caller says: its own buffer or the SDF pool itself
+ * (DeviceScenes.grid_slot), x-major like every other grid: out[out_offset + (i * dims[1] + j) * dims[2] + k].
+ * omg-planner_amd/scenes.py (closest_point_on_triangle, mesh_sdf) is the specification.  For node
+ * p = origin + ((i, j, k) + sample_offset) * delta, all in float64 without contraction:
+ *   d     sqrt(min over the mesh's faces of |p - q|^2), q = the closest point of the face to p by the seven regions of a
+ *         triangle (vertices a, b, c; edges ab, ac, bc; interior), the first that holds in the order a, b, ab, c, ac, bc; an edge
+ *         parameter is one quotient, the interior's barycentric weights share one reciprocal; |r|^2 = (rx*rx + ry*ry) + rz*rz
+ *   w     (1 / 4 pi) * sum over the faces of 2 * atan2(A . (B x C), |A||B||C| + (A.B)|C| + (B.C)|A| + (C.A)|B|) with
+ *         A, B, C = a - p, b - p, c - p: the generalised winding number, summed in float64 with the device library's atan2
+ *   value -d if |w| > 0.5 (inside; |w| so that a mesh whose faces all point inwards gives the same volume), else +d; rounded
+ *         to float32 once, on the store.  The bits of d are the specification's; of w only the decision is part of the contract.
+ *   verts   [V_total][3] double, faces [F_total][3] int32: the pools of all meshes; a face's indices are local to its mesh's
+ *           vertex range.  Indices outside [0, vert_count) and faces of zero area are the caller's to reject (ops.mesh_sdf does);
+ *           the kernel clamps an index into the mesh's range, so a bad one reads the wrong vertex, never outside the pool
+ *   meshes  [M] omgx_mesh on the device, h_meshes the same records on the host (all checks are made on the host copy, before
+ *           any HIP call).  first_workgroup is the prefix table that maps a workgroup to (mesh, first node): 0 for mesh 0, then
+ *           first_workgroup[m - 1] + ceil(nodes[m - 1] / OMGX_MESH_SDF_NODES_PER_WORKGROUP)
+ *   out     float32; the volumes must not overlap
+ * OMGX_ERR_INVALID: a null pointer, M < 1, a mesh without vertices or faces, delta <= 0 or not finite, a dims < 1, a
+ * sample_offset other than 0.0 (node i at origin + i * delta: the text .sdf convention) or 0.5 (the voxel centres the SDF op
+ * interpolates between), a negative begin or out_offset, a first_workgroup that is not the prefix sum.  OMGX_ERR_UNSUPPORTED:
+ * more than 2^31 nodes in one mesh (or more than 2^31 - 1 workgroups in all).
+ * omgx_mesh_sdf_tile(): the number of faces staged in LDS at a time (tests place face counts around it).
+ * ------------------------------------------------------------------------------------------- */
+#define OMGX_MESH_SDF_NODES_PER_WORKGROUP 256
+typedef struct omgx_mesh {
+    double origin[3];        /* min corner of the grid                                          */
+    double delta;            /* node spacing                                                    */
+    double sample_offset;    /* 0.5 or 0.0                                                      */
+    int64_t out_offset;      /* element offset of node (0,0,0) in `out`                         */
+    int64_t first_workgroup; /* prefix table (see above)                                        */
+    int32_t dims[3];         /* nodes per axis                                                  */
+    int32_t vert_begin, vert_count; /* the mesh's rows of `verts`                               */
+    int32_t face_begin, face_count; /* the mesh's rows of `faces`                               */
+    int32_t reserved_;       /* 0 (keeps the record a multiple of 8 bytes: 88)                  */
+} omgx_mesh;
+int32_t omgx_mesh_sdf_tile(void);
+int omgx_mesh_sdf(const double* verts, const int32_t* faces, const omgx_mesh* meshes, const omgx_mesh* h_meshes,
+                  int32_t num_meshes, float* out, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Diagnostics
  * ------------------------------------------------------------------------------------------- */
 const char* omgx_last_error(void); /* thread-local text of the last OMGX_ERR_LAUNCH               */

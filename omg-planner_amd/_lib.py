@@ -18,14 +18,14 @@ SCHEDULE_MAX_SCENES = 1792  # OMGX_SCHEDULE_MAX_SCENES
 SCHEDULE_SCENE_MAJOR, SCHEDULE_LONGEST_FIRST = 0, 1  # OMGX_SCHEDULE_*: the order inside an XCD (omgx_goalset_schedule_ordered)
 SCHEDULE_LONGEST_FIRST_MAX_ITEMS = 8192
 SELECT_MAX_GOALS = 1 << 24  # OMGX_SELECT_MAX_GOALS
-ABI_VERSION = 13  # omgx_abi_version() of the library these argtypes describe
+ABI_VERSION = 14  # omgx_abi_version() of the library these argtypes describe
 
 # every symbol include/omg_hip.h declares
 EXPORTS = ["omgx_sdf_loss_forward", "omgx_fk_sdf_workspace_bytes", "omgx_fk_sdf", "omgx_forward_kinematics", "omgx_pose_table",
            "omgx_goalset_workspace_bytes", "omgx_goalset_cost", "omgx_goalset_cost_layer", "omgx_goalset_parts", "omgx_goalset_cost_layer_tiled", "omgx_goalset_cost_layer_parts", "omgx_goalset_schedule_len", "omgx_goalset_schedule", "omgx_goalset_schedule_parts", "omgx_goalset_schedule_ordered", "omgx_region_scratch_bytes", "omgx_object_set_grid", "omgx_fit_influence_region", "omgx_regions_scratch_bytes", "omgx_fit_influence_regions", "omgx_volume_hashes", "omgx_chomp_aux_doubles", "omgx_chomp_optimize",
            "omgx_learner_state_doubles", "omgx_goal_update", "omgx_goal_update_optimize", "omgx_point_cloud_sdf", "omgx_last_error", "omgx_abi_version", "omgx_device_arch", "omgx_device_cu_count", "omgx_download_sync",
            "omgx_timing_enable", "omgx_timing_collect", "omgx_plan_persistent_workspace_bytes", "omgx_plan_persistent", "omgx_plan_persistent_status", "omgx_goal_ik",
-           "omgx_select_goals_workspace_bytes", "omgx_select_goals"]
+           "omgx_select_goals_workspace_bytes", "omgx_select_goals", "omgx_mesh_sdf_tile", "omgx_mesh_sdf"]
 
 
 class OmgHipError(RuntimeError):
@@ -55,6 +55,15 @@ class PlanIter(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("mode", "start_idx", "stop_on_terminate", "do_update")] + [(n, C.c_double) for n in (
         "obstacle_weight", "smoothness_weight", "step_size")]
 
+
+class Mesh(C.Structure):
+    """Mirror of `omgx_mesh` (include/omg_hip.h): one mesh of an omgx_mesh_sdf batch (88 bytes)."""
+    _fields_ = [("origin", C.c_double * 3), ("delta", C.c_double), ("sample_offset", C.c_double), ("out_offset", C.c_int64),
+                ("first_workgroup", C.c_int64), ("dims", C.c_int32 * 3), ("vert_begin", C.c_int32), ("vert_count", C.c_int32),
+                ("face_begin", C.c_int32), ("face_count", C.c_int32), ("reserved_", C.c_int32)]
+
+
+MESH_SDF_NODES_PER_WORKGROUP = 256  # OMGX_MESH_SDF_NODES_PER_WORKGROUP
 
 ALG = {"FTL": 0, "FTC": 1, "Exp": 2, "MD": 3, "Proj": 4}
 
@@ -155,6 +164,10 @@ def lib() -> C.CDLL:
         l.omgx_select_goals_workspace_bytes.restype = i64
         l.omgx_select_goals.argtypes = [vp, vp, C.POINTER(i32), i32, i32, vp, f64, i32, vp, vp, vp, vp, vp]
         l.omgx_select_goals.restype = C.c_int
+        l.omgx_mesh_sdf_tile.argtypes = []
+        l.omgx_mesh_sdf_tile.restype = i32
+        l.omgx_mesh_sdf.argtypes = [vp, vp, vp, vp, i32, vp, vp]
+        l.omgx_mesh_sdf.restype = C.c_int
         for name in ("omgx_sdf_loss_forward", "omgx_fk_sdf", "omgx_forward_kinematics", "omgx_pose_table", "omgx_goalset_cost", "omgx_chomp_optimize",
                      "omgx_abi_version", "omgx_device_arch", "omgx_timing_enable", "omgx_timing_collect"):
             getattr(l, name).restype = C.c_int

@@ -700,7 +700,7 @@ static void timing_events(int kind, hipEvent_t* ev0, hipEvent_t* ev1) {
     *ev0 = g_ev[i][0]; *ev1 = g_ev[i][1];
     ++g_timing_n;
 }
-extern "C" int omgx_abi_version(void) { return 13; }  // 13: omgx_select_goals (goal-set selection); 12: omgx_goal_ik (goal-set IK); 11: omgx_plan_persistent (K iterations of all scenes in one launch); 10: kinematics pre-pass (k_goalset_kin) behind the `workspace` argument of omgx_goalset_cost / _cost_layer, new trailing `workspace` of _cost_layer_parts / _cost_layer_tiled; 9: omgx_goalset_schedule_ordered (longest first inside an XCD); 8: omgx_goalset_cost_layer_parts, omgx_goalset_schedule_parts (a goal's tiles over several workgroups of the batch kernel); 2: `active` masks; 3: ragged goal sets (goal_count, eta); 4: goal schedule + work; 5: 184-byte object records (influence region = rounded box); 6: omgx_goalset_cost_layer_tiled, omgx_learner_params.cost_parts; 7: pose tables (omgx_pose_table, pointer fields at the end of both parameter blocks, layer_poses)
+extern "C" int omgx_abi_version(void) { return 14; }  // 14: omgx_mesh_sdf (signed distance grids from triangle meshes, omg_mesh_sdf.hip); 13: omgx_select_goals (goal-set selection); 12: omgx_goal_ik (goal-set IK); 11: omgx_plan_persistent (K iterations of all scenes in one launch); 10: kinematics pre-pass (k_goalset_kin) behind the `workspace` argument of omgx_goalset_cost / _cost_layer, new trailing `workspace` of _cost_layer_parts / _cost_layer_tiled; 9: omgx_goalset_schedule_ordered (longest first inside an XCD); 8: omgx_goalset_cost_layer_parts, omgx_goalset_schedule_parts (a goal's tiles over several workgroups of the batch kernel); 2: `active` masks; 3: ragged goal sets (goal_count, eta); 4: goal schedule + work; 5: 184-byte object records (influence region = rounded box); 6: omgx_goalset_cost_layer_tiled, omgx_learner_params.cost_parts; 7: pose tables (omgx_pose_table, pointer fields at the end of both parameter blocks, layer_poses)
 // One call for "copy these bytes back and wait": hipMemcpyAsync (device -> pinned host) + hipStreamSynchronize on the caller's stream
 // — the last step of a planner iteration through the drop-in classes (device_loop.DeviceLoop), where two framework calls cost the
 // host more than the copy itself.

@@ -1014,3 +1014,117 @@ def point_cloud_sdf(points: torch.Tensor, grid_resolution: float = 0.02, margin:
                                               float(grid_resolution), dims.ctypes.data_as(C.POINTER(C.c_int32)), _ptr(out),
                                               _stream()), "omgx_point_cloud_sdf")
     return out, origin, float(grid_resolution)
+
+
+def _mesh_layout(verts, delta, padding, sample, origin, dims):
+    from . import scenes as _sc
+    if sample not in _sc.MESH_SAMPLE_OFFSET:
+        raise _lib.OmgHipError(f"sample must be 'centre' or 'node', got {sample!r}")
+    if (origin is None) != (dims is None):
+        raise _lib.OmgHipError("give origin and dims together")
+    if not (float(delta) > 0 and np.isfinite(float(delta))):
+        raise _lib.OmgHipError("delta must be positive and finite")
+    if origin is None:
+        origin, dims = _sc.mesh_grid_layout(verts, float(delta), padding)
+    return np.asarray(origin, np.float64).copy(), tuple(int(d) for d in dims), _sc.MESH_SAMPLE_OFFSET[sample]
+
+
+def _mesh_pack(meshes, delta, padding, sample, origins, dims, out_offsets):
+    """Host side of mesh_sdf_batch: every mesh cleaned and laid out -> (omgx_mesh records, vertex pool [V,3] float64, face pool
+    [F,3] int32, shapes, origins, deltas, dropped, elements of the volumes back to back)."""
+    from . import scenes as _sc
+    M = len(meshes)
+    if M < 1:
+        raise _lib.OmgHipError("mesh_sdf_batch needs at least one mesh")
+
+    def per_mesh(x, name):
+        if isinstance(x, (list, tuple)):
+            if len(x) != M:
+                raise _lib.OmgHipError(f"{name} must have one entry per mesh ({M}), got {len(x)}")
+            return list(x)
+        return [x] * M
+    deltas, pads, samples = per_mesh(delta, "delta"), per_mesh(padding, "padding"), per_mesh(sample, "sample")
+    if (origins is None) != (dims is None):
+        raise _lib.OmgHipError("give origins and dims together")
+    if origins is not None and (len(origins) != M or len(dims) != M):
+        raise _lib.OmgHipError(f"origins and dims must have one entry per mesh ({M})")
+    if out_offsets is not None and len(out_offsets) != M:
+        raise _lib.OmgHipError(f"out_offsets must have one entry per mesh ({M})")
+    rec = (_lib.Mesh * M)()
+    vs, fs, shapes, org, dropped = [], [], [], [], []
+    v0 = f0 = wg = flat = 0
+    for m, (verts, faces) in enumerate(meshes):
+        try:
+            verts, faces, drop = _sc.clean_mesh(verts, faces)
+        except ValueError as e:
+            raise _lib.OmgHipError(f"mesh {m}: {e}") from None
+        o, d, off = _mesh_layout(verts, deltas[m], pads[m], samples[m], None if origins is None else origins[m], None if dims is None else dims[m])
+        if min(d) < 1:
+            raise _lib.OmgHipError(f"mesh {m}: dims must be >= 1, got {d}")
+        n = d[0] * d[1] * d[2]
+        r = rec[m]
+        r.origin[:], r.delta, r.sample_offset, r.dims[:] = list(o), float(deltas[m]), off, list(d)
+        r.vert_begin, r.vert_count, r.face_begin, r.face_count = v0, len(verts), f0, len(faces)
+        r.first_workgroup = wg
+        r.out_offset = flat if out_offsets is None else int(out_offsets[m])
+        wg += -(-n // _lib.MESH_SDF_NODES_PER_WORKGROUP)
+        flat, v0, f0 = flat + n, v0 + len(verts), f0 + len(faces)
+        vs.append(verts), fs.append(faces), shapes.append(d), org.append(o), dropped.append(drop)
+    return rec, np.concatenate(vs), np.concatenate(fs), shapes, org, [float(x) for x in deltas], dropped, flat
+
+
+def mesh_sdf_batch(meshes, delta, padding=4, sample="centre", origins=None, dims=None, out=None, out_offsets=None, device="cuda:0"):
+    """Signed distance grids of M triangle meshes in ONE launch (omgx_mesh_sdf; scenes.mesh_sdf is the specification: the same
+    float32 magnitudes bit for bit, the sign from the winding number's decision |w| > 0.5).
+    meshes: a list of (verts [V,3] float, faces [F,3] int) on the host; delta / padding / sample: one value for all or a list
+    with one per mesh; origins / dims: None (scenes.mesh_grid_layout per mesh) or lists with an explicit layout per mesh.
+    out: None -> one flat float32 buffer holding the volumes back to back; or a contiguous float32 device tensor (the SDF
+    pool, for instance) written IN PLACE at the element offsets `out_offsets` (one per mesh; the volumes must not overlap), its
+    autograd version counter bumped like point_cloud_sdf does.
+    -> (grids: M float32 [X,Y,Z] views into the buffer, origins: M float64 [3], deltas: M floats, dropped: M counts of zero-area
+    faces left out).  Raises OmgHipError on indices outside a mesh's vertices, a mesh left without faces, a bad layout."""
+    rec, verts, faces, shapes, org, deltas, dropped, flat = _mesh_pack(meshes, delta, padding, sample, origins, dims, out_offsets)
+    M = len(meshes)
+    if out is None:
+        if out_offsets is not None:
+            raise _lib.OmgHipError("out_offsets needs out")
+        out = torch.empty(flat, dtype=torch.float32, device=device)
+    else:
+        _need(out, torch.float32, "out")
+        if out_offsets is None and M > 1:
+            raise _lib.OmgHipError("out needs out_offsets (one element offset per mesh)")
+        spans = sorted((int(rec[m].out_offset), int(np.prod(shapes[m]))) for m in range(M))
+        if spans[0][0] < 0 or spans[-1][0] + spans[-1][1] > out.numel() or any(spans[i][0] + spans[i][1] > spans[i + 1][0] for i in range(M - 1)):
+            raise _lib.OmgHipError(f"the volumes (offset, elements) {spans} overlap or leave out ({out.numel()} elements)")
+        torch.autograd.graph.increment_version(out)
+    dev = out.device
+    d_verts, d_faces = torch.from_numpy(verts).to(dev), torch.from_numpy(faces).to(dev)
+    d_rec = torch.from_numpy(np.frombuffer(rec, np.uint8).copy()).to(dev)
+    with torch.cuda.device(dev):
+        check(_lib.lib().omgx_mesh_sdf(_ptr(d_verts), _ptr(d_faces), _ptr(d_rec), C.cast(rec, C.c_void_p), M, _ptr(out), _stream()),
+              "omgx_mesh_sdf")
+        for t in (d_verts, d_faces, d_rec):
+            t.record_stream(torch.cuda.current_stream(dev))
+    flat_out = out.reshape(-1)
+    grids = [flat_out[int(rec[m].out_offset): int(rec[m].out_offset) + int(np.prod(shapes[m]))].view(shapes[m]) for m in range(M)]
+    return grids, org, deltas, dropped
+
+
+def mesh_sdf(verts, faces, delta, padding=4, sample="centre", origin=None, dims=None, out=None, device="cuda:0"):
+    """Signed distance grid of one triangle mesh on the device -> (grid float32 [X,Y,Z], origin [3] float64 numpy, delta).
+    scenes.mesh_sdf with the same arguments is the specification.  out: a contiguous float32 device tensor with X*Y*Z elements,
+    e.g. DeviceScenes.grid_slot(scene, obj, dims) with dims from scenes.mesh_grid_layout — written IN PLACE, ready for
+    DeviceScenes.replace_grid(scene, obj, grid, origin, delta).  Faces of zero area are dropped (their number is logged at
+    debug level; mesh_sdf_batch returns it)."""
+    if out is not None:
+        _need(out, torch.float32, "out")
+        _, d, _ = _mesh_layout(np.asarray(verts, np.float64), delta, padding, sample, origin, dims)
+        if out.numel() != d[0] * d[1] * d[2]:
+            raise _lib.OmgHipError(f"out must hold {d[0] * d[1] * d[2]} elements (grid {d})")
+    grids, org, deltas, dropped = mesh_sdf_batch([(verts, faces)], delta, padding, sample, None if origin is None else [origin],
+                                                 None if dims is None else [dims], out=out, out_offsets=None if out is None else [0],
+                                                 device=device)
+    if dropped[0]:
+        import logging
+        logging.getLogger(__name__).debug("mesh_sdf: dropped %d faces of zero area", dropped[0])
+    return grids[0], org[0], deltas[0]

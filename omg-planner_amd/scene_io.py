@@ -91,3 +91,63 @@ def save_scene_mat(mat_path: str, root_dir: str, scene: Scene, goals: np.ndarray
             save_sdf_pth(f, o.sdf)
     sio.savemat(mat_path, {"pose": np.stack([o.pose_mat for o in scene.objects]), "path": np.array(rel_dirs),
                            "goals": goals, "reach_grasps": reach_grasps, "target_name": np.array([scene.objects[scene.target_idx].name])})
+
+
+# ------------------------------------------------------------------------------------------------
+# asset files a user brings: a triangle mesh (Wavefront OBJ) and the text .sdf volume the reference's tooling exchanges
+# ------------------------------------------------------------------------------------------------
+def load_obj(path: str):
+    """(verts [V,3] float64, faces [F,3] int32) of a Wavefront OBJ file.  Only `v` and `f` lines are read (normals, texture
+    coordinates, groups, materials are skipped); a face entry may be `a`, `a/b`, `a//c` or `a/b/c` (the vertex index is the first
+    field), indices are 1-based or negative (relative to the vertices read so far); polygons are fan-triangulated around their
+    first corner."""
+    verts, faces = [], []
+    with open(path, "r") as fh:
+        for ln, line in enumerate(fh, 1):
+            tok = line.split("#", 1)[0].split()
+            if not tok:
+                continue
+            if tok[0] == "v":
+                if len(tok) < 4:
+                    raise ValueError(f"{path}:{ln}: a vertex needs three coordinates")
+                verts.append([float(tok[1]), float(tok[2]), float(tok[3])])
+            elif tok[0] == "f":
+                idx = []
+                for t in tok[1:]:
+                    i = int(t.split("/", 1)[0])
+                    i = i - 1 if i > 0 else len(verts) + i
+                    if i < 0 or i >= len(verts) or t.split("/", 1)[0] in ("0", "-0", "+0"):
+                        raise ValueError(f"{path}:{ln}: face index {t} does not name a vertex read so far")
+                    idx.append(i)
+                if len(idx) < 3:
+                    raise ValueError(f"{path}:{ln}: a face needs three corners")
+                faces.extend([idx[0], idx[k], idx[k + 1]] for k in range(1, len(idx) - 1))
+    return np.array(verts, np.float64).reshape(-1, 3), np.array(faces, np.int32).reshape(-1, 3)
+
+
+def read_sdf_text(path: str) -> SdfGrid:
+    """A text .sdf volume (what SignedDensityField.from_sdf reads, omg/sdf_tools.py:169-185; real_world/convert_sdf.py:17-26):
+    three header lines `nx ny nz`, `x0 y0 z0`, `delta`, then one value per line with x running fastest and z slowest ->
+    SdfGrid(data[x, y, z] float32, origin (x0, y0, z0), delta)."""
+    with open(path, "r") as fh:
+        tok = fh.read().split()
+    if len(tok) < 7:
+        raise ValueError(f"{path}: no .sdf header (nx ny nz / x0 y0 z0 / delta)")
+    nx, ny, nz = (int(t) for t in tok[:3])
+    origin = np.array([float(t) for t in tok[3:6]], np.float64)
+    delta = float(tok[6])
+    if min(nx, ny, nz) < 1 or len(tok) - 7 != nx * ny * nz:
+        raise ValueError(f"{path}: the header says {nx} x {ny} x {nz} values, the file holds {len(tok) - 7}")
+    vals = np.array([float(t) for t in tok[7:]], np.float64)
+    return SdfGrid(np.ascontiguousarray(vals.reshape(nz, ny, nx).transpose(2, 1, 0), np.float32), origin, delta)
+
+
+def write_sdf_text(path: str, grid: SdfGrid) -> None:
+    """Inverse of read_sdf_text; numbers are written with repr, so a float32 volume and a float64 header read back unchanged."""
+    data = np.asarray(grid.data)
+    nx, ny, nz = data.shape
+    o = np.asarray(grid.origin, np.float64)
+    with open(path, "w") as fh:
+        fh.write(f"{nx} {ny} {nz}\n{float(o[0])!r} {float(o[1])!r} {float(o[2])!r}\n{float(grid.delta)!r}\n")
+        fh.write("\n".join(repr(float(v)) for v in data.transpose(2, 1, 0).ravel()))
+        fh.write("\n")

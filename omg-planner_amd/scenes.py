@@ -339,6 +339,146 @@ def point_cloud_sdf(points: np.ndarray, grid_resolution: float = 0.02, margin: f
 
 
 # ------------------------------------------------------------------------------------------------
+# signed distance grids from triangle meshes: the specification of omgx_mesh_sdf (csrc/omg_mesh_sdf.hip follows it operation by
+# operation) and the CPU path.  The reference has no counterpart in the planner: it runs a mesh through the external SDFGen binary
+# (real_world/gen_sdf.py:13-37) and reads the text file that comes out (omg/sdf_tools.py:169-185).
+# ------------------------------------------------------------------------------------------------
+MESH_SAMPLE_OFFSET = {"centre": 0.5, "node": 0.0}
+REGION_NAMES = ("a", "b", "ab", "c", "ac", "bc", "interior")  # closest_point_on_triangle's region numbers
+
+
+def _dot3(u, v):
+    return (u[0] * v[0] + u[1] * v[1]) + u[2] * v[2]
+
+
+def closest_point_on_triangle(p, a, b, c):
+    """The point of triangle (a, b, c) closest to each row of p [N,3], by the seven regions of the triangle's plane: the first
+    that holds of vertex a, vertex b, edge ab, vertex c, edge ac, edge bc, else the interior -> (q [N,3], region [N] indexing
+    REGION_NAMES).  float64, every operation rounded on its own, in the order the kernel keeps: dot products as (x*x' + y*y') + z*z',
+    an edge point as base + (num / den) * dir, the interior as (a + ab * v) + ac * w with v = vb * inv, w = vc * inv,
+    inv = 1 / ((va + vb) + vc)."""
+    p = np.asarray(p, np.float64)
+    a, b, c = (np.asarray(v, np.float64) for v in (a, b, c))
+    P = (p[..., 0], p[..., 1], p[..., 2])
+    ab, ac, bc = [b[k] - a[k] for k in range(3)], [c[k] - a[k] for k in range(3)], [c[k] - b[k] for k in range(3)]
+    ap, bp, cp = [P[k] - a[k] for k in range(3)], [P[k] - b[k] for k in range(3)], [P[k] - c[k] for k in range(3)]
+    d1, d2 = _dot3(ab, ap), _dot3(ac, ap)
+    d3, d4 = _dot3(ab, bp), _dot3(ac, bp)
+    d5, d6 = _dot3(ab, cp), _dot3(ac, cp)
+    vc, vb, va = d1 * d4 - d3 * d2, d5 * d2 - d1 * d6, d3 * d6 - d5 * d4
+    e1, e2 = d4 - d3, d5 - d6
+    region = np.select([(d1 <= 0) & (d2 <= 0), (d3 >= 0) & (d4 <= d3), (vc <= 0) & (d1 >= 0) & (d3 <= 0), (d6 >= 0) & (d5 <= d6),
+                        (vb <= 0) & (d2 >= 0) & (d6 <= 0), (va <= 0) & (e1 >= 0) & (e2 >= 0)], [0, 1, 2, 3, 4, 5], 6)
+    on_ab, on_ac, on_bc = region == 2, region == 4, region == 5
+    with np.errstate(divide="ignore", invalid="ignore", over="ignore"):  # the quotients of the regions that do not hold
+        t = np.select([on_ab, on_ac, on_bc], [d1, d2, e1], 0.0) / np.select([on_ab, on_ac, on_bc], [d1 - d3, d2 - d6, e1 + e2], 1.0)
+        inv = 1.0 / ((va + vb) + vc)
+        v, w = vb * inv, vc * inv
+        q = []
+        for k in range(3):
+            base = np.where((region == 1) | on_bc, b[k], np.where(region == 3, c[k], a[k]))
+            edge = base + t * np.where(on_ab, ab[k], np.where(on_ac, ac[k], bc[k]))
+            q.append(np.where(region == 6, (a[k] + ab[k] * v) + ac[k] * w, edge))
+    return np.stack(q, -1), region
+
+
+def clean_mesh(verts, faces):
+    """(verts [V,3] float64, faces [F',3] int32, dropped): the mesh as omgx_mesh_sdf takes it.  Face indices must lie in [0, V)
+    (ValueError otherwise); faces whose normal (b - a) x (c - a) is exactly zero in float64 have no closest-point regions and
+    no solid angle, and are dropped (`dropped` of them)."""
+    verts = np.ascontiguousarray(verts, np.float64)
+    faces = np.asarray(faces)
+    if verts.ndim != 2 or verts.shape[1] != 3 or faces.ndim != 2 or faces.shape[1] != 3:
+        raise ValueError(f"a mesh is verts [V,3] and faces [F,3], got {verts.shape} and {faces.shape}")
+    if not np.issubdtype(faces.dtype, np.integer):
+        raise ValueError(f"face indices must be integers, got {faces.dtype}")
+    if not np.isfinite(verts).all():
+        raise ValueError("a vertex is not finite")
+    if len(verts) < 1 or len(faces) < 1:
+        raise ValueError("a mesh needs at least one vertex and one face")
+    if faces.min() < 0 or faces.max() >= len(verts):
+        raise ValueError(f"face indices must lie in [0, {len(verts)}): found {int(faces.min())} .. {int(faces.max())}")
+    a, b, c = verts[faces[:, 0]], verts[faces[:, 1]], verts[faces[:, 2]]
+    u, v = b - a, c - a
+    keep = ~((u[:, 1] * v[:, 2] - u[:, 2] * v[:, 1] == 0) & (u[:, 2] * v[:, 0] - u[:, 0] * v[:, 2] == 0) &
+             (u[:, 0] * v[:, 1] - u[:, 1] * v[:, 0] == 0))
+    if not keep.any():
+        raise ValueError("every face of the mesh has zero area")
+    return verts, np.ascontiguousarray(faces[keep], np.int32), int((~keep).sum())
+
+
+def mesh_grid_layout(verts, delta: float, padding: int):
+    """(origin [3] float64, dims [3] int) of a grid around a mesh: `padding` voxels on every side of the vertices' bounding box
+    [lo, hi]: origin = lo - padding * delta, dims = ceil((hi - lo) / delta) + 2 * padding (float64)."""
+    verts = np.asarray(verts, np.float64)
+    lo, hi = verts.min(0), verts.max(0)
+    dims = np.array([int(np.ceil((hi[a] - lo[a]) / delta)) + 2 * int(padding) for a in range(3)], np.int64)
+    return lo - int(padding) * float(delta), dims
+
+
+def mesh_nodes(origin, dims, delta: float, sample: str = "centre") -> np.ndarray:
+    """The sample positions [X*Y*Z, 3] (x-major) of a grid: origin + ((i, j, k) + offset) * delta, offset 0.5 for "centre" and 0.0 for
+    "node" (see mesh_sdf)."""
+    off = MESH_SAMPLE_OFFSET[sample]
+    ax = [origin[a] + (np.arange(int(dims[a])).astype(np.float64) + off) * float(delta) for a in range(3)]
+    return np.stack([g.ravel() for g in np.meshgrid(*ax, indexing="ij")], -1)
+
+
+def mesh_distance_winding(verts, faces, p):
+    """(d [N], w [N]) float64 for the points p [N,3]: d = sqrt(min over faces |p - closest_point_on_triangle(p, face)|^2) with
+    |r|^2 = (rx*rx + ry*ry) + rz*rz, and the generalised winding number
+    w = (1 / 4 pi) sum over faces 2 atan2(A.(BxC), |A||B||C| + (A.B)|C| + (B.C)|A| + (C.A)|B|), A, B, C = a - p, b - p, c - p.
+    verts / faces as clean_mesh returns them.  Vectorised over the points with a loop over the faces."""
+    p = np.asarray(p, np.float64)
+    best = np.full(len(p), 1.0e300)
+    wsum = np.zeros(len(p))
+    for f in faces:
+        a, b, c = verts[f[0]], verts[f[1]], verts[f[2]]
+        q, _ = closest_point_on_triangle(p, a, b, c)
+        r = [p[:, k] - q[:, k] for k in range(3)]
+        dd = (r[0] * r[0] + r[1] * r[1]) + r[2] * r[2]
+        best = np.where(dd < best, dd, best)
+        A, B, C = [a[k] - p[:, k] for k in range(3)], [b[k] - p[:, k] for k in range(3)], [c[k] - p[:, k] for k in range(3)]
+        la, lb, lc = np.sqrt(_dot3(A, A)), np.sqrt(_dot3(B, B)), np.sqrt(_dot3(C, C))
+        n = [B[1] * C[2] - B[2] * C[1], B[2] * C[0] - B[0] * C[2], B[0] * C[1] - B[1] * C[0]]
+        wsum += np.arctan2(_dot3(A, n), ((la * lb) * lc + _dot3(A, B) * lc) + (_dot3(B, C) * la + _dot3(C, A) * lb))
+    return np.sqrt(best), wsum * (2.0 / (4.0 * np.pi))
+
+
+def mesh_sdf(verts, faces, delta: float, padding: int = 4, sample: str = "centre", origin=None, dims=None) -> SdfGrid:
+    """Signed distance grid of a triangle mesh -> SdfGrid (float32 data[x, y, z], origin, delta).  Sample i of an axis sits at
+    origin + (i + offset) * delta:
+
+    * sample="centre" (offset 0.5, the default) is where the SDF op reads a grid: it interpolates at p / delta - 0.5
+      (layers/sdf_matching_loss_kernel.cu:36-41; `_voxel_centres`, what sphere_sdf / box_sdf fill), so this is the
+      convention that makes the looked-up distance right;
+    * sample="node" (offset 0.0) is the convention of the text .sdf files the reference consumes as far as its reader shows
+      (sdf_tools.py:169-185 takes origin and delta from the header and keeps them as min_coords and voxel size).  The program
+      that writes those files, SDFGen, is not part of the reference and nothing here pins where it samples.
+
+    origin / dims default to mesh_grid_layout(verts, delta, padding); given explicitly they align the grid with another one.
+    Value: mesh_distance_winding's d, negated where |w| > 0.5 (inside; |w| so that a mesh whose faces all point inwards gives the
+    same volume), rounded to float32 once.  Faces of zero area are dropped (clean_mesh).  Plain numpy float64: the specification
+    of omgx_mesh_sdf (ops.mesh_sdf gives the same float32 magnitudes bit for bit) and the CPU path; it may be slow."""
+    verts, faces, _ = clean_mesh(verts, faces)
+    if sample not in MESH_SAMPLE_OFFSET:
+        raise ValueError(f"sample must be 'centre' or 'node', got {sample!r}")
+    delta = float(delta)
+    if not (delta > 0 and np.isfinite(delta)):
+        raise ValueError("delta must be positive and finite")
+    if (origin is None) != (dims is None):
+        raise ValueError("give origin and dims together")
+    if origin is None:
+        origin, dims = mesh_grid_layout(verts, delta, padding)
+    origin = np.asarray(origin, np.float64).copy()
+    dims = tuple(int(d) for d in dims)
+    if min(dims) < 1:
+        raise ValueError(f"dims must be >= 1, got {dims}")
+    d, w = mesh_distance_winding(verts, faces, mesh_nodes(origin, dims, delta, sample))
+    return SdfGrid(np.where(np.abs(w) > 0.5, -d, d).astype(np.float32).reshape(dims), origin, delta)
+
+
+# ------------------------------------------------------------------------------------------------
 # per-object SDF-layer parameters (Cost.compute_obstacle_cost_layer, omg/cost.py:303-328)
 # ------------------------------------------------------------------------------------------------
 def layer_params(scene: Scene, epsilon=0.2, target_epsilon=0.1, clearance=0.01, target_clearance=0.0,
