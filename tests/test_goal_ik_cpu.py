@@ -239,3 +239,219 @@ def test_ik_kernel_does_not_spill(tmp_path):
     block = text[start: text.index("; Occupancy:", start) + 40]
     assert int(re.search(r"; ScratchSize: (\d+)", block).group(1)) == 0
     assert int(re.search(r"; Occupancy: (\d+)", block).group(1)) >= 1
+
+
+# ---- the directed cases of tests/ik_cases.py: each is what it claims, away from every threshold, and stable --------------------
+
+import ik_cases as ikc  # noqa: E402
+
+
+@pytest.fixture(scope="module")
+def blocks(model):
+    return ikc.newton_blocks(model)
+
+
+@pytest.fixture(scope="module")
+def traces(model, blocks):
+    return {name: ikc.trace(model, b.R, b.t, b.seeds, b.k) for name, b in blocks.items()}
+
+
+def test_trace_is_the_restatements_loop(model, blocks, traces):
+    for name, b in blocks.items():
+        q, _, _ = ikr.solve(model, b.R, b.t, b.seeds, max_iter=b.k)
+        assert np.array_equal(q, traces[name][0]), name
+
+
+def test_directed_blocks_take_their_branch(model, blocks):
+    """Every pair of every block takes the block's branch at its first step; the half turns take all three sub-branches, each
+    pair the one of its axis' largest component; the kept near-singular steps are clamped by the limits."""
+    for name, b in blocks.items():
+        census = ikc.branch_census(model, b.R, b.t, b.seeds, b.k)
+        assert census["first"][b.branch].all(), (name, census["counts"])
+        assert census["steps"] == b.k * len(b.seeds), name  # nothing converges on the way: every update is compared
+        if b.branch == "half_turn":
+            for a, sub in enumerate(("half_turn_x", "half_turn_y", "half_turn_z")):
+                assert np.array_equal(census["first"][sub], ikc.AXIS_LARGEST[b.axis] == a), (name, sub)
+                assert census["counts"][sub] >= 8
+        if name == "singular_kept":
+            assert census["first"]["clamped"].all()
+    lo, hi = ikr.limits(model)
+    inside = lambda q: ((q >= lo) & (q <= hi)).all(-1)
+    assert inside(blocks["half_turn"].seeds).all()
+    assert inside(ikc.SINGULAR).tolist() == [True, True, False]
+
+
+def test_random_generators_miss_the_directed_branches(model):
+    """The gap the directed blocks close: 512 pairs of each random generator of test_gpu_goal_ik.py take no half-turn arm and
+    drop no singular value."""
+    for k in (1, 5):
+        census = ikc.branch_census(model, *ikc.random_pairs(model, 512, k), k)
+        print("random pairs, k =", k, census["steps"], census["counts"])
+        for b in ("half_turn", "half_turn_x", "half_turn_y", "half_turn_z", "dropped"):
+            assert census["counts"][b] == 0, (k, b)
+    census = ikc.branch_census(model, *ikc.random_full_solves(model, 512), 100)
+    print("random full solves", census["steps"], census["counts"])
+    for b in ("half_turn", "half_turn_x", "half_turn_y", "half_turn_z", "dropped"):
+        assert census["counts"][b] == 0, b
+
+
+def _decided(x, lo, hi):
+    """A test `every x_i < threshold` is decided away from the threshold: all of x [n,m] below lo, or the largest above hi."""
+    top = x.max(-1)
+    return bool(((top < lo) | (top > hi)).all())
+
+
+def test_directed_blocks_keep_their_margins(blocks, traces):
+    """No comparison a directed step decides by sits near its threshold, at any of the block's k steps: GetRot's symmetry test
+    against 1e-6 (all three asymmetries below 0.5e-6, or one above 2e-6), its identity test against 1e-5 (0.5e-5 / 2e-5), every
+    singular value against pinv_eps = 1e-5 (outside [0.5e-5, 2e-5]), and the half turns' largest of xx, yy, zz ahead of the
+    next by 0.05.  The one exception is stated with its block: "tiny_turn_identity_4e-7" has the angle the blocks were asked
+    with, whose asymmetry 2 sin(4e-7) |axis_i| <= 8e-7 is 20 % below 1e-6, not 50 % (2e-7 away: 1e9 roundings)."""
+    for name, (_, steps) in traces.items():
+        for i, step in enumerate(steps):
+            br = ikc.step_branches(step)
+            if name == "tiny_turn_identity_4e-7" and i == 0:
+                assert (step["asym"] <= 8.0e-7 * (1 + 1e-9)).all(), name
+            else:
+                assert _decided(step["asym"], 0.5e-6, 2e-6), (name, i)
+            sym = br["half_turn"] | br["identity"]
+            assert _decided(step["ident"][sym], 0.5e-5, 2e-5), (name, i)
+            assert not ((step["sigma"] >= 0.5e-5) & (step["sigma"] <= 2e-5)).any(), (name, i)
+            top = np.sort(step["diag"][br["half_turn"]], axis=-1)
+            assert (top[:, 2] - top[:, 1] >= 0.05).all(), (name, i)
+
+
+def test_near_singular_seeds_bracket_pinv_eps(model):
+    for sigma, (a, b) in ((0.0, (0.0, 1e-12)), (ikc.SIGMA_DROPPED, (2e-6, 5e-6)), (ikc.SIGMA_KEPT, (2e-5, 5e-5))):
+        _, t, z, p = ikr.hand_kinematics(model, ikc.singular_seeds(sigma))
+        S = np.linalg.svd(ikr.jacobian(t, z, p), compute_uv=False)
+        assert ((S[:, 5] >= a) & (S[:, 5] < b)).all() and (S[:, 4] > 0.1).all(), (sigma, S[:, 4:])
+
+
+def test_directed_updates_are_the_definition(model, blocks):
+    """One update of the restatement on every directed pair equals clip(q + pinv_step(jacobian, twist_diff)) of the 4x4
+    kinematics and LAPACK's SVD, within test_solver_arithmetic_is_the_definition's bars: 1e-11, and 1e-9 where rounding is
+    amplified — by a singular value below 1e-2 (that test's own split), or, in "near_half_turn", by the normalisation of an axis
+    of length 2e-5 (1e-16 / 2e-5 * pi * |J^+| ~ 1e-10)."""
+    lo, hi = ikr.limits(model)
+    for name, b in blocks.items():
+        R, t, z, p = ikr.hand_kinematics(model, b.seeds)
+        J = ikr.jacobian(t, z, p)
+        want = np.clip(b.seeds + ikr.pinv_step(J, ikr.twist_diff(R, t, b.R, b.t)), lo, hi)
+        got, _, _ = ikr.solve(model, b.R, b.t, b.seeds, max_iter=1)
+        small = (np.linalg.svd(J, compute_uv=False).min(-1) <= 1e-2) | (name == "near_half_turn")
+        err = np.abs(got - want).max(-1)
+        print(name, "restatement - definition:", err[~small].max(initial=0.0), err[small].max(initial=0.0))
+        assert (err[~small] <= 1e-11).all() and (err[small] <= 1e-9).all(), name
+
+
+def test_rotvec_half_turn_arms_return_pi_times_the_axis():
+    """All three arms of the half-turn branch, the y-largest one included, on axes with three non-zero components: pi times the
+    axis, its largest component positive."""
+    for axis, big in zip(ikc.AXES, ikc.AXIS_LARGEST):
+        want = np.pi * axis * np.sign(axis[big])
+        for theta in (np.pi, np.pi - 1e-7):
+            np.testing.assert_allclose(ikr.rotvec(ikc.rotation(axis, theta)[None])[0], want, rtol=0, atol=2e-7)
+        np.testing.assert_allclose(ikr.rotvec(ikc.rotation(axis, np.pi)[None])[0], want, rtol=0, atol=1e-15)
+
+
+def _kdl_route(R):
+    H = np.tile(np.eye(4), R.shape[:-2] + (1, 1))
+    H[..., :3, :3] = R
+    return np.array([ikr.kdl_target(h) for h in H.reshape(-1, 4, 4)]).reshape(R.shape)
+
+
+def test_directed_blocks_are_stable(model, blocks, traces):
+    """A block is compared on the device only where rounding cannot decide it: with its targets through the reference's
+    quaternion route (kdl_target: ~1e-16 off) the restatement's result after the block's k updates moves by at most 1e-11, a
+    tenth of the device bar.  A block that does not meet this is not compared on the device (ik_cases.newton_blocks)."""
+    assert [n for n, b in blocks.items() if not b.on_device] == ["near_half_turn"]
+    for name, b in blocks.items():
+        if not b.on_device:
+            continue
+        q, _, _ = ikr.solve(model, _kdl_route(b.R), b.t, b.seeds, max_iter=b.k)
+        moved = np.abs(q - traces[name][0]).max()
+        print(name, "k =", b.k, "moved", moved)
+        assert moved <= 1e-11, (name, moved)
+
+
+def chain_restatement(model, targets, grasp_begin, seeds, use_standoff=True, accept_diff=2.0, max_iter=ikr.MAX_ITER, record=None):
+    """omgx_goal_ik's contract (include/omg_hip.h, section 10) on ikr.solve: targets [N,T,4,4], grasp_begin [S+1], seeds [S,K,7]
+    -> (status [N,K], solutions [N,K,T,7], iterations [N,K,1+T] ([N,K,1] without standoff))."""
+    targets, seeds = np.asarray(targets, np.float64), np.asarray(seeds, np.float64)
+    (N, T), K = targets.shape[:2], seeds.shape[1]
+    scene = np.searchsorted(np.asarray(grasp_begin), np.arange(N), side="right") - 1
+    q0 = seeds[scene].reshape(N * K, 7)  # chain c = n * K + k
+    pose = lambda k: (np.repeat(targets[:, k, :3, :3], K, 0), np.repeat(targets[:, k, :3, 3], K, 0))
+    status = np.zeros(N * K, np.int32)
+    sols = np.zeros((N * K, T, 7))
+    its = np.full((N * K, 1 + T if use_standoff else 1), -1, np.int32)
+    q, alive, its[:, 0] = ikr.solve(model, *pose(T - 1 if use_standoff else 0), q0, max_iter=max_iter, record=record)
+    status[~alive] = 1
+    if not use_standoff:
+        sols[:, 0] = q
+    else:
+        for k in range(T):
+            idx = np.nonzero(alive)[0]
+            TR, Tt = pose(k)
+            q[idx], ok, its[idx, 1 + k] = ikr.solve(model, TR[idx], Tt[idx], q[idx], max_iter=max_iter, record=record)
+            sols[idx, k] = q[idx]
+            status[idx[~ok]] = 2 + k
+            alive[idx[~ok]] = False
+        for c in np.nonzero(alive)[0]:
+            if not np.linalg.norm(np.diff(sols[c], axis=0)) < accept_diff:
+                status[c] = -1
+    return status.reshape(N, K), sols.reshape(N, K, T, 7), its.reshape(N, K, -1)
+
+
+def chain_norms(solutions):
+    """The Frobenius norm the acceptance test compares, per chain: [N,K]."""
+    return np.sqrt((np.diff(solutions, axis=2) ** 2).sum((-1, -2)))
+
+
+def run_chain_block(model, b, record=None, route=None, accept_diff=None):
+    targets = b.targets
+    if route is not None:
+        targets = targets.copy()
+        targets[..., :3, :3] = route(targets[..., :3, :3])
+    return chain_restatement(model, targets, b.grasp_begin, b.seeds, b.use_standoff, b.accept_diff if accept_diff is None else
+                             accept_diff, b.max_iter, record)
+
+
+@pytest.fixture(scope="module")
+def chains(model):
+    return ikc.chain_blocks(model)
+
+
+@pytest.mark.parametrize("name", ["accepted", "presolve_fails", "chained_fails_0", "chained_fails_2", "tail_of_one_accepted",
+                                  "tail_of_one_rejected", "single_solve_fails", "limits"])
+def test_chain_blocks_follow_the_fixture_rules(model, chains, name):
+    """make_ik_golden.py's rules for a chain that is compared on the device: no result moves by more than 1e-9 between matrix
+    and quaternion-route targets, and every residual a solve checked is at least 0.1 % away from eps; and the block reports
+    what ik_cases says it does."""
+    b = chains[name]
+    record = []
+    st, sol, its = run_chain_block(model, b, record)
+    st2, sol2, its2 = run_chain_block(model, b, route=_kdl_route)
+    assert np.array_equal(st, st2) and np.array_equal(its, its2)
+    assert np.abs(sol - sol2).max() <= 1e-9, np.abs(sol - sol2).max()
+    res = np.concatenate(record)
+    assert (np.abs(res - ikr.EPS) >= 1e-3 * ikr.EPS).all()
+    T = b.targets.shape[1]
+    if b.status is not None:
+        assert (st == b.status).all(), st
+    if name == "limits":
+        assert b.targets.shape[1] == 16 and b.seeds.shape[1] == 64 and (st == 0).any() and (st > 0).any()
+    if b.status in (0, -1) and b.use_standoff:
+        assert (its >= 0).all() and (its < b.max_iter).all()
+        norm = chain_norms(sol)
+        if T > 1:  # accept_diff at half the smallest norm rejects all, at twice the largest accepts all
+            assert norm.min() > 1e-3
+            assert (run_chain_block(model, b, accept_diff=0.5 * norm.min())[0] == -1).all()
+            assert (run_chain_block(model, b, accept_diff=2.0 * norm.max())[0] == 0).all()
+        else:
+            assert (norm == 0).all()
+    if b.status is not None and b.status > 0:  # the failed solve holds max_iter, the ones after it did not run
+        j = b.status - 1
+        assert (its[..., j] == b.max_iter).all() and (its[..., j + 1:] == -1).all() and (its[..., :j] < b.max_iter).all()
+        assert (sol[:, :, max(j, 1):] == 0).all()

@@ -223,3 +223,147 @@ def test_tabletop_grasps_to_plan(dev, model):
     assert np.isfinite(info[:, 0]).all()
     final = eng.end.cpu().numpy()[0]  # the goal the plan ends at
     assert np.abs(goal_set[0] - final[None]).max(axis=1).min() == 0.0
+
+
+# ---- the directed cases of tests/ik_cases.py (each proven to take its branch, away from every threshold and stable, by
+# test_goal_ik_cpu.py) and the raw contract of omgx_goal_ik (include/omg_hip.h, section 10) -------------------------------------
+
+import ik_cases as ikc  # noqa: E402
+from test_goal_ik_cpu import chain_norms, chain_restatement  # noqa: E402
+
+NEWTON_BLOCKS = ["half_turn", "tiny_turn_identity", "tiny_turn_identity_4e-7", "tiny_turn_general", "singular", "singular_dropped",
+                 "singular_kept"]
+CHAIN_BLOCKS = ["accepted", "presolve_fails", "chained_fails_0", "chained_fails_2", "tail_of_one_accepted", "tail_of_one_rejected",
+                "single_solve_fails", "limits"]
+
+
+@pytest.fixture(scope="module")
+def blocks(model):
+    return ikc.newton_blocks(model)
+
+
+@pytest.fixture(scope="module")
+def chains(model):
+    return ikc.chain_blocks(model)
+
+
+def test_every_stable_block_is_compared(blocks, chains):
+    assert NEWTON_BLOCKS == [n for n, b in blocks.items() if b.on_device] and CHAIN_BLOCKS == list(chains)
+
+
+@pytest.mark.parametrize("name", NEWTON_BLOCKS)
+def test_directed_newton_blocks_match_restatement(dev, model, blocks, name):
+    """The joint vector after the block's k updates, every pair of it: GetRot's half-turn arms (x, y, z largest), its identity
+    case with the position still off, the general case at 3e-6, and seeds at and next to singular configurations, where the
+    pseudo-inverse drops a singular value (sigma_min ~ 0 and 3.2e-6) or keeps a small one (3.2e-5)."""
+    b = blocks[name]
+    st, q, its = _device_single(model, dev, b.R, b.t, b.seeds, max_iter=b.k, want_iterations=True)
+    qr, ok, itr = ikr.solve(model, b.R, b.t, b.seeds, max_iter=b.k)
+    np.testing.assert_array_equal(st == 0, ok)
+    np.testing.assert_array_equal(its, itr)
+    print(name, "max |q - q_ref| =", np.abs(q - qr).max())
+    assert np.abs(q - qr).max() <= 1e-10, np.abs(q - qr).max()
+
+
+def test_half_turn_solves_reach_their_targets(dev, model, blocks):
+    """The half-turn pairs run to 100 iterations: what the device reports solved reaches its target by pose_table, as in
+    test_full_solves_agree_with_restatement."""
+    from omg_planner_amd import ops
+    b = blocks["half_turn"]
+    st, q, _ = _device_single(model, dev, b.R, b.t, b.seeds)
+    dok = st == 0
+    assert dok.any()
+    qs = np.concatenate([q[dok], np.full((int(dok.sum()), 2), 0.04)], axis=1)
+    tab = ops.pose_table(ops.robot_blob(model, dev), model.points_per_link,
+                         torch.as_tensor(qs, dtype=torch.float64, device=dev)).cpu().numpy()[:, 7]
+    assert np.abs(tab[:, 9:12] - b.t[dok]).max() <= 2e-6
+    assert np.abs(tab[:, :9].reshape(-1, 3, 3) - b.R[dok]).max() <= 2e-6
+    lo, hi = ikr.limits(model)
+    assert (q[dok] >= lo).all() and (q[dok] <= hi).all()
+
+
+def _device_chains(model, dev, b, accept_diff=None, targets=None, grasp_begin=None, seeds=None):
+    from omg_planner_amd import ops
+    H = b.targets if targets is None else targets
+    K = (b.seeds if seeds is None else seeds).shape[1]
+    # the outputs are torch.empty: hand the allocator blocks of their sizes that hold no zeros, so that a slot reads 0 because
+    # the kernel wrote it
+    poison = [torch.full((H.shape[0], K, H.shape[1], 7), 7.0, dtype=torch.float64, device=dev),
+              torch.full((H.shape[0], K, 1 + H.shape[1]), 7, dtype=torch.int32, device=dev)]
+    del poison
+    rows = np.concatenate([H[..., :3, :3].reshape(*H.shape[:2], 9), H[..., :3, 3]], axis=-1)
+    out = ops.goal_ik(ops.robot_blob(model, dev), model.points_per_link, torch.as_tensor(rows, dtype=torch.float64, device=dev).contiguous(),
+                      b.grasp_begin if grasp_begin is None else grasp_begin,
+                      torch.as_tensor(b.seeds if seeds is None else seeds, dtype=torch.float64, device=dev).contiguous(),
+                      use_standoff=b.use_standoff, max_iter=b.max_iter, accept_diff=b.accept_diff if accept_diff is None else accept_diff,
+                      want_iterations=True)
+    torch.cuda.synchronize()
+    return out
+
+
+def _check_contract(model, b, got, want):
+    """status and iterations integer-equal, solutions to 1e-6 (the fixture tests' bar); per chain: the slots after a failed solve
+    exactly 0, the failed solve's own slot non-zero and inside the limits, max_iter in its iterations entry and -1 after it."""
+    st, sol, its = (x.cpu().numpy() for x in got)
+    rst, rsol, rits = want
+    np.testing.assert_array_equal(st, rst)
+    np.testing.assert_array_equal(its, rits)
+    assert np.abs(sol - rsol).max() <= 1e-6, np.abs(sol - rsol).max()
+    lo, hi = ikr.limits(model)
+    T = sol.shape[2]
+    for n, k in np.ndindex(st.shape):
+        j = int(st[n, k]) - 1  # the solve that failed: 0 the first, 1 + t the chained solve of pose t
+        if j < 0:
+            assert (its[n, k] >= 0).all() and (its[n, k] < b.max_iter).all() and (sol[n, k] != 0).any(axis=-1).all()
+            continue
+        assert its[n, k, j] == b.max_iter and (its[n, k, j + 1:] == -1).all() and (its[n, k, :j] < b.max_iter).all()
+        slot = j - 1 if b.use_standoff else 0  # the pre-solve of a chain with standoff has no slot
+        assert (sol[n, k, slot + 1:] == 0.0).all()
+        if slot >= 0:
+            assert (sol[n, k, slot] != 0).any() and (sol[n, k, slot] >= lo).all() and (sol[n, k, slot] <= hi).all()
+    return st, sol, its
+
+
+@pytest.fixture(scope="module")
+def chain_refs(model, chains):
+    return {n: chain_restatement(model, b.targets, b.grasp_begin, b.seeds, b.use_standoff, b.accept_diff, b.max_iter)
+            for n, b in chains.items()}
+
+
+@pytest.mark.parametrize("name", CHAIN_BLOCKS)
+def test_chain_contract(dev, model, chains, chain_refs, name):
+    """status 0 / 1 / 2 + k / -1, the solutions' slots and the iterations' entries of section 10, chain by chain.  A pose 3 m away
+    at k = T - 1 fails the pre-solve, which solves that pose: status 1, never 2 + (T - 1); T = 1 with standoff has a zero
+    norm, accepted under accept_diff = 2 and rejected under 0."""
+    b = chains[name]
+    st, _, _ = _check_contract(model, b, _device_chains(model, dev, b), chain_refs[name])
+    if b.status is not None:
+        assert (st == b.status).all()
+
+
+def test_accept_diff_rejects_and_accepts(dev, model, chains, chain_refs):
+    """The accepted chains again with accept_diff at half the smallest Frobenius norm of theirs (the restatement's): all -1;
+    at twice the largest: all 0.  Their solutions do not depend on it."""
+    b = chains["accepted"]
+    rst, rsol, rits = chain_refs["accepted"]
+    norm = chain_norms(rsol)
+    for accept_diff, status in ((0.5 * norm.min(), -1), (2.0 * norm.max(), 0)):
+        st, _, _ = _check_contract(model, b, _device_chains(model, dev, b, accept_diff), (np.full_like(rst, status), rsol, rits))
+        assert (st == status).all()
+
+
+def test_limits_call_equals_per_scene_calls(dev, model, chains):
+    """T = OMGX_IK_MAX_TAIL and K = OMGX_IK_MAX_SEEDS, an empty scene before the full one: bit for bit what a call per scene
+    gives; one more pose or seed is refused."""
+    from omg_planner_amd import _lib
+    b = chains["limits"]
+    assert b.targets.shape[1] == 16 and b.seeds.shape[1] == 64 and list(b.grasp_begin) == [0, 0, 2]
+    st, sol, its = _device_chains(model, dev, b)
+    e_st, e_sol, e_its = _device_chains(model, dev, b, targets=b.targets[:0], grasp_begin=[0, 0], seeds=b.seeds[:1])
+    assert e_st.shape == (0, 64) and e_sol.shape == (0, 64, 16, 7) and e_its.shape == (0, 64, 17)
+    f_st, f_sol, f_its = _device_chains(model, dev, b, grasp_begin=[0, 2], seeds=b.seeds[1:])
+    assert torch.equal(st, f_st) and torch.equal(sol, f_sol) and torch.equal(its, f_its)
+    with pytest.raises(_lib.OmgHipError):
+        _device_chains(model, dev, b, targets=np.concatenate([b.targets, b.targets[:, :1]], axis=1))
+    with pytest.raises(_lib.OmgHipError):
+        _device_chains(model, dev, b, seeds=np.concatenate([b.seeds, b.seeds[:, :1]], axis=1))
