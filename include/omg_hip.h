@@ -717,6 +717,78 @@ int omgx_mesh_sdf(const double* verts, const int32_t* faces, const omgx_mesh* me
                   int32_t num_meshes, float* out, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * (13) omgx_mesh_raycast, omgx_grasp_poses: antipodal grasp sets from meshes
+ * Replaces the grasp files the reference reads (data/grasps/simulated/<object>.npy, omg/planner.py:457-500): rays from sampled
+ * surface points through the mesh give contact pairs, every pair `num_angles` hand poses about its closing axis, and the
+ * object's own volume in the pool decides which of them the gripper fits.  omg-planner_amd/grasps.py (mesh_raycast, grasp_poses)
+ * is the specification; all arithmetic is float64 without contraction, dot products as (x*x' + y*y') + z*z', cross products as
+ * a*b - c*d per component, and the results have the specification's bits.  New entry points only: no earlier signature or
+ * struct changes, so omgx_abi_version() stays 14.
+ *
+ * A launch takes a ragged batch: M meshes (the omgx_mesh records and the vertex / face pools of omgx_mesh_sdf), mesh m owning the
+ * rays [h_ray_begin[m], h_ray_begin[m] + h_ray_count[m]) of the ray arrays (num_rays rows; ranges must not overlap; a mesh with
+ * zero rays is legal and skipped; rows outside every range are neither read nor written).  The work list has one omgx_ray_work
+ * per workgroup: for every mesh in order, its rays in groups of OMGX_RAYCAST_RAYS_PER_WORKGROUP, and for every group `chunks`
+ * records in chunk order whose face ranges tile [0, face_count) in ascending order (a range may be empty).  `work` is the list on
+ * the device, `h_work` the same on the host; ALL checks are made on the host copies (h_meshes, h_ray_*, h_work) before any HIP call.
+ *
+ * omgx_mesh_raycast: for ray (o, d) and the faces (a, b, c) of its mesh in face order (Moeller-Trumbore):
+ *   e1 = b - a, e2 = c - a, h = d x e2, det = e1 . h, inv = 1.0 / det, s = o - a,
+ *   u = (s . h) * inv, q = s x e1, v = (d . q) * inv, t = (e2 . q) * inv
+ *   a face hits iff (u >= -tol) & (v >= -tol) & (u + v <= 1 + tol) & (t > t_min) & (t < best), from best = +inf, face = -1: the
+ *   nearest hit, the lowest face index of a tie.  No test on det: a parallel ray gives inf or NaN, every comparison is false.
+ *   t_out [num_rays] double, face_out [num_rays] int32 (index local to the mesh; -1 and +inf: no hit).
+ *   chunks: 1..OMGX_RAYCAST_MAX_CHUNKS workgroups share the faces of a ray group, partial results go to `workspace`
+ *   (omgx_mesh_raycast_workspace_bytes(num_rays, chunks) bytes; may be NULL with one chunk) and a second kernel folds them in
+ *   chunk order with the same strict <, so the result does not depend on the split.  0: omgx_mesh_raycast_chunks(ray groups,
+ *   largest face count, 0), which the list must have been built for.
+ * omgx_mesh_raycast_chunks(ray_workgroups, max_faces, chunks): chunks if > 0, else the automatic choice
+ *   min(ceil(4 * compute units / ray_workgroups), ceil(max_faces / omgx_mesh_sdf_tile()), OMGX_RAYCAST_MAX_CHUNKS) >= 1
+ *   (needs a device; OMGX_ERR_LAUNCH without one).
+ * OMGX_ERR_INVALID: a null pointer, M < 1, a negative count, chunks < 0 or > OMGX_RAYCAST_MAX_CHUNKS, t_min or tol negative or
+ * not finite, a mesh without vertices or faces or with a negative begin, a ray range outside [0, num_rays], a work list that is
+ * not the one described above (does not cover the rays, wrong order, face ranges that do not tile the mesh), ray ranges of two
+ * meshes that overlap, no workspace with chunks > 1.
+ *
+ * omgx_grasp_poses: one hand pose per (ray, angle); the hand frame is the reference's drawing (omg/util.py:308-320): z the
+ * approach direction, y the closing axis, fingers at y = +-0.043, palm at z = 0.058, finger tips at z = 0.098.
+ *   p1, n1, dirs [num_rays][3], t [num_rays], face2 [num_rays] (omgx_mesh_raycast's outputs), normals [F_total][3] unit face
+ *   normals in the face pool's order, cs [num_angles][2] = (cos, sin)(2 pi a / num_angles) (no trigonometry on the device)
+ *   antipodal iff face2 >= 0, min_width <= t <= max_width, -(d . n1) >= cos_cone, d . n2 >= cos_cone (n2 = normals[face2])
+ *   y = d; m = p1 + (0.5 * t) * d; k = the first axis with the smallest |d_k|; b1 = (e_k x d) / sqrt((e_k x d) . (e_k x d))
+ *   with e_0 x d = (0, -dz, dy), e_1 x d = (dz, 0, -dx), e_2 x d = (-dy, dx, 0); b2 = d x b1; z = c * b1 + s * b2; x = y x z;
+ *   pose = [x y z | m - pad_depth * z] -> poses [num_rays][num_angles][4][4] row-major; sixteen zeros when not antipodal
+ *   gripper: every probe point q [num_probe][3] (hand frame) at w = ((x*q0 + y*q1) + z*q2) + o is looked up in the mesh's volume
+ *   (pool + out_offset, x-major, dims, origin, delta, sample_offset of its omgx_mesh: what omgx_mesh_sdf wrote) at the nearest
+ *   sample idx_a = floor((w_a - origin_a) / delta + (0.5 - sample_offset)); outside the grid: free; value < (float)clearance:
+ *   collides.  valid [num_rays][num_angles] uint8 = antipodal and no probe point collides.
+ *   work / h_work / chunks: the ray-cast's list (its chunk-0 records are used), or one built with chunks = 1.
+ * OMGX_ERR_INVALID: as above, and num_angles outside [1, 65535], a dims < 1, delta <= 0 or not finite, a sample_offset other
+ * than 0.0 / 0.5, an origin that is not finite, a volume outside [0, pool_elems), a NaN parameter.  OMGX_ERR_UNSUPPORTED: more
+ * than 2^31 nodes in one volume.
+ * ------------------------------------------------------------------------------------------- */
+#define OMGX_RAYCAST_RAYS_PER_WORKGROUP 256
+#define OMGX_RAYCAST_MAX_CHUNKS 64
+typedef struct omgx_ray_work {
+    int32_t mesh;                   /* index into meshes                                        */
+    int32_t ray_begin, ray_count;   /* this group's rows of the ray arrays (1..256 rays)        */
+    int32_t face_begin, face_count; /* this chunk's faces, local to the mesh                    */
+    int32_t chunk;                  /* 0..chunks-1: the workspace row this workgroup writes     */
+} omgx_ray_work; /* sizeof == 24 */
+int32_t omgx_mesh_raycast_chunks(int32_t ray_workgroups, int32_t max_faces, int32_t chunks);
+int64_t omgx_mesh_raycast_workspace_bytes(int32_t num_rays, int32_t chunks);
+int omgx_mesh_raycast(const double* verts, const int32_t* faces, const omgx_mesh* meshes, const omgx_mesh* h_meshes,
+                      int32_t num_meshes, const int32_t* h_ray_begin, const int32_t* h_ray_count, const omgx_ray_work* work,
+                      const omgx_ray_work* h_work, int32_t num_work, int32_t chunks, const double* origins, const double* dirs,
+                      int32_t num_rays, double t_min, double tol, double* t_out, int32_t* face_out, void* workspace, void* stream);
+int omgx_grasp_poses(const omgx_mesh* meshes, const omgx_mesh* h_meshes, int32_t num_meshes, const int32_t* h_ray_begin,
+                     const int32_t* h_ray_count, const omgx_ray_work* work, const omgx_ray_work* h_work, int32_t num_work,
+                     int32_t chunks, const double* p1, const double* n1, const double* dirs, const double* t, const int32_t* face2,
+                     int32_t num_rays, const double* normals, const double* cs, int32_t num_angles, const double* probe,
+                     int32_t num_probe, const float* pool, int64_t pool_elems, double max_width, double min_width, double cos_cone,
+                     double pad_depth, double clearance, double* poses, uint8_t* valid, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Diagnostics
  * ------------------------------------------------------------------------------------------- */
 const char* omgx_last_error(void); /* thread-local text of the last OMGX_ERR_LAUNCH               */

@@ -25,7 +25,8 @@ EXPORTS = ["omgx_sdf_loss_forward", "omgx_fk_sdf_workspace_bytes", "omgx_fk_sdf"
            "omgx_goalset_workspace_bytes", "omgx_goalset_cost", "omgx_goalset_cost_layer", "omgx_goalset_parts", "omgx_goalset_cost_layer_tiled", "omgx_goalset_cost_layer_parts", "omgx_goalset_schedule_len", "omgx_goalset_schedule", "omgx_goalset_schedule_parts", "omgx_goalset_schedule_ordered", "omgx_region_scratch_bytes", "omgx_object_set_grid", "omgx_fit_influence_region", "omgx_regions_scratch_bytes", "omgx_fit_influence_regions", "omgx_volume_hashes", "omgx_chomp_aux_doubles", "omgx_chomp_optimize",
            "omgx_learner_state_doubles", "omgx_goal_update", "omgx_goal_update_optimize", "omgx_point_cloud_sdf", "omgx_last_error", "omgx_abi_version", "omgx_device_arch", "omgx_device_cu_count", "omgx_download_sync",
            "omgx_timing_enable", "omgx_timing_collect", "omgx_plan_persistent_workspace_bytes", "omgx_plan_persistent", "omgx_plan_persistent_status", "omgx_goal_ik",
-           "omgx_select_goals_workspace_bytes", "omgx_select_goals", "omgx_mesh_sdf_tile", "omgx_mesh_sdf"]
+           "omgx_select_goals_workspace_bytes", "omgx_select_goals", "omgx_mesh_sdf_tile", "omgx_mesh_sdf",
+           "omgx_mesh_raycast_chunks", "omgx_mesh_raycast_workspace_bytes", "omgx_mesh_raycast", "omgx_grasp_poses"]
 
 
 class OmgHipError(RuntimeError):
@@ -64,6 +65,15 @@ class Mesh(C.Structure):
 
 
 MESH_SDF_NODES_PER_WORKGROUP = 256  # OMGX_MESH_SDF_NODES_PER_WORKGROUP
+
+
+class RayWork(C.Structure):
+    """Mirror of `omgx_ray_work` (include/omg_hip.h): one workgroup of omgx_mesh_raycast / omgx_grasp_poses (24 bytes)."""
+    _fields_ = [(n, C.c_int32) for n in ("mesh", "ray_begin", "ray_count", "face_begin", "face_count", "chunk")]
+
+
+RAYCAST_RAYS_PER_WORKGROUP = 256  # OMGX_RAYCAST_RAYS_PER_WORKGROUP
+RAYCAST_MAX_CHUNKS = 64           # OMGX_RAYCAST_MAX_CHUNKS
 
 ALG = {"FTL": 0, "FTC": 1, "Exp": 2, "MD": 3, "Proj": 4}
 
@@ -168,6 +178,15 @@ def lib() -> C.CDLL:
         l.omgx_mesh_sdf_tile.restype = i32
         l.omgx_mesh_sdf.argtypes = [vp, vp, vp, vp, i32, vp, vp]
         l.omgx_mesh_sdf.restype = C.c_int
+        l.omgx_mesh_raycast_chunks.argtypes = [i32, i32, i32]
+        l.omgx_mesh_raycast_chunks.restype = i32
+        l.omgx_mesh_raycast_workspace_bytes.argtypes = [i32, i32]
+        l.omgx_mesh_raycast_workspace_bytes.restype = i64
+        l.omgx_mesh_raycast.argtypes = [vp, vp, vp, vp, i32, vp, vp, vp, vp, i32, i32, vp, vp, i32, f64, f64, vp, vp, vp, vp]
+        l.omgx_mesh_raycast.restype = C.c_int
+        l.omgx_grasp_poses.argtypes = ([vp, vp, i32, vp, vp, vp, vp, i32, i32] + [vp] * 5 + [i32, vp, vp, i32, vp, i32, vp, i64] +
+                                       [f64] * 5 + [vp, vp, vp])
+        l.omgx_grasp_poses.restype = C.c_int
         for name in ("omgx_sdf_loss_forward", "omgx_fk_sdf", "omgx_forward_kinematics", "omgx_pose_table", "omgx_goalset_cost", "omgx_chomp_optimize",
                      "omgx_abi_version", "omgx_device_arch", "omgx_timing_enable", "omgx_timing_collect"):
             getattr(l, name).restype = C.c_int

@@ -1,0 +1,258 @@
+// omg_grasp.hip — antipodal grasp sets from triangle meshes (include/omg_hip.h section 13).
+//
+// k_mesh_raycast: one thread per ray, one workgroup per (256 rays x one chunk of faces) of ONE mesh of a ragged batch, as a
+// host-built work list says (omgx_ray_work).  The chunk's faces stream through LDS in tiles of GRASP_TILE faces (9 doubles each),
+// every lane reading the same face at a time (LDS broadcast), like k_mesh_sdf.  With more than one chunk the partial (t, face)
+// pairs go to a workspace [chunks][N] and k_mesh_raycast_reduce folds them in chunk order with the same strict <, so the result
+// does not depend on the split.  k_grasp_poses: one thread per (ray, angle); blockIdx.y is the angle, blockIdx.x a ray group of
+// the same work list.  All arithmetic is float64 with contraction off (omg_grasp_body.h), one operation per operation of the
+// specification grasps.mesh_raycast / grasps.grasp_poses (omg-planner_amd/grasps.py).  Plain loads and stores only.
+#include <cmath>
+#include <cstdint>
+
+#include "omg_host.h"
+#include "omg_grasp_body.h"
+
+#pragma clang fp contract(off)
+
+#define GRASP_TILE OMGX_MESH_FACE_TILE  // the tile of k_mesh_sdf: omgx_mesh_sdf_tile()
+#define GRASP_BLOCK OMGX_RAYCAST_RAYS_PER_WORKGROUP
+static_assert(GRASP_TILE == GRASP_BLOCK, "the tile load below moves one face per thread");
+
+namespace {
+
+__global__ __launch_bounds__(GRASP_BLOCK) void k_mesh_raycast(const double* __restrict__ verts, const int32_t* __restrict__ faces,
+                                                              const omgx_mesh* __restrict__ meshes,
+                                                              const omgx_ray_work* __restrict__ work,
+                                                              const double* __restrict__ origins, const double* __restrict__ dirs,
+                                                              double t_min, double neg_tol, double one_tol, int64_t row_stride,
+                                                              double* __restrict__ t_out, int32_t* __restrict__ face_out) {
+    __shared__ double tile[GRASP_TILE * 9];
+    const omgx_ray_work w = work[blockIdx.x];  // uniform: scalar loads
+    const omgx_mesh* __restrict__ ms = meshes + w.mesh;
+    const double* __restrict__ mv = verts + (int64_t)ms->vert_begin * 3;
+    const int32_t* __restrict__ mf = faces + (int64_t)ms->face_begin * 3;
+    const int nv = ms->vert_count;
+    // idle lanes of the last group redo its last ray and store nothing
+    const int64_t ray = (int64_t)w.ray_begin + min((int)threadIdx.x, w.ray_count - 1);
+    const double ox = origins[ray * 3], oy = origins[ray * 3 + 1], oz = origins[ray * 3 + 2];
+    const double dx = dirs[ray * 3], dy = dirs[ray * 3 + 1], dz = dirs[ray * 3 + 2];
+
+    double best = __builtin_inf();
+    int32_t face = -1;
+    const int f_end = w.face_begin + w.face_count;
+    for (int t0 = w.face_begin; t0 < f_end; t0 += GRASP_TILE) {
+        const int cnt = min(GRASP_TILE, f_end - t0);
+        __syncthreads();
+        if ((int)threadIdx.x < cnt) {
+            const int32_t* f = mf + (int64_t)(t0 + (int)threadIdx.x) * 3;
+            for (int c = 0; c < 3; ++c) {
+                // the wrappers reject indices outside the mesh; clamped here so that no index can read outside the pool
+                const int v = min(max(f[c], 0), nv - 1);
+                for (int a = 0; a < 3; ++a) tile[threadIdx.x * 9 + c * 3 + a] = mv[(int64_t)v * 3 + a];
+            }
+        }
+        __syncthreads();
+        for (int q = 0; q < cnt; ++q) {
+            mesh_raycast_pair(ox, oy, oz, dx, dy, dz, tile + q * 9, t0 + q, t_min, neg_tol, one_tol, best, face);
+        }
+    }
+    if ((int)threadIdx.x < w.ray_count) {
+        const int64_t at = (int64_t)w.chunk * row_stride + ray;
+        t_out[at] = best;
+        face_out[at] = face;
+    }
+}
+
+// the chunks of a ray in chunk order: ascending face ranges, so the strict < keeps the lowest face index of a tie
+__global__ __launch_bounds__(GRASP_BLOCK) void k_mesh_raycast_reduce(const omgx_ray_work* __restrict__ work, int chunks,
+                                                                     int64_t row_stride, const double* __restrict__ ws_t,
+                                                                     const int32_t* __restrict__ ws_face,
+                                                                     double* __restrict__ t_out, int32_t* __restrict__ face_out) {
+    const omgx_ray_work w = work[(int64_t)blockIdx.x * chunks];
+    if ((int)threadIdx.x >= w.ray_count) return;
+    const int64_t ray = (int64_t)w.ray_begin + threadIdx.x;
+    double best = __builtin_inf();
+    int32_t face = -1;
+    for (int c = 0; c < chunks; ++c) {
+        const double t = ws_t[(int64_t)c * row_stride + ray];
+        const int32_t f = ws_face[(int64_t)c * row_stride + ray];
+        const bool hit = t < best;
+        best = hit ? t : best;
+        face = hit ? f : face;
+    }
+    t_out[ray] = best;
+    face_out[ray] = face;
+}
+
+__global__ __launch_bounds__(GRASP_BLOCK) void k_grasp_poses(const omgx_mesh* __restrict__ meshes, const omgx_ray_work* __restrict__ work,
+                                                             int chunks, const double* __restrict__ p1, const double* __restrict__ n1,
+                                                             const double* __restrict__ dirs, const double* __restrict__ t,
+                                                             const int32_t* __restrict__ face2, const double* __restrict__ normals,
+                                                             const double* __restrict__ cs, int num_angles,
+                                                             const double* __restrict__ probe, int num_probe,
+                                                             const float* __restrict__ pool, double max_width, double min_width,
+                                                             double cos_cone, double pad_depth, float clearance,
+                                                             double* __restrict__ poses, uint8_t* __restrict__ valid) {
+    const omgx_ray_work w = work[(int64_t)blockIdx.x * chunks];
+    if ((int)threadIdx.x >= w.ray_count) return;  // (no barrier below)
+    const omgx_mesh* __restrict__ ms = meshes + w.mesh;
+    const int a = blockIdx.y;
+    const int64_t ray = (int64_t)w.ray_begin + threadIdx.x;
+    const int32_t f2 = face2[ray];
+    const int64_t fn = (int64_t)ms->face_begin + min(max(f2, 0), ms->face_count - 1);  // a miss reads face 0's normal and fails f2 >= 0
+    grasp_frame F;
+    bool ok = grasp_pose_pair(p1[ray * 3], p1[ray * 3 + 1], p1[ray * 3 + 2], n1[ray * 3], n1[ray * 3 + 1], n1[ray * 3 + 2],
+                              dirs[ray * 3], dirs[ray * 3 + 1], dirs[ray * 3 + 2], t[ray], f2, normals[fn * 3], normals[fn * 3 + 1],
+                              normals[fn * 3 + 2], cs[a * 2], cs[a * 2 + 1], max_width, min_width, cos_cone, pad_depth, F);
+    double* __restrict__ P = poses + (ray * num_angles + a) * 16;
+    if (!ok) {  // not antipodal: a pose of zeros
+        for (int i = 0; i < 16; ++i) P[i] = 0.0;
+        valid[ray * num_angles + a] = 0;
+        return;
+    }
+    const float* __restrict__ vol = pool + ms->out_offset;
+    for (int q = 0; q < num_probe && ok; ++q) {
+        ok = !grasp_probe_collides(F, probe[q * 3], probe[q * 3 + 1], probe[q * 3 + 2], ms->origin, ms->delta, ms->sample_offset,
+                                   ms->dims, vol, clearance);
+    }
+    P[0] = F.xx, P[1] = F.yx, P[2] = F.zx, P[3] = F.ox;
+    P[4] = F.xy, P[5] = F.yy, P[6] = F.zy, P[7] = F.oy;
+    P[8] = F.xz, P[9] = F.yz, P[10] = F.zz, P[11] = F.oz;
+    P[12] = 0.0, P[13] = 0.0, P[14] = 0.0, P[15] = 1.0;
+    valid[ray * num_angles + a] = ok ? 1 : 0;
+}
+
+// The work list against the ray ranges of the meshes (host copies): for every mesh in order, its rays in groups of GRASP_BLOCK,
+// every group `chunks` records in chunk order whose face ranges tile [0, face_count); the ray ranges of two meshes must not
+// overlap.  -> number of ray groups, or < 0.
+int64_t check_work(const omgx_mesh* h_meshes, int32_t M, const int32_t* h_ray_begin, const int32_t* h_ray_count,
+                   const omgx_ray_work* h_work, int32_t num_work, int32_t chunks, int32_t num_rays) {
+    int64_t i = 0, groups = 0;
+    for (int32_t m = 0; m < M; ++m) {
+        const int64_t rb = h_ray_begin[m], rc = h_ray_count[m];
+        if (rb < 0 || rc < 0 || rb + rc > (int64_t)num_rays) return -1;
+        for (int32_t k = 0; k < m && rc > 0; ++k)  // two meshes that share a row would race on the outputs
+            if (h_ray_count[k] > 0 && rb < (int64_t)h_ray_begin[k] + h_ray_count[k] && (int64_t)h_ray_begin[k] < rb + rc) return -1;
+        const int32_t nf = h_meshes[m].face_count;
+        for (int64_t r0 = 0; r0 < rc; r0 += GRASP_BLOCK, ++groups) {
+            const int64_t cnt = rc - r0 < GRASP_BLOCK ? rc - r0 : GRASP_BLOCK;
+            int64_t next = 0;
+            for (int32_t c = 0; c < chunks; ++c) {
+                if (i >= num_work) return -1;
+                const omgx_ray_work& w = h_work[i++];
+                if (w.mesh != m || w.ray_begin != rb + r0 || w.ray_count != cnt || w.chunk != c) return -1;
+                if (w.face_begin != next || w.face_count < 0 || (int64_t)w.face_begin + w.face_count > nf) return -1;
+                next += w.face_count;
+            }
+            if (next != nf) return -1;
+        }
+    }
+    return i == num_work ? groups : -1;
+}
+
+bool bad_mesh_geometry(const omgx_mesh& h) {
+    return h.vert_begin < 0 || h.face_begin < 0 || h.vert_count < 1 || h.face_count < 1;
+}
+
+}  // namespace
+
+extern "C" int32_t omgx_mesh_raycast_chunks(int32_t ray_workgroups, int32_t max_faces, int32_t chunks) {
+    if (ray_workgroups < 0 || max_faces < 1 || chunks < 0 || chunks > OMGX_RAYCAST_MAX_CHUNKS) return OMGX_ERR_INVALID;
+    if (chunks > 0) return chunks;
+    if (ray_workgroups == 0) return 1;
+    const int32_t cu = omgx_device_cu_count();
+    if (cu < 1) return OMGX_ERR_LAUNCH;
+    // four workgroups per compute unit, no chunk below one tile
+    const int64_t want = ((int64_t)4 * cu + ray_workgroups - 1) / ray_workgroups;
+    const int64_t tiles = ((int64_t)max_faces + GRASP_TILE - 1) / GRASP_TILE;
+    int64_t c = want < tiles ? want : tiles;
+    if (c > OMGX_RAYCAST_MAX_CHUNKS) c = OMGX_RAYCAST_MAX_CHUNKS;
+    return (int32_t)(c < 1 ? 1 : c);
+}
+
+extern "C" int64_t omgx_mesh_raycast_workspace_bytes(int32_t num_rays, int32_t chunks) {
+    if (num_rays < 0 || chunks < 0 || chunks > OMGX_RAYCAST_MAX_CHUNKS) return OMGX_ERR_INVALID;
+    if (chunks <= 1) return 0;  // one chunk writes the results themselves
+    return (int64_t)chunks * num_rays * (int64_t)(sizeof(double) + sizeof(int32_t));
+}
+
+extern "C" int omgx_mesh_raycast(const double* verts, const int32_t* faces, const omgx_mesh* meshes, const omgx_mesh* h_meshes,
+                                 int32_t num_meshes, const int32_t* h_ray_begin, const int32_t* h_ray_count,
+                                 const omgx_ray_work* work, const omgx_ray_work* h_work, int32_t num_work, int32_t chunks,
+                                 const double* origins, const double* dirs, int32_t num_rays, double t_min, double tol,
+                                 double* t_out, int32_t* face_out, void* workspace, void* stream) {
+    if (!verts || !faces || !meshes || !h_meshes || !h_ray_begin || !h_ray_count || num_meshes < 1) return OMGX_ERR_INVALID;
+    if (num_work < 0 || num_rays < 0 || chunks < 0 || chunks > OMGX_RAYCAST_MAX_CHUNKS) return OMGX_ERR_INVALID;
+    if (!(t_min >= 0.0) || !(tol >= 0.0) || !std::isfinite(t_min) || !std::isfinite(tol)) return OMGX_ERR_INVALID;
+    if (num_work > 0 && (!work || !h_work || !origins || !dirs || !t_out || !face_out)) return OMGX_ERR_INVALID;
+    int32_t max_faces = 1;
+    for (int32_t m = 0; m < num_meshes; ++m) {
+        if (bad_mesh_geometry(h_meshes[m])) return OMGX_ERR_INVALID;
+        if (h_meshes[m].face_count > max_faces) max_faces = h_meshes[m].face_count;
+    }
+    if (chunks == 0) {  // the automatic choice, which the list must have been built for
+        int64_t groups = 0;
+        for (int32_t m = 0; m < num_meshes; ++m)
+            if (h_ray_count[m] > 0) groups += ((int64_t)h_ray_count[m] + GRASP_BLOCK - 1) / GRASP_BLOCK;
+        if (groups > 0x7fffffffll) return OMGX_ERR_UNSUPPORTED;
+        chunks = omgx_mesh_raycast_chunks((int32_t)groups, max_faces, 0);
+        if (chunks < 1) return chunks;
+    }
+    const int64_t groups = check_work(h_meshes, num_meshes, h_ray_begin, h_ray_count, h_work, num_work, chunks, num_rays);
+    if (groups < 0) return OMGX_ERR_INVALID;
+    if (groups == 0) return OMGX_OK;  // no mesh has a ray
+    if (chunks > 1 && !workspace) return OMGX_ERR_INVALID;
+    const double neg_tol = -tol, one_tol = 1.0 + tol;
+    if (chunks == 1) {
+        hipLaunchKernelGGL(k_mesh_raycast, dim3((unsigned)num_work), dim3(GRASP_BLOCK), 0, (hipStream_t)stream, verts, faces, meshes, work,
+                           origins, dirs, t_min, neg_tol, one_tol, (int64_t)num_rays, t_out, face_out);
+        OMGX_CHECK_LAUNCH("k_mesh_raycast");
+        return OMGX_OK;
+    }
+    double* ws_t = (double*)workspace;
+    int32_t* ws_face = (int32_t*)(ws_t + (int64_t)chunks * num_rays);
+    hipLaunchKernelGGL(k_mesh_raycast, dim3((unsigned)num_work), dim3(GRASP_BLOCK), 0, (hipStream_t)stream, verts, faces, meshes, work,
+                       origins, dirs, t_min, neg_tol, one_tol, (int64_t)num_rays, ws_t, ws_face);
+    OMGX_CHECK_LAUNCH("k_mesh_raycast");
+    hipLaunchKernelGGL(k_mesh_raycast_reduce, dim3((unsigned)groups), dim3(GRASP_BLOCK), 0, (hipStream_t)stream, work, (int)chunks,
+                       (int64_t)num_rays, ws_t, ws_face, t_out, face_out);
+    OMGX_CHECK_LAUNCH("k_mesh_raycast_reduce");
+    return OMGX_OK;
+}
+
+extern "C" int omgx_grasp_poses(const omgx_mesh* meshes, const omgx_mesh* h_meshes, int32_t num_meshes, const int32_t* h_ray_begin,
+                                const int32_t* h_ray_count, const omgx_ray_work* work, const omgx_ray_work* h_work, int32_t num_work,
+                                int32_t chunks, const double* p1, const double* n1, const double* dirs, const double* t,
+                                const int32_t* face2, int32_t num_rays, const double* normals, const double* cs, int32_t num_angles,
+                                const double* probe, int32_t num_probe, const float* pool, int64_t pool_elems, double max_width,
+                                double min_width, double cos_cone, double pad_depth, double clearance, double* poses, uint8_t* valid,
+                                void* stream) {
+    if (!meshes || !h_meshes || !h_ray_begin || !h_ray_count || !pool || num_meshes < 1) return OMGX_ERR_INVALID;
+    if (num_work < 0 || num_rays < 0 || chunks < 1 || chunks > OMGX_RAYCAST_MAX_CHUNKS || num_probe < 0 || pool_elems < 0) return OMGX_ERR_INVALID;
+    if (num_angles < 1 || num_angles > 65535) return OMGX_ERR_INVALID;
+    if (!cs || !normals || (num_probe > 0 && !probe)) return OMGX_ERR_INVALID;
+    if (std::isnan(max_width) || std::isnan(min_width) || std::isnan(cos_cone) || !std::isfinite(pad_depth) || !std::isfinite(clearance))
+        return OMGX_ERR_INVALID;
+    if (num_work > 0 && (!work || !h_work || !p1 || !n1 || !dirs || !t || !face2 || !poses || !valid)) return OMGX_ERR_INVALID;
+    for (int32_t m = 0; m < num_meshes; ++m) {
+        const omgx_mesh& h = h_meshes[m];
+        if (h.face_begin < 0 || h.face_count < 1 || h.out_offset < 0) return OMGX_ERR_INVALID;
+        if (!(h.delta > 0.0) || !std::isfinite(h.delta)) return OMGX_ERR_INVALID;
+        if (h.dims[0] < 1 || h.dims[1] < 1 || h.dims[2] < 1) return OMGX_ERR_INVALID;
+        if (!(h.sample_offset == 0.0 || h.sample_offset == 0.5)) return OMGX_ERR_INVALID;
+        for (int a = 0; a < 3; ++a)
+            if (!std::isfinite(h.origin[a])) return OMGX_ERR_INVALID;
+        const int64_t total = (int64_t)h.dims[0] * h.dims[1] * h.dims[2];
+        if (total > (int64_t)1 << 31) return OMGX_ERR_UNSUPPORTED;
+        if (h.out_offset + total > pool_elems) return OMGX_ERR_INVALID;  // the volume must lie in the pool
+    }
+    const int64_t groups = check_work(h_meshes, num_meshes, h_ray_begin, h_ray_count, h_work, num_work, chunks, num_rays);
+    if (groups < 0) return OMGX_ERR_INVALID;
+    if (groups == 0) return OMGX_OK;
+    hipLaunchKernelGGL(k_grasp_poses, dim3((unsigned)groups, (unsigned)num_angles), dim3(GRASP_BLOCK), 0, (hipStream_t)stream, meshes, work,
+                       (int)chunks, p1, n1, dirs, t, face2, normals, cs, (int)num_angles, probe, (int)num_probe, pool, max_width, min_width,
+                       cos_cone, pad_depth, (float)clearance, poses, valid);
+    OMGX_CHECK_LAUNCH("k_grasp_poses");
+    return OMGX_OK;
+}

@@ -14,7 +14,7 @@
 
 #pragma clang fp contract(off)
 
-#define MSDF_TILE 256
+#define MSDF_TILE OMGX_MESH_FACE_TILE
 #define MSDF_BLOCK OMGX_MESH_SDF_NODES_PER_WORKGROUP
 static_assert(MSDF_TILE == MSDF_BLOCK, "the tile load below moves one face per thread");
 

@@ -1128,3 +1128,173 @@ def mesh_sdf(verts, faces, delta, padding=4, sample="centre", origin=None, dims=
         import logging
         logging.getLogger(__name__).debug("mesh_sdf: dropped %d faces of zero area", dropped[0])
     return grids[0], org[0], deltas[0]
+
+
+class RayBatch:
+    """Host side of a ragged ray batch over M meshes, shared by mesh_raycast_batch and grasp_poses: the meshes cleaned and pooled
+    (vertex pool [V,3] float64, face pool [F,3] int32, omgx_mesh records), every mesh's rows of the ray arrays, and the work list
+    (omgx_ray_work: one record per workgroup) on the host and on the device.
+
+    meshes: a list of (verts [V,3], faces [F,3]) on the host; ray_counts: rays per mesh (0 is legal); ray_begins: the first row of
+    each mesh's rays (default: back to back); num_rays: rows of the ray arrays (default: the end of the last range); chunks:
+    workgroups that share the faces of one ray group (0: omgx_mesh_raycast_chunks decides from the compute units); layout: per
+    mesh (origin [3], delta, sample, dims, element offset in the pool) of its volume, needed by grasp_poses only."""
+
+    def __init__(self, meshes, ray_counts, ray_begins=None, num_rays=None, chunks: int = 0, device="cuda:0", layout=None):
+        from . import scenes as _sc
+        M = len(meshes)
+        if M < 1:
+            raise _lib.OmgHipError("a ray batch needs at least one mesh")
+        if len(ray_counts) != M or (ray_begins is not None and len(ray_begins) != M) or (layout is not None and len(layout) != M):
+            raise _lib.OmgHipError(f"ray_counts, ray_begins and layout must have one entry per mesh ({M})")
+        counts = [int(c) for c in ray_counts]
+        if min(counts) < 0:
+            raise _lib.OmgHipError("a ray count is negative")
+        begins = [int(b) for b in ray_begins] if ray_begins is not None else [int(x) for x in np.concatenate([[0], np.cumsum(counts)[:-1]])]
+        spans = sorted((b, c) for b, c in zip(begins, counts) if c > 0)
+        end = max([b + c for b, c in spans], default=0)
+        self.num_rays = end if num_rays is None else int(num_rays)
+        if any(b < 0 for b in begins) or end > self.num_rays or any(spans[i][0] + spans[i][1] > spans[i + 1][0] for i in range(len(spans) - 1)):
+            raise _lib.OmgHipError(f"the ray ranges (begin, count) {spans} overlap or leave the {self.num_rays} rows")
+        if not 0 <= int(chunks) <= _lib.RAYCAST_MAX_CHUNKS:
+            raise _lib.OmgHipError(f"chunks must lie in [0, {_lib.RAYCAST_MAX_CHUNKS}], got {chunks}")
+        self.device = torch.device(device)
+        self.num_meshes, self.ray_begin, self.ray_count, self.has_layout = M, begins, counts, layout is not None
+        self.rec = (_lib.Mesh * M)()
+        vs, fs = [], []
+        v0 = f0 = 0
+        for m, (verts, faces) in enumerate(meshes):
+            try:
+                verts, faces, dropped = _sc.clean_mesh(verts, faces)
+            except ValueError as e:
+                raise _lib.OmgHipError(f"mesh {m}: {e}") from None
+            if dropped:  # dropping them here would renumber the faces the results name
+                raise _lib.OmgHipError(f"mesh {m}: {dropped} faces of zero area (scenes.clean_mesh removes them; face indices stay as given here)")
+            r = self.rec[m]
+            o, delta, sample, dims, off = ((0.0, 0.0, 0.0), 1.0, "centre", (1, 1, 1), 0) if layout is None else layout[m]
+            if sample not in _sc.MESH_SAMPLE_OFFSET:
+                raise _lib.OmgHipError(f"sample must be 'centre' or 'node', got {sample!r}")
+            if not (float(delta) > 0 and np.isfinite(float(delta))) or min(int(x) for x in dims) < 1 or int(off) < 0:
+                raise _lib.OmgHipError(f"mesh {m}: delta must be positive and finite, dims >= 1, the offset >= 0")
+            r.origin[:], r.delta, r.sample_offset, r.dims[:] = [float(x) for x in o], float(delta), _sc.MESH_SAMPLE_OFFSET[sample], [int(x) for x in dims]
+            r.out_offset, r.first_workgroup = int(off), 0
+            r.vert_begin, r.vert_count, r.face_begin, r.face_count = v0, len(verts), f0, len(faces)
+            v0, f0 = v0 + len(verts), f0 + len(faces)
+            vs.append(verts), fs.append(faces)
+        self.num_faces = f0
+        groups = sum(-(-c // _lib.RAYCAST_RAYS_PER_WORKGROUP) for c in counts)
+        max_faces = max(len(f) for f in fs)
+        if int(chunks) == 0 and groups > 0:
+            with torch.cuda.device(self.device):
+                self.chunks = int(_lib.lib().omgx_mesh_raycast_chunks(groups, max_faces, 0))
+            check(min(self.chunks, 0), "omgx_mesh_raycast_chunks")
+        else:
+            self.chunks = max(int(chunks), 1)
+        tile = int(_lib.lib().omgx_mesh_sdf_tile())
+        work = []
+        for m in range(M):
+            nf = len(fs[m])
+            tiles = -(-nf // tile)
+            cut = [min(nf, tile * ((c * tiles) // self.chunks)) for c in range(self.chunks)] + [nf]
+            for r0 in range(0, counts[m], _lib.RAYCAST_RAYS_PER_WORKGROUP):
+                for c in range(self.chunks):
+                    work.append((m, begins[m] + r0, min(_lib.RAYCAST_RAYS_PER_WORKGROUP, counts[m] - r0), cut[c], cut[c + 1] - cut[c], c))
+        self.num_work = len(work)
+        self.h_work = np.ascontiguousarray(np.array(work, np.int32).reshape(-1, 6))
+        self.h_ray_begin, self.h_ray_count = np.array(begins, np.int32), np.array(counts, np.int32)
+        dev = self.device
+        self.verts, self.faces = torch.from_numpy(np.concatenate(vs)).to(dev), torch.from_numpy(np.concatenate(fs)).to(dev)
+        self.d_rec = torch.from_numpy(np.frombuffer(self.rec, np.uint8).copy()).to(dev)
+        self.d_work = torch.from_numpy(self.h_work if self.num_work else np.zeros((1, 6), np.int32)).to(dev)
+
+    def _args(self):
+        """(meshes, h_meshes, M, h_ray_begin, h_ray_count, work, h_work, num_work, chunks) as the entry points take them."""
+        vp = C.c_void_p
+        return (_ptr(self.d_rec), C.cast(self.rec, vp), self.num_meshes, vp(self.h_ray_begin.ctypes.data), vp(self.h_ray_count.ctypes.data),
+                _ptr(self.d_work), vp(self.h_work.ctypes.data), self.num_work, self.chunks)
+
+    def _rays(self, t, name, cols=3, dtype=torch.float64):
+        _need(t, dtype, name)
+        want = (self.num_rays, cols) if cols else (self.num_rays,)
+        if t.device != self.device or tuple(t.shape) != want:
+            raise _lib.OmgHipError(f"{name} must be {want} on {self.device}, got {tuple(t.shape)} on {t.device}")
+        return t
+
+
+def mesh_raycast_batch(batch: RayBatch, origins: torch.Tensor, dirs: torch.Tensor, t_min: float = 1e-6, tol: float = 1e-9, out=None):
+    """The nearest hit of every ray of a ragged batch with its own mesh, in ONE launch (omgx_mesh_raycast; grasps.mesh_raycast is
+    the specification: the same float64 t bit for bit, the same face).  origins, dirs: [num_rays,3] float64 device tensors, mesh
+    m's rays in rows [ray_begin[m], ray_begin[m] + ray_count[m]).  out: None or (t [num_rays] float64, face [num_rays] int32)
+    written IN PLACE on those rows only.  -> (t, face); face is local to the mesh, (+inf, -1) is a miss; rows outside every
+    range are left as they were (zeros in a fresh output)."""
+    if not (float(t_min) >= 0 and np.isfinite(float(t_min)) and float(tol) >= 0 and np.isfinite(float(tol))):
+        raise _lib.OmgHipError("t_min and tol must be finite and not negative")
+    batch._rays(origins, "origins"), batch._rays(dirs, "dirs")
+    if out is None:
+        out = (torch.zeros(batch.num_rays, dtype=torch.float64, device=batch.device), torch.zeros(batch.num_rays, dtype=torch.int32, device=batch.device))
+    t, face = batch._rays(out[0], "out[0]", 0), batch._rays(out[1], "out[1]", 0, torch.int32)
+    l = _lib.lib()
+    ws = _workspace(int(l.omgx_mesh_raycast_workspace_bytes(batch.num_rays, batch.chunks)), batch.device) if batch.chunks > 1 else None
+    a = batch._args()
+    with torch.cuda.device(batch.device):
+        check(l.omgx_mesh_raycast(_ptr(batch.verts), _ptr(batch.faces), *a, _ptr(origins), _ptr(dirs), batch.num_rays, float(t_min), float(tol),
+                                  _ptr(t), _ptr(face), _ptr(ws), _stream()), "omgx_mesh_raycast")
+    return t, face
+
+
+def mesh_raycast(verts, faces, origins, dirs, t_min: float = 1e-6, tol: float = 1e-9, chunks: int = 0, device="cuda:0"):
+    """Rays against one mesh on the device -> (t [N] float64, face [N] int32) device tensors; grasps.mesh_raycast with the same
+    arguments is the specification.  origins, dirs: [N,3] on the host or float64 device tensors."""
+    dev = torch.device(device)
+    up = lambda x: x if isinstance(x, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(x, np.float64)).to(dev)
+    origins, dirs = up(origins), up(dirs)
+    if origins.dim() != 2 or origins.shape[1:] != (3,) or origins.shape != dirs.shape:
+        raise _lib.OmgHipError(f"origins and dirs must both be [N,3], got {tuple(origins.shape)} and {tuple(dirs.shape)}")
+    return mesh_raycast_batch(RayBatch([(verts, faces)], [origins.shape[0]], chunks=chunks, device=dev), origins, dirs, t_min, tol)
+
+
+def grasp_poses(batch: RayBatch, p1, n1, dirs, t, face2, normals, cs, probe, pool, max_width=0.08, min_width=0.005,
+                cos_cone=float(np.cos(np.deg2rad(15.0))), pad_depth=0.088, clearance=0.0, out=None):
+    """Hand poses of the contact pairs of a ragged batch in ONE launch (omgx_grasp_poses; grasps.grasp_poses is the specification:
+    the same poses bit for bit, the same flags) -> (poses [num_rays,A,4,4] float64, valid [num_rays,A] uint8).
+    batch: a RayBatch built with `layout` (where each mesh's volume lies in `pool`); p1, n1, dirs [num_rays,3], t [num_rays]
+    float64, face2 [num_rays] int32: device tensors (mesh_raycast_batch's inputs and outputs); normals [F,3] float64 device tensor:
+    unit face normals in the batch's face order; cs [A,2] (grasps.approach_angles) and probe [Q,3] on the host or the device;
+    pool: contiguous float32 device tensor (the SDF pool or mesh_sdf_batch's buffer).  Rows outside every ray range are left as
+    they were."""
+    if not batch.has_layout:
+        raise _lib.OmgHipError("grasp_poses needs a RayBatch with the layout of the volumes")
+    dev = batch.device
+    up = lambda x: x if isinstance(x, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(x, np.float64)).to(dev)
+    cs, probe = up(cs), up(probe)
+    for x, name in ((cs, "cs"), (probe, "probe"), (normals, "normals")):
+        _need(x, torch.float64, name)
+    if cs.dim() != 2 or cs.shape[1] != 2 or not 1 <= cs.shape[0] <= 65535:
+        raise _lib.OmgHipError(f"cs must be [A,2] with 1 <= A <= 65535, got {tuple(cs.shape)}")
+    if probe.dim() != 2 or probe.shape[1] != 3:
+        raise _lib.OmgHipError(f"probe must be [Q,3], got {tuple(probe.shape)}")
+    if tuple(normals.shape) != (batch.num_faces, 3):
+        raise _lib.OmgHipError(f"normals must be ({batch.num_faces}, 3): one per face of the batch, got {tuple(normals.shape)}")
+    _need(pool, torch.float32, "pool")
+    for m in range(batch.num_meshes):
+        r = batch.rec[m]
+        if int(r.out_offset) + int(r.dims[0]) * int(r.dims[1]) * int(r.dims[2]) > pool.numel():
+            raise _lib.OmgHipError(f"mesh {m}: its volume leaves the pool ({pool.numel()} elements)")
+    if any(np.isnan(float(x)) for x in (max_width, min_width, cos_cone)) or not np.isfinite(float(pad_depth)) or not np.isfinite(float(clearance)):
+        raise _lib.OmgHipError("max_width, min_width, cos_cone must not be NaN; pad_depth and clearance must be finite")
+    batch._rays(p1, "p1"), batch._rays(n1, "n1"), batch._rays(dirs, "dirs"), batch._rays(t, "t", 0), batch._rays(face2, "face2", 0, torch.int32)
+    A, N = int(cs.shape[0]), batch.num_rays
+    if out is None:
+        out = (torch.zeros((N, A, 4, 4), dtype=torch.float64, device=dev), torch.zeros((N, A), dtype=torch.uint8, device=dev))
+    poses, valid = out
+    _need(poses, torch.float64, "out[0]"), _need(valid, torch.uint8, "out[1]")
+    if tuple(poses.shape) != (N, A, 4, 4) or tuple(valid.shape) != (N, A) or poses.device != dev or valid.device != dev:
+        raise _lib.OmgHipError(f"out must be ({N}, {A}, 4, 4) float64 and ({N}, {A}) uint8 on {dev}")
+    with torch.cuda.device(dev):
+        check(_lib.lib().omgx_grasp_poses(*batch._args(), _ptr(p1), _ptr(n1), _ptr(dirs), _ptr(t), _ptr(face2), N, _ptr(normals), _ptr(cs), A,
+                                          _ptr(probe), int(probe.shape[0]), _ptr(pool), pool.numel(), float(max_width), float(min_width),
+                                          float(cos_cone), float(pad_depth), float(clearance), _ptr(poses), _ptr(valid), _stream()),
+              "omgx_grasp_poses")
+        for x in (cs, probe):
+            x.record_stream(torch.cuda.current_stream(dev))
+    return poses, valid

@@ -82,3 +82,22 @@ def plan_grasps(model, scenes, grasp_poses, starts, cfg, ol_alg=None, rng=np.ran
         info.index_copy_(0, sel, out)
         goal_idx.index_copy_(0, sel, eng.goal_idx)
     return GraspPlans(traj, info, goal_idx, goals, grasps, reach, pot, k, nfree, ncand, planned, eng)
+
+
+def plan_meshes(model, scenes, meshes, starts, cfg, n_rays: int = 512, n_angles: int = 8, ol_alg=None, rng=np.random,
+                grasp_rng=None, max_grasps=None, device="cuda:0", layout_scenes: "int | None" = None, **grasp_kwargs):
+    """Plans for S grasping scenes from the triangle meshes of their targets: grasps.sample_grasp_sets on the device (one ray-cast
+    launch and one pose launch for all scenes, the target's own volume as the gripper check), then plan_grasps unchanged.
+
+    meshes: S (verts, faces) in the frame of the target object's volume (scenes[s].objects[target_idx].sdf, voxel centres).
+    grasp_rng: the stream the sampler consumes (default np.random.RandomState(0)), or a list of S; rng: the stream plan_grasps'
+    goal draw consumes.  grasp_kwargs: sample_grasp_sets' parameters (cone, max_width, clearance, probe, chunks, ...).  The
+    targets' volumes are uploaded for the sampler and again by plan_grasps for its scene table (it builds its own).
+    -> (GraspPlans, grasp poses: S arrays [G_s,4,4] in the targets' frames)."""
+    from . import grasps as _gr
+    if len(meshes) != len(scenes):
+        raise ValueError("meshes must hold one (verts, faces) per scene")
+    grids = [sc_.objects[sc_.target_idx].sdf for sc_ in scenes]
+    sets = _gr.sample_grasp_sets(meshes, grids, n_rays, n_angles, np.random.RandomState(0) if grasp_rng is None else grasp_rng,
+                                 max_grasps=max_grasps, device=device, **grasp_kwargs)
+    return plan_grasps(model, scenes, sets, starts, cfg, ol_alg=ol_alg, rng=rng, obj_coord=True, device=device, layout_scenes=layout_scenes), sets
