@@ -1,23 +1,18 @@
 // omg_grasp.hip — antipodal grasp sets from triangle meshes (include/omg_hip.h section 13).
 //
 // k_mesh_raycast: one thread per ray, one workgroup per (256 rays x one chunk of faces) of ONE mesh of a ragged batch, as a
-// host-built work list says (omgx_ray_work).  The chunk's faces stream through LDS in tiles of GRASP_TILE faces (9 doubles each),
-// every lane reading the same face at a time (LDS broadcast), like k_mesh_sdf.  With more than one chunk the partial (t, face)
-// pairs go to a workspace [chunks][N] and k_mesh_raycast_reduce folds them in chunk order with the same strict <, so the result
-// does not depend on the split.  k_grasp_poses: one thread per (ray, angle); blockIdx.y is the angle, blockIdx.x a ray group of
-// the same work list.  All arithmetic is float64 with contraction off (omg_grasp_body.h), one operation per operation of the
-// specification grasps.mesh_raycast / grasps.grasp_poses (omg-planner_amd/grasps.py).  Plain loads and stores only.
-#include <cmath>
-#include <cstdint>
-
-#include "omg_host.h"
+// host-built work list says (omgx_ray_work).  The chunk's faces stream through LDS tile by tile as in k_mesh_sdf (mesh_stage_faces,
+// omg_mesh_common.h).  With more than one chunk the partial (t, face) pairs go to a workspace [chunks][N] and
+// k_mesh_raycast_reduce folds them in chunk order with the same strict <, so the result does not depend on the split.
+// k_grasp_poses: one thread per (ray, angle); blockIdx.y is the angle, blockIdx.x a ray group of the same work list.  All
+// arithmetic is float64 with contraction off (omg_grasp_body.h), one operation per operation of the specification
+// grasps.mesh_raycast / grasps.grasp_poses (omg-planner_amd/grasps.py).  Plain loads and stores only.
+#include "omg_mesh_common.h"
 #include "omg_grasp_body.h"
 
 #pragma clang fp contract(off)
 
-#define GRASP_TILE OMGX_MESH_FACE_TILE  // the tile of k_mesh_sdf: omgx_mesh_sdf_tile()
 #define GRASP_BLOCK OMGX_RAYCAST_RAYS_PER_WORKGROUP
-static_assert(GRASP_TILE == GRASP_BLOCK, "the tile load below moves one face per thread");
 
 namespace {
 
@@ -27,7 +22,7 @@ __global__ __launch_bounds__(GRASP_BLOCK) void k_mesh_raycast(const double* __re
                                                               const double* __restrict__ origins, const double* __restrict__ dirs,
                                                               double t_min, double neg_tol, double one_tol, int64_t row_stride,
                                                               double* __restrict__ t_out, int32_t* __restrict__ face_out) {
-    __shared__ double tile[GRASP_TILE * 9];
+    __shared__ double tile[OMGX_MESH_FACE_TILE * 9];
     const omgx_ray_work w = work[blockIdx.x];  // uniform: scalar loads
     const omgx_mesh* __restrict__ ms = meshes + w.mesh;
     const double* __restrict__ mv = verts + (int64_t)ms->vert_begin * 3;
@@ -41,18 +36,9 @@ __global__ __launch_bounds__(GRASP_BLOCK) void k_mesh_raycast(const double* __re
     double best = __builtin_inf();
     int32_t face = -1;
     const int f_end = w.face_begin + w.face_count;
-    for (int t0 = w.face_begin; t0 < f_end; t0 += GRASP_TILE) {
-        const int cnt = min(GRASP_TILE, f_end - t0);
-        __syncthreads();
-        if ((int)threadIdx.x < cnt) {
-            const int32_t* f = mf + (int64_t)(t0 + (int)threadIdx.x) * 3;
-            for (int c = 0; c < 3; ++c) {
-                // the wrappers reject indices outside the mesh; clamped here so that no index can read outside the pool
-                const int v = min(max(f[c], 0), nv - 1);
-                for (int a = 0; a < 3; ++a) tile[threadIdx.x * 9 + c * 3 + a] = mv[(int64_t)v * 3 + a];
-            }
-        }
-        __syncthreads();
+    for (int t0 = w.face_begin; t0 < f_end; t0 += OMGX_MESH_FACE_TILE) {
+        const int cnt = min(OMGX_MESH_FACE_TILE, f_end - t0);
+        mesh_stage_faces(tile, mv, mf, nv, t0, cnt);
         for (int q = 0; q < cnt; ++q) {
             mesh_raycast_pair(ox, oy, oz, dx, dy, dz, tile + q * 9, t0 + q, t_min, neg_tol, one_tol, best, face);
         }
@@ -151,10 +137,6 @@ int64_t check_work(const omgx_mesh* h_meshes, int32_t M, const int32_t* h_ray_be
     return i == num_work ? groups : -1;
 }
 
-bool bad_mesh_geometry(const omgx_mesh& h) {
-    return h.vert_begin < 0 || h.face_begin < 0 || h.vert_count < 1 || h.face_count < 1;
-}
-
 }  // namespace
 
 extern "C" int32_t omgx_mesh_raycast_chunks(int32_t ray_workgroups, int32_t max_faces, int32_t chunks) {
@@ -165,7 +147,7 @@ extern "C" int32_t omgx_mesh_raycast_chunks(int32_t ray_workgroups, int32_t max_
     if (cu < 1) return OMGX_ERR_LAUNCH;
     // four workgroups per compute unit, no chunk below one tile
     const int64_t want = ((int64_t)4 * cu + ray_workgroups - 1) / ray_workgroups;
-    const int64_t tiles = ((int64_t)max_faces + GRASP_TILE - 1) / GRASP_TILE;
+    const int64_t tiles = ((int64_t)max_faces + OMGX_MESH_FACE_TILE - 1) / OMGX_MESH_FACE_TILE;
     int64_t c = want < tiles ? want : tiles;
     if (c > OMGX_RAYCAST_MAX_CHUNKS) c = OMGX_RAYCAST_MAX_CHUNKS;
     return (int32_t)(c < 1 ? 1 : c);
@@ -188,7 +170,7 @@ extern "C" int omgx_mesh_raycast(const double* verts, const int32_t* faces, cons
     if (num_work > 0 && (!work || !h_work || !origins || !dirs || !t_out || !face_out)) return OMGX_ERR_INVALID;
     int32_t max_faces = 1;
     for (int32_t m = 0; m < num_meshes; ++m) {
-        if (bad_mesh_geometry(h_meshes[m])) return OMGX_ERR_INVALID;
+        if (mesh_check_ranges(h_meshes[m]) != OMGX_OK) return OMGX_ERR_INVALID;  // the volume fields are not read here
         if (h_meshes[m].face_count > max_faces) max_faces = h_meshes[m].face_count;
     }
     if (chunks == 0) {  // the automatic choice, which the list must have been built for
@@ -237,15 +219,9 @@ extern "C" int omgx_grasp_poses(const omgx_mesh* meshes, const omgx_mesh* h_mesh
     if (num_work > 0 && (!work || !h_work || !p1 || !n1 || !dirs || !t || !face2 || !poses || !valid)) return OMGX_ERR_INVALID;
     for (int32_t m = 0; m < num_meshes; ++m) {
         const omgx_mesh& h = h_meshes[m];
-        if (h.face_begin < 0 || h.face_count < 1 || h.out_offset < 0) return OMGX_ERR_INVALID;
-        if (!(h.delta > 0.0) || !std::isfinite(h.delta)) return OMGX_ERR_INVALID;
-        if (h.dims[0] < 1 || h.dims[1] < 1 || h.dims[2] < 1) return OMGX_ERR_INVALID;
-        if (!(h.sample_offset == 0.0 || h.sample_offset == 0.5)) return OMGX_ERR_INVALID;
-        for (int a = 0; a < 3; ++a)
-            if (!std::isfinite(h.origin[a])) return OMGX_ERR_INVALID;
-        const int64_t total = (int64_t)h.dims[0] * h.dims[1] * h.dims[2];
-        if (total > (int64_t)1 << 31) return OMGX_ERR_UNSUPPORTED;
-        if (h.out_offset + total > pool_elems) return OMGX_ERR_INVALID;  // the volume must lie in the pool
+        const int status = mesh_check_ranges(h) != OMGX_OK ? OMGX_ERR_INVALID : mesh_check_volume(h);
+        if (status != OMGX_OK) return status;
+        if (h.out_offset + mesh_node_count(h) > pool_elems) return OMGX_ERR_INVALID;  // the volume must lie in the pool
     }
     const int64_t groups = check_work(h_meshes, num_meshes, h_ray_begin, h_ray_count, h_work, num_work, chunks, num_rays);
     if (groups < 0) return OMGX_ERR_INVALID;

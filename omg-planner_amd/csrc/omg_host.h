@@ -6,9 +6,6 @@
 
 #include "../../include/omg_hip.h"
 
-// Faces of a mesh staged in LDS at a time by k_mesh_sdf and k_mesh_raycast (omgx_mesh_sdf_tile()): one face per thread of a tile load.
-#define OMGX_MESH_FACE_TILE 256
-
 // Records "<what>: <hip error string>" for omgx_last_error() and returns OMGX_ERR_LAUNCH.
 int omgx_set_error(const char* what, hipError_t e);
 

@@ -1,0 +1,46 @@
+// omg_mesh_common.h — what the mesh translation units (omg_mesh_sdf.hip, omg_grasp.hip) share: the face tile that k_mesh_sdf and
+// k_mesh_raycast stage in LDS, and the checks on one host omgx_mesh record (include/omg_hip.h sections 12 and 13).
+#pragma once
+#include <cmath>
+#include <cstdint>
+
+#include "omg_host.h"
+
+// Faces of a mesh staged in LDS at a time (omgx_mesh_sdf_tile()), 9 doubles each: a, b, c.
+#define OMGX_MESH_FACE_TILE 256
+static_assert(OMGX_MESH_FACE_TILE == OMGX_MESH_SDF_NODES_PER_WORKGROUP && OMGX_MESH_FACE_TILE == OMGX_RAYCAST_RAYS_PER_WORKGROUP,
+              "mesh_stage_faces moves one face per thread");
+
+// The faces [t0, t0 + cnt) of a mesh (mv, mf: its rows of the vertex and face pools, nv vertices) into tile[cnt * 9], between two
+// barriers: every thread of the workgroup must call it, with cnt <= OMGX_MESH_FACE_TILE.
+__device__ __forceinline__ void mesh_stage_faces(double* tile, const double* __restrict__ mv, const int32_t* __restrict__ mf, int nv,
+                                                 int t0, int cnt) {
+    __syncthreads();
+    if ((int)threadIdx.x < cnt) {
+        const int32_t* f = mf + (int64_t)(t0 + (int)threadIdx.x) * 3;
+        for (int c = 0; c < 3; ++c) {
+            // the wrappers reject indices outside the mesh; clamped here so that no index can read outside the pool
+            const int v = min(max(f[c], 0), nv - 1);
+            for (int a = 0; a < 3; ++a) tile[threadIdx.x * 9 + c * 3 + a] = mv[(int64_t)v * 3 + a];
+        }
+    }
+    __syncthreads();
+}
+
+// One host record's rows of the vertex and face pools -> OMGX_OK or OMGX_ERR_INVALID.
+static inline int mesh_check_ranges(const omgx_mesh& h) {
+    return h.vert_begin < 0 || h.face_begin < 0 || h.vert_count < 1 || h.face_count < 1 ? OMGX_ERR_INVALID : OMGX_OK;
+}
+
+static inline int64_t mesh_node_count(const omgx_mesh& h) { return (int64_t)h.dims[0] * h.dims[1] * h.dims[2]; }
+// One host record's volume -> OMGX_OK, OMGX_ERR_INVALID, or OMGX_ERR_UNSUPPORTED for more than 2^31 nodes (an invalid field is
+// reported first).
+static inline int mesh_check_volume(const omgx_mesh& h) {
+    if (h.out_offset < 0) return OMGX_ERR_INVALID;
+    if (!(h.delta > 0.0) || !std::isfinite(h.delta)) return OMGX_ERR_INVALID;
+    if (h.dims[0] < 1 || h.dims[1] < 1 || h.dims[2] < 1) return OMGX_ERR_INVALID;
+    if (!(h.sample_offset == 0.0 || h.sample_offset == 0.5)) return OMGX_ERR_INVALID;
+    for (int a = 0; a < 3; ++a)
+        if (!std::isfinite(h.origin[a])) return OMGX_ERR_INVALID;
+    return mesh_node_count(h) > (int64_t)1 << 31 ? OMGX_ERR_UNSUPPORTED : OMGX_OK;
+}

@@ -1,29 +1,24 @@
 // omg_mesh_sdf.hip — signed distance grids from triangle meshes (include/omg_hip.h section 12, ABI 14).
 //
 // k_mesh_sdf: one thread per grid node, one workgroup per 256 nodes of ONE mesh of a ragged batch; the mesh's faces stream
-// through LDS in tiles of MSDF_TILE faces (9 doubles each: a, b, c), every lane reading the same face at a time (LDS
+// through LDS tile by tile (mesh_stage_faces, omg_mesh_common.h), every lane reading the same face at a time (LDS
 // broadcast), like k_point_cloud_sdf (omg_kernels.hip).  All arithmetic is float64 with contraction off, one operation per
 // line of the specification scenes.closest_point_on_triangle / scenes.mesh_sdf (omg-planner_amd/scenes.py), so the distance
 // has the specification's bits; the sign is the generalised winding number's decision |w| > 0.5, summed in float64 with the
 // device library's atan2 (the sum itself is not pinned, only the decision: DESIGN.md section 7d).
-#include <cmath>
-#include <cstdint>
-
-#include "omg_host.h"
+#include "omg_mesh_common.h"
 #include "omg_mesh_sdf_body.h"
 
 #pragma clang fp contract(off)
 
-#define MSDF_TILE OMGX_MESH_FACE_TILE
 #define MSDF_BLOCK OMGX_MESH_SDF_NODES_PER_WORKGROUP
-static_assert(MSDF_TILE == MSDF_BLOCK, "the tile load below moves one face per thread");
 
 namespace {
 
 __global__ __launch_bounds__(MSDF_BLOCK) void k_mesh_sdf(const double* __restrict__ verts, const int32_t* __restrict__ faces,
                                                           const omgx_mesh* __restrict__ meshes, int num_meshes,
                                                           float* __restrict__ out) {
-    __shared__ double tile[MSDF_TILE * 9];
+    __shared__ double tile[OMGX_MESH_FACE_TILE * 9];
     // the mesh of this workgroup: the last one whose first_workgroup is <= blockIdx.x (uniform: scalar loads)
     int lo = 0, hi = num_meshes - 1;
     while (lo < hi) {
@@ -45,18 +40,9 @@ __global__ __launch_bounds__(MSDF_BLOCK) void k_mesh_sdf(const double* __restric
     const int nv = ms.vert_count, nf = ms.face_count;
 
     double best = 1.0e300, wsum = 0.0;
-    for (int t0 = 0; t0 < nf; t0 += MSDF_TILE) {
-        const int cnt = min(MSDF_TILE, nf - t0);
-        __syncthreads();
-        if ((int)threadIdx.x < cnt) {
-            const int32_t* f = mf + (int64_t)(t0 + (int)threadIdx.x) * 3;
-            for (int c = 0; c < 3; ++c) {
-                // the wrappers reject indices outside the mesh; clamped here so that no index can read outside the pool
-                const int v = min(max(f[c], 0), nv - 1);
-                for (int a = 0; a < 3; ++a) tile[threadIdx.x * 9 + c * 3 + a] = mv[(int64_t)v * 3 + a];
-            }
-        }
-        __syncthreads();
+    for (int t0 = 0; t0 < nf; t0 += OMGX_MESH_FACE_TILE) {
+        const int cnt = min(OMGX_MESH_FACE_TILE, nf - t0);
+        mesh_stage_faces(tile, mv, mf, nv, t0, cnt);
         for (int q = 0; q < cnt; ++q) {
             mesh_sdf_pair(px, py, pz, tile + q * 9, best, wsum);
         }
@@ -70,7 +56,7 @@ __global__ __launch_bounds__(MSDF_BLOCK) void k_mesh_sdf(const double* __restric
 
 }  // namespace
 
-extern "C" int32_t omgx_mesh_sdf_tile(void) { return MSDF_TILE; }
+extern "C" int32_t omgx_mesh_sdf_tile(void) { return OMGX_MESH_FACE_TILE; }
 
 extern "C" int omgx_mesh_sdf(const double* verts, const int32_t* faces, const omgx_mesh* meshes, const omgx_mesh* h_meshes,
                              int32_t num_meshes, float* out, void* stream) {
@@ -79,16 +65,11 @@ extern "C" int omgx_mesh_sdf(const double* verts, const int32_t* faces, const om
     int64_t wg = 0;
     for (int32_t m = 0; m < num_meshes; ++m) {
         const omgx_mesh& h = h_meshes[m];
-        if (h.vert_begin < 0 || h.face_begin < 0 || h.vert_count < 1 || h.face_count < 1 || h.out_offset < 0) return OMGX_ERR_INVALID;
-        if (!(h.delta > 0.0) || !std::isfinite(h.delta)) return OMGX_ERR_INVALID;
-        if (h.dims[0] < 1 || h.dims[1] < 1 || h.dims[2] < 1) return OMGX_ERR_INVALID;
-        if (!(h.sample_offset == 0.0 || h.sample_offset == 0.5)) return OMGX_ERR_INVALID;
-        for (int a = 0; a < 3; ++a)
-            if (!std::isfinite(h.origin[a])) return OMGX_ERR_INVALID;
+        const int volume = mesh_check_volume(h);
+        if (mesh_check_ranges(h) != OMGX_OK || volume == OMGX_ERR_INVALID) return OMGX_ERR_INVALID;
         if (h.first_workgroup != wg) return OMGX_ERR_INVALID;  // the prefix table: workgroups of the meshes before this one
-        const int64_t total = (int64_t)h.dims[0] * h.dims[1] * h.dims[2];
-        if (total > (int64_t)1 << 31) too_big = true;
-        wg += (total + MSDF_BLOCK - 1) / MSDF_BLOCK;
+        if (volume != OMGX_OK) too_big = true;  // reported after an invalid record of any mesh
+        wg += (mesh_node_count(h) + MSDF_BLOCK - 1) / MSDF_BLOCK;
     }
     if (too_big || wg > 0x7fffffffll) return OMGX_ERR_UNSUPPORTED;
     hipLaunchKernelGGL(k_mesh_sdf, dim3((unsigned)wg), dim3(MSDF_BLOCK), 0, (hipStream_t)stream, verts, faces, meshes, num_meshes, out);

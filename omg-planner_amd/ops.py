@@ -1016,26 +1016,75 @@ def point_cloud_sdf(points: torch.Tensor, grid_resolution: float = 0.02, margin:
     return out, origin, float(grid_resolution)
 
 
-def _mesh_layout(verts, delta, padding, sample, origin, dims):
+class MeshPool:
+    """Host meshes [(verts [V,3] float, faces [F,3] int)] as omgx_mesh_sdf, omgx_mesh_raycast and omgx_grasp_poses take them:
+    each cleaned (scenes.clean_mesh) and appended to `verts` [V,3] float64 and `faces` [F,3] int32, its rows of both in `rec`
+    (omgx_mesh records).  Faces of zero area are dropped and counted in `dropped`, or rejected (drop_zero_area=False).  The
+    volume fields of a record are set_volume's; first_workgroup is the caller's."""
+
+    def __init__(self, meshes, drop_zero_area: bool):
+        from . import scenes as _sc
+        if len(meshes) < 1:
+            raise _lib.OmgHipError("a batch of meshes needs at least one mesh")
+        self.rec = (_lib.Mesh * len(meshes))()
+        vs, fs, self.dropped = [], [], []
+        v0 = f0 = 0
+        for m, (verts, faces) in enumerate(meshes):
+            try:
+                verts, faces, dropped = _sc.clean_mesh(verts, faces)
+            except ValueError as e:
+                raise _lib.OmgHipError(f"mesh {m}: {e}") from None
+            if dropped and not drop_zero_area:
+                raise _lib.OmgHipError(f"mesh {m}: {dropped} faces of zero area (scenes.clean_mesh removes them; face indices stay as given here)")
+            r = self.rec[m]
+            r.vert_begin, r.vert_count, r.face_begin, r.face_count = v0, len(verts), f0, len(faces)
+            v0, f0 = v0 + len(verts), f0 + len(faces)
+            vs.append(verts), fs.append(faces), self.dropped.append(dropped)
+        self.verts, self.faces = np.concatenate(vs), np.concatenate(fs)
+
+    def set_volume(self, m: int, origin, delta, sample, dims, out_offset, padding=4):
+        """The grid of mesh m's volume into its record: origin [3] and nodes per axis (both None: scenes.mesh_grid_layout with
+        `padding`), node spacing, "centre" or "node", the element offset of the volume in its buffer -> (origin, dims)."""
+        from . import scenes as _sc
+        if sample not in _sc.MESH_SAMPLE_OFFSET:
+            raise _lib.OmgHipError(f"mesh {m}: sample must be 'centre' or 'node', got {sample!r}")
+        r = self.rec[m]
+        origin, dims = _mesh_grid(self.verts[r.vert_begin: r.vert_begin + r.vert_count], delta, padding, origin, dims, m)
+        if len(dims) != 3 or min(dims) < 1 or int(out_offset) < 0:
+            raise _lib.OmgHipError(f"mesh {m}: the three dims must be >= 1 and the offset >= 0, got {dims} and {out_offset}")
+        r.origin[:], r.delta, r.sample_offset, r.dims[:] = list(origin), float(delta), _sc.MESH_SAMPLE_OFFSET[sample], list(dims)
+        r.out_offset = int(out_offset)
+        return origin, dims
+
+    def upload(self, device):
+        """(vertex pool, face pool, records as bytes) on `device`; the records as they are now."""
+        return (torch.from_numpy(self.verts).to(device), torch.from_numpy(self.faces).to(device),
+                torch.from_numpy(np.frombuffer(self.rec, np.uint8).copy()).to(device))
+
+
+def _mesh_grid(verts, delta, padding, origin, dims, m: int = 0):
+    """(origin [3] float64, dims as ints) of mesh m's grid: as given, or scenes.mesh_grid_layout's around `verts`."""
     from . import scenes as _sc
-    if sample not in _sc.MESH_SAMPLE_OFFSET:
-        raise _lib.OmgHipError(f"sample must be 'centre' or 'node', got {sample!r}")
-    if (origin is None) != (dims is None):
-        raise _lib.OmgHipError("give origin and dims together")
     if not (float(delta) > 0 and np.isfinite(float(delta))):
-        raise _lib.OmgHipError("delta must be positive and finite")
+        raise _lib.OmgHipError(f"mesh {m}: delta must be positive and finite, got {delta}")
+    if (origin is None) != (dims is None):
+        raise _lib.OmgHipError(f"mesh {m}: give origin and dims together")
     if origin is None:
         origin, dims = _sc.mesh_grid_layout(verts, float(delta), padding)
-    return np.asarray(origin, np.float64).copy(), tuple(int(d) for d in dims), _sc.MESH_SAMPLE_OFFSET[sample]
+    return np.asarray(origin, np.float64).copy(), tuple(int(d) for d in dims)
 
 
-def _mesh_pack(meshes, delta, padding, sample, origins, dims, out_offsets):
-    """Host side of mesh_sdf_batch: every mesh cleaned and laid out -> (omgx_mesh records, vertex pool [V,3] float64, face pool
-    [F,3] int32, shapes, origins, deltas, dropped, elements of the volumes back to back)."""
-    from . import scenes as _sc
+def mesh_sdf_batch(meshes, delta, padding=4, sample="centre", origins=None, dims=None, out=None, out_offsets=None, device="cuda:0"):
+    """Signed distance grids of M triangle meshes in ONE launch (omgx_mesh_sdf; scenes.mesh_sdf is the specification: the same
+    float32 magnitudes bit for bit, the sign from the winding number's decision |w| > 0.5).
+    meshes: a list of (verts [V,3] float, faces [F,3] int) on the host; delta / padding / sample: one value for all or a list
+    with one per mesh; origins / dims: None (scenes.mesh_grid_layout per mesh) or lists with an explicit layout per mesh.
+    out: None -> one flat float32 buffer holding the volumes back to back; or a contiguous float32 device tensor (the SDF
+    pool, for instance) written IN PLACE at the element offsets `out_offsets` (one per mesh; the volumes must not overlap), its
+    autograd version counter bumped like point_cloud_sdf does.
+    -> (grids: M float32 [X,Y,Z] views into the buffer, origins: M float64 [3], deltas: M floats, dropped: M counts of zero-area
+    faces left out).  Raises OmgHipError on indices outside a mesh's vertices, a mesh left without faces, a bad layout."""
     M = len(meshes)
-    if M < 1:
-        raise _lib.OmgHipError("mesh_sdf_batch needs at least one mesh")
 
     def per_mesh(x, name):
         if isinstance(x, (list, tuple)):
@@ -1050,41 +1099,17 @@ def _mesh_pack(meshes, delta, padding, sample, origins, dims, out_offsets):
         raise _lib.OmgHipError(f"origins and dims must have one entry per mesh ({M})")
     if out_offsets is not None and len(out_offsets) != M:
         raise _lib.OmgHipError(f"out_offsets must have one entry per mesh ({M})")
-    rec = (_lib.Mesh * M)()
-    vs, fs, shapes, org, dropped = [], [], [], [], []
-    v0 = f0 = wg = flat = 0
-    for m, (verts, faces) in enumerate(meshes):
-        try:
-            verts, faces, drop = _sc.clean_mesh(verts, faces)
-        except ValueError as e:
-            raise _lib.OmgHipError(f"mesh {m}: {e}") from None
-        o, d, off = _mesh_layout(verts, deltas[m], pads[m], samples[m], None if origins is None else origins[m], None if dims is None else dims[m])
-        if min(d) < 1:
-            raise _lib.OmgHipError(f"mesh {m}: dims must be >= 1, got {d}")
+    mp = MeshPool(meshes, drop_zero_area=True)
+    shapes, org = [], []
+    wg = flat = 0
+    for m in range(M):
+        o, d = mp.set_volume(m, None if origins is None else origins[m], deltas[m], samples[m], None if dims is None else dims[m],
+                             flat if out_offsets is None else out_offsets[m], pads[m])
         n = d[0] * d[1] * d[2]
-        r = rec[m]
-        r.origin[:], r.delta, r.sample_offset, r.dims[:] = list(o), float(deltas[m]), off, list(d)
-        r.vert_begin, r.vert_count, r.face_begin, r.face_count = v0, len(verts), f0, len(faces)
-        r.first_workgroup = wg
-        r.out_offset = flat if out_offsets is None else int(out_offsets[m])
+        mp.rec[m].first_workgroup = wg  # the prefix table that maps a workgroup to its mesh
         wg += -(-n // _lib.MESH_SDF_NODES_PER_WORKGROUP)
-        flat, v0, f0 = flat + n, v0 + len(verts), f0 + len(faces)
-        vs.append(verts), fs.append(faces), shapes.append(d), org.append(o), dropped.append(drop)
-    return rec, np.concatenate(vs), np.concatenate(fs), shapes, org, [float(x) for x in deltas], dropped, flat
-
-
-def mesh_sdf_batch(meshes, delta, padding=4, sample="centre", origins=None, dims=None, out=None, out_offsets=None, device="cuda:0"):
-    """Signed distance grids of M triangle meshes in ONE launch (omgx_mesh_sdf; scenes.mesh_sdf is the specification: the same
-    float32 magnitudes bit for bit, the sign from the winding number's decision |w| > 0.5).
-    meshes: a list of (verts [V,3] float, faces [F,3] int) on the host; delta / padding / sample: one value for all or a list
-    with one per mesh; origins / dims: None (scenes.mesh_grid_layout per mesh) or lists with an explicit layout per mesh.
-    out: None -> one flat float32 buffer holding the volumes back to back; or a contiguous float32 device tensor (the SDF
-    pool, for instance) written IN PLACE at the element offsets `out_offsets` (one per mesh; the volumes must not overlap), its
-    autograd version counter bumped like point_cloud_sdf does.
-    -> (grids: M float32 [X,Y,Z] views into the buffer, origins: M float64 [3], deltas: M floats, dropped: M counts of zero-area
-    faces left out).  Raises OmgHipError on indices outside a mesh's vertices, a mesh left without faces, a bad layout."""
-    rec, verts, faces, shapes, org, deltas, dropped, flat = _mesh_pack(meshes, delta, padding, sample, origins, dims, out_offsets)
-    M = len(meshes)
+        flat += n
+        shapes.append(d), org.append(o)
     if out is None:
         if out_offsets is not None:
             raise _lib.OmgHipError("out_offsets needs out")
@@ -1093,21 +1118,20 @@ def mesh_sdf_batch(meshes, delta, padding=4, sample="centre", origins=None, dims
         _need(out, torch.float32, "out")
         if out_offsets is None and M > 1:
             raise _lib.OmgHipError("out needs out_offsets (one element offset per mesh)")
-        spans = sorted((int(rec[m].out_offset), int(np.prod(shapes[m]))) for m in range(M))
+        spans = sorted((int(mp.rec[m].out_offset), int(np.prod(shapes[m]))) for m in range(M))
         if spans[0][0] < 0 or spans[-1][0] + spans[-1][1] > out.numel() or any(spans[i][0] + spans[i][1] > spans[i + 1][0] for i in range(M - 1)):
             raise _lib.OmgHipError(f"the volumes (offset, elements) {spans} overlap or leave out ({out.numel()} elements)")
         torch.autograd.graph.increment_version(out)
     dev = out.device
-    d_verts, d_faces = torch.from_numpy(verts).to(dev), torch.from_numpy(faces).to(dev)
-    d_rec = torch.from_numpy(np.frombuffer(rec, np.uint8).copy()).to(dev)
+    d_verts, d_faces, d_rec = mp.upload(dev)
     with torch.cuda.device(dev):
-        check(_lib.lib().omgx_mesh_sdf(_ptr(d_verts), _ptr(d_faces), _ptr(d_rec), C.cast(rec, C.c_void_p), M, _ptr(out), _stream()),
+        check(_lib.lib().omgx_mesh_sdf(_ptr(d_verts), _ptr(d_faces), _ptr(d_rec), C.cast(mp.rec, C.c_void_p), M, _ptr(out), _stream()),
               "omgx_mesh_sdf")
         for t in (d_verts, d_faces, d_rec):
             t.record_stream(torch.cuda.current_stream(dev))
     flat_out = out.reshape(-1)
-    grids = [flat_out[int(rec[m].out_offset): int(rec[m].out_offset) + int(np.prod(shapes[m]))].view(shapes[m]) for m in range(M)]
-    return grids, org, deltas, dropped
+    grids = [flat_out[int(mp.rec[m].out_offset): int(mp.rec[m].out_offset) + int(np.prod(shapes[m]))].view(shapes[m]) for m in range(M)]
+    return grids, org, [float(x) for x in deltas], mp.dropped
 
 
 def mesh_sdf(verts, faces, delta, padding=4, sample="centre", origin=None, dims=None, out=None, device="cuda:0"):
@@ -1118,7 +1142,7 @@ def mesh_sdf(verts, faces, delta, padding=4, sample="centre", origin=None, dims=
     debug level; mesh_sdf_batch returns it)."""
     if out is not None:
         _need(out, torch.float32, "out")
-        _, d, _ = _mesh_layout(np.asarray(verts, np.float64), delta, padding, sample, origin, dims)
+        _, d = _mesh_grid(np.asarray(verts, np.float64), delta, padding, origin, dims)
         if out.numel() != d[0] * d[1] * d[2]:
             raise _lib.OmgHipError(f"out must hold {d[0] * d[1] * d[2]} elements (grid {d})")
     grids, org, deltas, dropped = mesh_sdf_batch([(verts, faces)], delta, padding, sample, None if origin is None else [origin],
@@ -1141,10 +1165,8 @@ class RayBatch:
     mesh (origin [3], delta, sample, dims, element offset in the pool) of its volume, needed by grasp_poses only."""
 
     def __init__(self, meshes, ray_counts, ray_begins=None, num_rays=None, chunks: int = 0, device="cuda:0", layout=None):
-        from . import scenes as _sc
+        mp = MeshPool(meshes, drop_zero_area=False)  # dropping them here would renumber the faces the results name
         M = len(meshes)
-        if M < 1:
-            raise _lib.OmgHipError("a ray batch needs at least one mesh")
         if len(ray_counts) != M or (ray_begins is not None and len(ray_begins) != M) or (layout is not None and len(layout) != M):
             raise _lib.OmgHipError(f"ray_counts, ray_begins and layout must have one entry per mesh ({M})")
         counts = [int(c) for c in ray_counts]
@@ -1160,40 +1182,20 @@ class RayBatch:
             raise _lib.OmgHipError(f"chunks must lie in [0, {_lib.RAYCAST_MAX_CHUNKS}], got {chunks}")
         self.device = torch.device(device)
         self.num_meshes, self.ray_begin, self.ray_count, self.has_layout = M, begins, counts, layout is not None
-        self.rec = (_lib.Mesh * M)()
-        vs, fs = [], []
-        v0 = f0 = 0
-        for m, (verts, faces) in enumerate(meshes):
-            try:
-                verts, faces, dropped = _sc.clean_mesh(verts, faces)
-            except ValueError as e:
-                raise _lib.OmgHipError(f"mesh {m}: {e}") from None
-            if dropped:  # dropping them here would renumber the faces the results name
-                raise _lib.OmgHipError(f"mesh {m}: {dropped} faces of zero area (scenes.clean_mesh removes them; face indices stay as given here)")
-            r = self.rec[m]
-            o, delta, sample, dims, off = ((0.0, 0.0, 0.0), 1.0, "centre", (1, 1, 1), 0) if layout is None else layout[m]
-            if sample not in _sc.MESH_SAMPLE_OFFSET:
-                raise _lib.OmgHipError(f"sample must be 'centre' or 'node', got {sample!r}")
-            if not (float(delta) > 0 and np.isfinite(float(delta))) or min(int(x) for x in dims) < 1 or int(off) < 0:
-                raise _lib.OmgHipError(f"mesh {m}: delta must be positive and finite, dims >= 1, the offset >= 0")
-            r.origin[:], r.delta, r.sample_offset, r.dims[:] = [float(x) for x in o], float(delta), _sc.MESH_SAMPLE_OFFSET[sample], [int(x) for x in dims]
-            r.out_offset, r.first_workgroup = int(off), 0
-            r.vert_begin, r.vert_count, r.face_begin, r.face_count = v0, len(verts), f0, len(faces)
-            v0, f0 = v0 + len(verts), f0 + len(faces)
-            vs.append(verts), fs.append(faces)
-        self.num_faces = f0
+        for m in range(M):
+            mp.set_volume(m, *(((0.0, 0.0, 0.0), 1.0, "centre", (1, 1, 1), 0) if layout is None else layout[m]))
+        self.rec, self.num_faces = mp.rec, len(mp.faces)
         groups = sum(-(-c // _lib.RAYCAST_RAYS_PER_WORKGROUP) for c in counts)
-        max_faces = max(len(f) for f in fs)
         if int(chunks) == 0 and groups > 0:
             with torch.cuda.device(self.device):
-                self.chunks = int(_lib.lib().omgx_mesh_raycast_chunks(groups, max_faces, 0))
+                self.chunks = int(_lib.lib().omgx_mesh_raycast_chunks(groups, max(r.face_count for r in self.rec), 0))
             check(min(self.chunks, 0), "omgx_mesh_raycast_chunks")
         else:
             self.chunks = max(int(chunks), 1)
         tile = int(_lib.lib().omgx_mesh_sdf_tile())
         work = []
         for m in range(M):
-            nf = len(fs[m])
+            nf = int(self.rec[m].face_count)
             tiles = -(-nf // tile)
             cut = [min(nf, tile * ((c * tiles) // self.chunks)) for c in range(self.chunks)] + [nf]
             for r0 in range(0, counts[m], _lib.RAYCAST_RAYS_PER_WORKGROUP):
@@ -1202,10 +1204,8 @@ class RayBatch:
         self.num_work = len(work)
         self.h_work = np.ascontiguousarray(np.array(work, np.int32).reshape(-1, 6))
         self.h_ray_begin, self.h_ray_count = np.array(begins, np.int32), np.array(counts, np.int32)
-        dev = self.device
-        self.verts, self.faces = torch.from_numpy(np.concatenate(vs)).to(dev), torch.from_numpy(np.concatenate(fs)).to(dev)
-        self.d_rec = torch.from_numpy(np.frombuffer(self.rec, np.uint8).copy()).to(dev)
-        self.d_work = torch.from_numpy(self.h_work if self.num_work else np.zeros((1, 6), np.int32)).to(dev)
+        self.verts, self.faces, self.d_rec = mp.upload(self.device)
+        self.d_work = torch.from_numpy(self.h_work if self.num_work else np.zeros((1, 6), np.int32)).to(self.device)
 
     def _args(self):
         """(meshes, h_meshes, M, h_ray_begin, h_ray_count, work, h_work, num_work, chunks) as the entry points take them."""

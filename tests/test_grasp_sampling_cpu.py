@@ -440,6 +440,10 @@ def test_c_abi_argument_checks_without_gpu():
     assert pose(_mesh_records(face_count=0)) == INV and pose(_mesh_records(face_begin=-1)) == INV
     assert pose(pool_elems=419) == INV and pose(pool_elems=-1) == INV        # the second volume leaves the pool
     assert pose(_mesh_records(dims=[2048, 2048, 513]), pool_elems=1 << 40) == UNS
+    mixed = _mesh_records(delta=0.0)                                         # mesh 0 too big, mesh 1 invalid: the first mesh decides
+    mixed[0].dims[:] = [2048, 2048, 513]
+    assert pose(mixed, pool_elems=1 << 40) == UNS
+    assert pose(mixed, pool_elems=pool) == UNS                               # and within a mesh, before the pool's bounds
     nan = float("nan")
     for i in range(5):
         w = [0.08, 0.005, 0.96, 0.088, 0.0]

@@ -326,6 +326,12 @@ def test_c_abi_argument_checks_without_gpu():
     assert call(_records(dims=[2048, 2048, 513], delta=0.0)) == INV  # an invalid argument is reported first
     big = _records(1, dims=[2048, 2048, 513])
     assert call(big, M=1) == UNS
+    mixed = _records(delta=0.0)                                      # mesh 0 too big, mesh 1 invalid: INVALID in any mesh comes first
+    mixed[0].dims[:] = [2048, 2048, 513]
+    mixed[1].first_workgroup = -(-2048 * 2048 * 513 // 256)
+    assert call(mixed) == INV
+    mixed[1].delta = 0.01                                            # (the delta alone made it invalid)
+    assert call(mixed) == UNS
 
 
 def test_wrapper_checks_without_gpu():

@@ -64,38 +64,35 @@ def main():
     G, M = a.grid, a.objects
     delta = 0.16 / G
     origin, dims = np.full(3, -0.08), (G, G, G)
-    lib = _lib.lib()
 
-    def prepared(count):
-        rng = np.random.RandomState(0)
-        meshes = [(v * rng.uniform(0.9, 1.1), f) for _ in range(count)]  # objects of one size, not one object
-        rec, verts, faces, shapes, _, _, _, flat = ops._mesh_pack(meshes, delta, 0, "centre", [origin] * count, [dims] * count, None)
-        d_v, d_f = torch.from_numpy(verts).to(dev), torch.from_numpy(faces).to(dev)
-        d_rec = torch.from_numpy(np.frombuffer(rec, np.uint8).copy()).to(dev)
-        out = torch.empty(flat, dtype=torch.float32, device=dev)
-        return meshes, rec, d_v, d_f, d_rec, out
+    rng = np.random.RandomState(0)
+    meshes = [(v * rng.uniform(0.9, 1.1), f) for _ in range(M)]  # objects of one size, not one object
 
-    def launch(rec, d_v, d_f, d_rec, out, count):
-        _lib.check(lib.omgx_mesh_sdf(ops._ptr(d_v), ops._ptr(d_f), ops._ptr(d_rec), C.cast(rec, C.c_void_p), count, ops._ptr(out),
-                                     ops._stream()), "omgx_mesh_sdf")
+    def prepared(batch, offsets):
+        """A batch pooled and on the device, volume m at element offsets[m] of the output -> (records, their three tensors)."""
+        mp = ops.MeshPool(batch, drop_zero_area=True)
+        for m, off in enumerate(offsets):
+            mp.set_volume(m, origin, delta, "centre", dims, off)
+            mp.rec[m].first_workgroup = m * -(-G ** 3 // _lib.MESH_SDF_NODES_PER_WORKGROUP)
+        return (mp.rec, *mp.upload(dev))
+
+    def launch(rec, d_v, d_f, d_rec, out):
+        _lib.check(_lib.lib().omgx_mesh_sdf(d_v.data_ptr(), d_f.data_ptr(), d_rec.data_ptr(), C.cast(rec, C.c_void_p), len(rec), out.data_ptr(),
+                                           stream.cuda_stream), "omgx_mesh_sdf")
 
     # (a)
-    _, rec1, v1, f1, r1, out1 = prepared(1)
-    a_ms, a_all = timed(lambda: launch(rec1, v1, f1, r1, out1, 1), a.reps, stream)
+    one, out1 = prepared(meshes[:1], [0]), torch.empty(G ** 3, dtype=torch.float32, device=dev)
+    a_ms, a_all = timed(lambda: launch(*one, out1), a.reps, stream)
     # (b)
-    meshes, recM, vM, fM, rM, outM = prepared(M)
-    b_ms, b_all = timed(lambda: launch(recM, vM, fM, rM, outM, M), a.reps, stream)
+    many, outM = prepared(meshes, [m * G ** 3 for m in range(M)]), torch.empty(M * G ** 3, dtype=torch.float32, device=dev)
+    b_ms, b_all = timed(lambda: launch(*many, outM), a.reps, stream)
     # (c): one record set per object, each a batch of one at its own offset
-    singles = []
-    for m in range(M):
-        rec, verts, faces, _, _, _, _, _ = ops._mesh_pack([meshes[m]], delta, 0, "centre", [origin], [dims], [m * G ** 3])
-        singles.append((rec, torch.from_numpy(verts).to(dev), torch.from_numpy(faces).to(dev),
-                        torch.from_numpy(np.frombuffer(rec, np.uint8).copy()).to(dev)))
+    singles = [prepared([meshes[m]], [m * G ** 3]) for m in range(M)]
     outC = torch.empty_like(outM)
 
     def all_single():
-        for rec, d_v, d_f, d_rec in singles:
-            launch(rec, d_v, d_f, d_rec, outC, 1)
+        for single in singles:
+            launch(*single, outC)
     c_ms, c_all = timed(all_single, a.reps, stream)
     same = bool(torch.equal(outC.view(torch.int32), outM.view(torch.int32)))
     # the wrapper as a user calls it (host work + uploads + launch), wall clock
