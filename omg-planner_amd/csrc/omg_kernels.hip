@@ -903,6 +903,13 @@ extern "C" void omgx_debug_set_wide(int on, long long max8, long long max6, long
     if (long6 >= 0) g_wide_long6 = long6; else if (long6 < -1) g_wide_long6 = GS_WIDE6_LONG_MAX_ITEMS;
 }
 
+// One goal-set launch: bracketed by the timing events when this launch is recorded (timing_events), plain otherwise.
+template <class K>
+static void gs_launch(K* kernel, unsigned grid, unsigned block, uint32_t lds, hipStream_t st, hipEvent_t ev0, hipEvent_t ev1, const ChunkArgs& ca) {
+    if (ev0) hipExtLaunchKernelGGL(kernel, dim3(grid), dim3(block), lds, st, ev0, ev1, 0, ca);
+    else hipLaunchKernelGGL(kernel, dim3(grid), dim3(block), lds, st, ca);
+}
+
 // dynamic LDS and grid of a k_goalset_queue launch (goal workgroups and / or trajectory-layer workgroups)
 static int launch_goalset(ChunkArgs& ca, int timing_kind, hipStream_t st, const GsTiling& tl = GsTiling()) {
     const int scene_groups = (ca.S + 7) / 8;
@@ -994,24 +1001,16 @@ static int launch_goalset(ChunkArgs& ca, int timing_kind, hipStream_t st, const 
 #ifdef OMGX_GS_CLOCK  // measurement build only (tools/gs_phase_clock.py): fewer workgroups per CU by asking for more LDS than the layout needs
     if (const char* e = getenv("OMGX_GS_LDS_MIN")) { const uint32_t v = (uint32_t)atoi(e); if (v > l32 && v <= 64 * 1024) l32 = v; }
 #endif
-#define GQ_GO(STAMP, LAT, SPLIT, PRE) do { if (ev0) hipExtLaunchKernelGGL((k_goalset_queue<2, STAMP, LAT, SPLIT, PRE>), dim3(g), dim3((LAT) ? 256 : GQ_NT), l32, st, ev0, ev1, 0, ca); \
-                                            else hipLaunchKernelGGL((k_goalset_queue<2, STAMP, LAT, SPLIT, PRE>), dim3(g), dim3((LAT) ? 256 : GQ_NT), l32, st, ca); } while (0)
-#define GQ_GO_W(STAMP, WW) do { if (ev0) hipExtLaunchKernelGGL((k_goalset_queue<2, STAMP, false, false, false, WW>), dim3(g), dim3(64 * WW), l32, st, ev0, ev1, 0, ca); \
-                                 else hipLaunchKernelGGL((k_goalset_queue<2, STAMP, false, false, false, WW>), dim3(g), dim3(64 * WW), l32, st, ca); } while (0)
-    if (range) {
-        if (ca.work) { if (ev0) hipExtLaunchKernelGGL((k_goalset_range<2, true>), dim3(g), dim3(GQ_NT), l32, st, ev0, ev1, 0, ca); else hipLaunchKernelGGL((k_goalset_range<2, true>), dim3(g), dim3(GQ_NT), l32, st, ca); }
-        else { if (ev0) hipExtLaunchKernelGGL((k_goalset_range<2, false>), dim3(g), dim3(GQ_NT), l32, st, ev0, ev1, 0, ca); else hipLaunchKernelGGL((k_goalset_range<2, false>), dim3(g), dim3(GQ_NT), l32, st, ca); }
-    } else
-    if (wide == 6) { if (ca.work) GQ_GO_W(true, 6); else GQ_GO_W(false, 6); }
-    else if (wide == 8) { if (ca.work) GQ_GO_W(true, 8); else GQ_GO_W(false, 8); }
-    else
-    if (ca.spread) { if (pre) GQ_GO(false, true, false, true); else GQ_GO(false, true, false, false); }
-    else if (split && ca.work) { if (pre) GQ_GO(true, false, true, true); else GQ_GO(true, false, true, false); }
-    else if (split) { if (pre) GQ_GO(false, false, true, true); else GQ_GO(false, false, true, false); }
-    else if (ca.work) { if (pre) GQ_GO(true, false, false, true); else GQ_GO(true, false, false, false); }
-    else { if (pre) GQ_GO(false, false, false, true); else GQ_GO(false, false, false, false); }
-#undef GQ_GO
-#undef GQ_GO_W
+    // k_goalset_queue<2, STAMP, LAT, SPLIT, PRE, W> and k_goalset_range<2, STAMP>
+    const auto go = [&](auto* kernel, int block) { gs_launch(kernel, g, (unsigned)block, l32, st, ev0, ev1, ca); };
+    if (range) { if (ca.work) go(k_goalset_range<2, true>, GQ_NT); else go(k_goalset_range<2, false>, GQ_NT); }
+    else if (wide == 6) { if (ca.work) go(k_goalset_queue<2, true, false, false, false, 6>, 64 * 6); else go(k_goalset_queue<2, false, false, false, false, 6>, 64 * 6); }
+    else if (wide == 8) { if (ca.work) go(k_goalset_queue<2, true, false, false, false, 8>, 64 * 8); else go(k_goalset_queue<2, false, false, false, false, 8>, 64 * 8); }
+    else if (ca.spread) { if (pre) go(k_goalset_queue<2, false, true, false, true>, 256); else go(k_goalset_queue<2, false, true, false, false>, 256); }
+    else if (split && ca.work) { if (pre) go(k_goalset_queue<2, true, false, true, true>, GQ_NT); else go(k_goalset_queue<2, true, false, true, false>, GQ_NT); }
+    else if (split) { if (pre) go(k_goalset_queue<2, false, false, true, true>, GQ_NT); else go(k_goalset_queue<2, false, false, true, false>, GQ_NT); }
+    else if (ca.work) { if (pre) go(k_goalset_queue<2, true, false, false, true>, GQ_NT); else go(k_goalset_queue<2, true, false, false, false>, GQ_NT); }
+    else { if (pre) go(k_goalset_queue<2, false, false, false, true>, GQ_NT); else go(k_goalset_queue<2, false, false, false, false>, GQ_NT); }
     g_last_goalset_variant = (range ? 0x100 : 0) | (split ? 0x200 : 0) | (ca.spread ? 0x400 : 0) | (pre ? 0x800 : 0) | (range ? GQ_WAVES : wide);
     OMGX_CHECK_LAUNCH("k_goalset_queue");
     return OMGX_OK;
@@ -1168,43 +1167,56 @@ extern "C" int omgx_pose_table(const double* robot, int32_t n_points, const doub
     return OMGX_OK;
 }
 
-static int goalset_cost_impl(const double* robot, int32_t n_points, const omgx_object* objects, const int32_t* scene_begin,
-                             const float* sdf_pool, const double* traj_start, int64_t traj_start_stride, const double* goals,
-                             int32_t num_scenes, int32_t num_goals, int32_t n_remaining, double time_interval,
-                             int32_t soften_fingers, float* goal_cost, float* potentials, float* collides, void* workspace,
-                             const double* layer_traj, int32_t layer_n, int32_t layer_soften, float* layer_pot, float* layer_grad,
-                             float* layer_col, const int32_t* active, const int32_t* goal_count, const int32_t* schedule,
-                             int32_t schedule_len, uint32_t* work, void* stream, const GsTiling& tiling = GsTiling()) {
-    if (num_scenes < 0 || num_goals < 0) return OMGX_ERR_INVALID;
-    if (num_scenes == 0 || (num_goals == 0 && !layer_traj)) return OMGX_OK;
-    if (!robot || !objects || !scene_begin) return OMGX_ERR_INVALID;
-    if (num_goals > 0 && (!traj_start || !goals || !goal_cost)) return OMGX_ERR_INVALID;
-    if (n_points < 1 || n_points > OMGX_MAX_POINTS || n_remaining < 1 || n_remaining > OMGX_MAX_WAYPOINTS)
+// The arguments of a goal-set launch by name (goalset_cost_impl); every default means "absent".
+struct GoalsetCall {
+    const double* robot = nullptr; int32_t n_points = 0;
+    const omgx_object* objects = nullptr; const int32_t* scene_begin = nullptr; const float* sdf_pool = nullptr;
+    const double* traj_start = nullptr; int64_t traj_start_stride = 0; const double* goals = nullptr;
+    int32_t num_scenes = 0, num_goals = 0, n_remaining = 0, soften_fingers = 0;
+    double time_interval = 0.0;
+    float *goal_cost = nullptr, *collides = nullptr;
+    float* potentials = nullptr;  // per-point potentials: the k_sdf_chunks path, without layer, masks or schedule
+    void* workspace = nullptr;    // the goals' kinematics as a launch of their own (ABI 10)
+    const double* layer_traj = nullptr;  // the trajectory layer rides on k_goalset_queue (cost-only batch)
+    int32_t layer_n = 0, layer_soften = 0;
+    float *layer_pot = nullptr, *layer_grad = nullptr, *layer_col = nullptr;
+    const int32_t *active = nullptr, *goal_count = nullptr, *schedule = nullptr;
+    int32_t schedule_len = 0; uint32_t* work = nullptr;
+    void* stream = nullptr;
+    GsTiling tiling;  // (its kin_ws is taken from `workspace`)
+};
+
+static int goalset_cost_impl(const GoalsetCall& a) {
+    if (a.num_scenes < 0 || a.num_goals < 0) return OMGX_ERR_INVALID;
+    if (a.num_scenes == 0 || (a.num_goals == 0 && !a.layer_traj)) return OMGX_OK;
+    if (!a.robot || !a.objects || !a.scene_begin) return OMGX_ERR_INVALID;
+    if (a.num_goals > 0 && (!a.traj_start || !a.goals || !a.goal_cost)) return OMGX_ERR_INVALID;
+    if (a.n_points < 1 || a.n_points > OMGX_MAX_POINTS || a.n_remaining < 1 || a.n_remaining > OMGX_MAX_WAYPOINTS)
         return OMGX_ERR_UNSUPPORTED;
-    if (!(time_interval > 0.0) || (num_goals > 0 && traj_start_stride < 9)) return OMGX_ERR_INVALID;
-    hipStream_t st = (hipStream_t)stream;
-    const int n = num_goals > 0 ? n_remaining : 0, C = num_goals * n;
-    if (layer_traj) {  // the trajectory layer rides on k_goalset_queue (cost-only batch)
-        if (!layer_pot || !layer_grad || !layer_col) return OMGX_ERR_INVALID;
-        if (layer_n < 1 || layer_n > OMGX_MAX_WAYPOINTS) return OMGX_ERR_UNSUPPORTED;
-        if (potentials) return OMGX_ERR_UNSUPPORTED;
+    if (!(a.time_interval > 0.0) || (a.num_goals > 0 && a.traj_start_stride < 9)) return OMGX_ERR_INVALID;
+    hipStream_t st = (hipStream_t)a.stream;
+    const int n = a.num_goals > 0 ? a.n_remaining : 0, C = a.num_goals * n;
+    if (a.layer_traj) {
+        if (!a.layer_pot || !a.layer_grad || !a.layer_col) return OMGX_ERR_INVALID;
+        if (a.layer_n < 1 || a.layer_n > OMGX_MAX_WAYPOINTS) return OMGX_ERR_UNSUPPORTED;
+        if (a.potentials) return OMGX_ERR_UNSUPPORTED;
     }
-    if ((active || goal_count || schedule || work) && potentials) return OMGX_ERR_UNSUPPORTED;  // masks and schedules live in k_goalset_queue
+    if ((a.active || a.goal_count || a.schedule || a.work) && a.potentials) return OMGX_ERR_UNSUPPORTED;  // masks and schedules live in k_goalset_queue
     ChunkArgs ca{};
-    ca.robot = robot; ca.objects = objects; ca.scene_begin = scene_begin; ca.pool = sdf_pool;
-    ca.S = num_scenes; ca.C = C; ca.CH = n; ca.NCH = num_goals; ca.P = n_points; ca.soften = soften_fingers != 0;
-    ca.arc = 1; ca.inv_dt = (float)(1.0 / time_interval);
-    ca.pot = potentials; ca.grad = nullptr; ca.col = nullptr; ca.chunk_cost = goal_cost; ca.chunk_col = collides;
-    ca.traj_start = traj_start; ca.ts_stride = traj_start_stride; ca.goals = goals;  // every workgroup runs its own kinematics
-    if (layer_traj) {
-        ca.wp_traj = layer_traj; ca.wp_n = layer_n; ca.wp_soften = layer_soften != 0;
-        ca.wp_pot = layer_pot; ca.wp_grad = layer_grad; ca.wp_col = layer_col;
+    ca.robot = a.robot; ca.objects = a.objects; ca.scene_begin = a.scene_begin; ca.pool = a.sdf_pool;
+    ca.S = a.num_scenes; ca.C = C; ca.CH = n; ca.NCH = a.num_goals; ca.P = a.n_points; ca.soften = a.soften_fingers != 0;
+    ca.arc = 1; ca.inv_dt = (float)(1.0 / a.time_interval);
+    ca.pot = a.potentials; ca.grad = nullptr; ca.col = nullptr; ca.chunk_cost = a.goal_cost; ca.chunk_col = a.collides;
+    ca.traj_start = a.traj_start; ca.ts_stride = a.traj_start_stride; ca.goals = a.goals;  // every workgroup runs its own kinematics
+    if (a.layer_traj) {
+        ca.wp_traj = a.layer_traj; ca.wp_n = a.layer_n; ca.wp_soften = a.layer_soften != 0;
+        ca.wp_pot = a.layer_pot; ca.wp_grad = a.layer_grad; ca.wp_col = a.layer_col;
     }
-    if (schedule && (schedule_len < 8 || schedule_len % 8 != 0)) return OMGX_ERR_INVALID;
-    ca.active = active; ca.goal_count = goal_count; ca.schedule = schedule; ca.sched_len = schedule ? schedule_len : 0; ca.work = work;
-    GsTiling tl = tiling;
-    tl.kin_ws = workspace;  // non-null: the goals' kinematics as a launch of their own (ABI 10)
-    return potentials ? launch_chunks(ca, st) : launch_goalset(ca, 0, st, tl);
+    if (a.schedule && (a.schedule_len < 8 || a.schedule_len % 8 != 0)) return OMGX_ERR_INVALID;
+    ca.active = a.active; ca.goal_count = a.goal_count; ca.schedule = a.schedule; ca.sched_len = a.schedule ? a.schedule_len : 0; ca.work = a.work;
+    GsTiling tl = a.tiling;
+    tl.kin_ws = a.workspace;
+    return a.potentials ? launch_chunks(ca, st) : launch_goalset(ca, 0, st, tl);
 }
 
 extern "C" int omgx_goalset_cost(const double* robot, int32_t n_points, const omgx_object* objects,
@@ -1213,9 +1225,13 @@ extern "C" int omgx_goalset_cost(const double* robot, int32_t n_points, const om
                                  int32_t n_remaining,
                                  double time_interval, int32_t soften_fingers, float* goal_cost, float* potentials,
                                  float* collides, void* workspace, const int32_t* active, const int32_t* goal_count, void* stream) {
-    return goalset_cost_impl(robot, n_points, objects, scene_begin, sdf_pool, traj_start, traj_start_stride, goals, num_scenes,
-                             num_goals, n_remaining, time_interval, soften_fingers, goal_cost, potentials, collides, workspace,
-                             nullptr, 0, 0, nullptr, nullptr, nullptr, active, goal_count, nullptr, 0, nullptr, stream);
+    GoalsetCall a;
+    a.robot = robot; a.n_points = n_points; a.objects = objects; a.scene_begin = scene_begin; a.sdf_pool = sdf_pool;
+    a.traj_start = traj_start; a.traj_start_stride = traj_start_stride; a.goals = goals; a.num_scenes = num_scenes; a.num_goals = num_goals;
+    a.n_remaining = n_remaining; a.time_interval = time_interval; a.soften_fingers = soften_fingers;
+    a.goal_cost = goal_cost; a.potentials = potentials; a.collides = collides; a.workspace = workspace;
+    a.active = active; a.goal_count = goal_count; a.stream = stream;
+    return goalset_cost_impl(a);
 }
 
 // =================================================================================================
@@ -1445,10 +1461,14 @@ extern "C" int omgx_goalset_cost_layer(const double* robot, int32_t n_points, co
                                        float* layer_collides, const int32_t* active, const int32_t* goal_count,
                                        const int32_t* schedule, int32_t schedule_len, uint32_t* work, void* stream) {
     if (!traj) return OMGX_ERR_INVALID;
-    return goalset_cost_impl(robot, n_points, objects, scene_begin, sdf_pool, traj_start, traj_start_stride, goals, num_scenes,
-                             num_goals, n_remaining, time_interval, soften_fingers, goal_cost, nullptr, collides, workspace, traj,
-                             n_waypoints, layer_soften_fingers, layer_potentials, layer_grads, layer_collides, active, goal_count, schedule,
-                             schedule_len, work, stream);
+    GoalsetCall a;
+    a.robot = robot; a.n_points = n_points; a.objects = objects; a.scene_begin = scene_begin; a.sdf_pool = sdf_pool;
+    a.traj_start = traj_start; a.traj_start_stride = traj_start_stride; a.goals = goals; a.num_scenes = num_scenes; a.num_goals = num_goals;
+    a.n_remaining = n_remaining; a.time_interval = time_interval; a.soften_fingers = soften_fingers;
+    a.goal_cost = goal_cost; a.collides = collides; a.workspace = workspace;
+    a.layer_traj = traj; a.layer_n = n_waypoints; a.layer_soften = layer_soften_fingers; a.layer_pot = layer_potentials; a.layer_grad = layer_grads; a.layer_col = layer_collides;
+    a.active = active; a.goal_count = goal_count; a.schedule = schedule; a.schedule_len = schedule_len; a.work = work; a.stream = stream;
+    return goalset_cost_impl(a);
 }
 
 extern "C" int omgx_goalset_cost_layer_parts(const double* robot, int32_t n_points, const omgx_object* objects,
@@ -1461,13 +1481,15 @@ extern "C" int omgx_goalset_cost_layer_parts(const double* robot, int32_t n_poin
                                              const int32_t* schedule, int32_t schedule_len, uint32_t* work, int32_t goal_parts,
                                              double* layer_poses, void* workspace, void* stream) {
     if (!traj) return OMGX_ERR_INVALID;
-    GsTiling tl;
-    tl.goal_parts = goal_parts;
-    tl.wp_pose_out = layer_poses;
-    return goalset_cost_impl(robot, n_points, objects, scene_begin, sdf_pool, traj_start, traj_start_stride, goals, num_scenes,
-                             num_goals, n_remaining, time_interval, soften_fingers, goal_cost, nullptr, collides, workspace, traj,
-                             n_waypoints, layer_soften_fingers, layer_potentials, layer_grads, layer_collides, active, goal_count, schedule,
-                             schedule_len, work, stream, tl);
+    GoalsetCall a;
+    a.robot = robot; a.n_points = n_points; a.objects = objects; a.scene_begin = scene_begin; a.sdf_pool = sdf_pool;
+    a.traj_start = traj_start; a.traj_start_stride = traj_start_stride; a.goals = goals; a.num_scenes = num_scenes; a.num_goals = num_goals;
+    a.n_remaining = n_remaining; a.time_interval = time_interval; a.soften_fingers = soften_fingers;
+    a.goal_cost = goal_cost; a.collides = collides; a.workspace = workspace;
+    a.layer_traj = traj; a.layer_n = n_waypoints; a.layer_soften = layer_soften_fingers; a.layer_pot = layer_potentials; a.layer_grad = layer_grads; a.layer_col = layer_collides;
+    a.active = active; a.goal_count = goal_count; a.schedule = schedule; a.schedule_len = schedule_len; a.work = work; a.stream = stream;
+    a.tiling.goal_parts = goal_parts; a.tiling.wp_pose_out = layer_poses;
+    return goalset_cost_impl(a);
 }
 
 extern "C" int32_t omgx_goalset_parts(int32_t n_remaining, int32_t goal_parts) {
@@ -1485,13 +1507,16 @@ extern "C" int omgx_goalset_cost_layer_tiled(const double* robot, int32_t n_poin
                                              int32_t layer_link_groups, int32_t layer_config_block, int32_t spread, double* layer_poses,
                                              void* workspace, void* stream) {
     if (!traj && num_goals <= 0) return OMGX_ERR_INVALID;
-    GsTiling tl;
-    tl.goal_parts = goal_parts; tl.layer_lg = layer_link_groups; tl.layer_cb = layer_config_block; tl.spread = spread;
-    tl.wp_pose_out = traj ? layer_poses : nullptr;
-    return goalset_cost_impl(robot, n_points, objects, scene_begin, sdf_pool, traj_start, traj_start_stride, goals, num_scenes,
-                             num_goals, num_goals > 0 ? n_remaining : 1, time_interval, soften_fingers, goal_cost, nullptr, collides, workspace, traj,
-                             n_waypoints, layer_soften_fingers, layer_potentials, layer_grads, layer_collides, active, goal_count, nullptr,
-                             0, nullptr, stream, tl);
+    GoalsetCall a;
+    a.robot = robot; a.n_points = n_points; a.objects = objects; a.scene_begin = scene_begin; a.sdf_pool = sdf_pool;
+    a.traj_start = traj_start; a.traj_start_stride = traj_start_stride; a.goals = goals; a.num_scenes = num_scenes; a.num_goals = num_goals;
+    a.n_remaining = num_goals > 0 ? n_remaining : 1; a.time_interval = time_interval; a.soften_fingers = soften_fingers;
+    a.goal_cost = goal_cost; a.collides = collides; a.workspace = workspace;
+    a.layer_traj = traj; a.layer_n = n_waypoints; a.layer_soften = layer_soften_fingers; a.layer_pot = layer_potentials; a.layer_grad = layer_grads; a.layer_col = layer_collides;
+    a.active = active; a.goal_count = goal_count; a.stream = stream;
+    a.tiling.goal_parts = goal_parts; a.tiling.layer_lg = layer_link_groups; a.tiling.layer_cb = layer_config_block; a.tiling.spread = spread;
+    a.tiling.wp_pose_out = traj ? layer_poses : nullptr;
+    return goalset_cost_impl(a);
 }
 
 // =================================================================================================

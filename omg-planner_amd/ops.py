@@ -53,6 +53,117 @@ def _kin_workspace(prepass, S: int, G: int, n_remaining: int, P: int, device):
     return _workspace(need, device)
 
 
+def _eta(eta, S):
+    if eta is not None and not (eta.is_cuda and eta.dtype == torch.float64 and eta.is_contiguous() and eta.numel() == S):
+        raise _lib.OmgHipError("eta must be a contiguous float64 device tensor [S]")
+    return eta
+
+
+def _i32n(t, n, name):
+    """Optional contiguous 4-byte integer device tensor of n elements (int32 schedules, uint32-as-int32 work counters)."""
+    if t is not None and not (t.is_cuda and t.dtype == torch.int32 and t.is_contiguous() and (n is None or t.numel() == n)):
+        raise _lib.OmgHipError(f"{name} must be a contiguous int32 device tensor" + (f" of {n} elements" if n is not None else ""))
+    return t
+
+
+def _active(active, S):
+    if active is not None and not (active.is_cuda and active.dtype == torch.int32 and active.is_contiguous() and active.numel() == S):
+        raise _lib.OmgHipError("active must be a contiguous int32 device tensor [S]")
+    return active
+
+
+def _traj_start(traj_start):
+    """traj_start [S,9] float64, a strided row view such as traj[:, k] included -> (pointer, row stride in doubles)."""
+    if not (traj_start.is_cuda and traj_start.dtype == torch.float64 and traj_start.dim() == 2 and traj_start.shape[1] == 9
+            and traj_start.stride(1) == 1 and (traj_start.shape[0] == 1 or traj_start.stride(0) >= 9)):
+        raise _lib.OmgHipError("traj_start must be a float64 device tensor [S,9] with unit inner stride")
+    return _ptr(traj_start), traj_start.stride(0) if traj_start.shape[0] > 1 else 9
+
+
+def _layer(S: int, P: int, traj, layer_out, layer_poses=None):
+    """The trajectory layer of a launch, checked: traj [S,n,9] f64, layer_out = (potentials [S,n,10,P], grads [S,n,10,P,3], collides
+    [S,n,10,P]) f32, layer_poses [S,n,10,12] f64 or None -> pointers (traj, n, potentials, grads, collides, layer_poses).
+    traj None: a launch without the layer (layer_out is not looked at, layer_poses is an error)."""
+    n, ptrs = 0, (None, None, None)
+    if traj is not None:
+        _need(traj, torch.float64, "traj")
+        for n_, t in zip(("layer potentials", "layer grads", "layer collides"), layer_out):
+            _need(t, torch.float32, n_)
+        lp, lg, lc = layer_out
+        n = traj.shape[1]
+        if traj.shape[0] != S or lp.numel() != S * n * 10 * P or lg.numel() != 3 * lp.numel() or lc.numel() != lp.numel():
+            raise _lib.OmgHipError("layer outputs must be [S,n,10,P], [S,n,10,P,3], [S,n,10,P]")
+        ptrs = (_ptr(lp), _ptr(lg), _ptr(lc))
+    if layer_poses is not None:
+        _need(layer_poses, torch.float64, "layer_poses")
+        if traj is None or layer_poses.numel() != S * n * 120:
+            raise _lib.OmgHipError("layer_poses must be [S,n,10,12] and needs the trajectory layer")
+    return (_ptr(traj), n, *ptrs, _ptr(layer_poses))
+
+
+def _goal_out(goal_out, need: int):
+    """(goal_cost, collides) f32 of at least `need` = S * G * parts elements each, checked -> their pointers."""
+    for n_, t in zip(("goal_cost", "goal collides"), goal_out):
+        _need(t, torch.float32, n_)
+        if t.numel() < need:
+            raise _lib.OmgHipError(f"{n_} must hold S * G * parts = {need} elements")
+    return _ptr(goal_out[0]), _ptr(goal_out[1])
+
+
+def _iteration_tensors(S: int, goal_set, reach, state, goal_idx, cost_vector, start, end, goal_rows, goal_point, step_out, active, goal_count,
+                       eta, scene_flags=None):
+    """The learner's and the step's tensors of an iteration (omgx_goal_update_optimize, omgx_plan_persistent), checked: all but the
+    trajectory and its layer (`_layer`) and the goal costs (`_goal_out`)."""
+    for n_, t in (("goal_set", goal_set), ("state", state), ("start", start), ("end", end), ("goal", goal_rows), ("goal_point", goal_point),
+                  *zip(("grad", "cost_traj", "info"), step_out)):
+        _need(t, torch.float64, n_)
+    for n_, t in (("reach", reach), ("cost_vector", cost_vector)):
+        if t is not None:
+            _need(t, torch.float64, n_)
+    if goal_idx.dtype != torch.int32 or not goal_idx.is_cuda or goal_idx.numel() != S:
+        raise _lib.OmgHipError("goal_idx must be an int32 device tensor [S]")
+    if scene_flags is not None and (scene_flags.dtype != torch.int32 or scene_flags.numel() < S or not scene_flags.is_cuda):
+        raise _lib.OmgHipError("scene_flags must be an int32 device tensor [S]")
+    _active(active, S); _active(goal_count, S); _eta(eta, S)
+
+
+def _schedule_args(schedule, work, items: int):
+    """(schedule, schedule_len, work) of a goal-set launch over `items` workgroups: checked int32 device tensors or None."""
+    work = None if work is None else _ptr(_i32n(work, items, "work"))
+    if schedule is None:
+        return None, 0, work
+    return _ptr(_i32n(schedule, None, "schedule")), schedule.numel(), work
+
+
+class _GoalsetArgs:
+    """The argument lists of omgx_goalset_cost_layer, _parts and _tiled from one set of checked pointers.  The three entry points
+    share robot .. goal collides and traj .. goal_count; they differ in where the pre-pass workspace goes and in what follows
+    goal_count, which is what their methods below add.  start = (traj_start, its row stride), active and stream change per launch."""
+
+    def __init__(self, robot, P, scenes: "DeviceScenes", goals, S, G, dt, soften_fingers, goal_out, layer, layer_soften_fingers, goal_count, kin_ws):
+        traj, n, lp, lg, lc, self.poses = layer
+        self.scene = (_ptr(robot), int(P), _ptr(scenes.objects), _ptr(scenes.scene_begin), _ptr(scenes.pool))
+        self.goals = (_ptr(goals), S, G)
+        self.cost = (float(dt), int(bool(soften_fingers)), *goal_out)
+        self.layer = (traj, n, int(bool(layer_soften_fingers)), lp, lg, lc)
+        self.items, self.goal_count, self.ws = S * G, _ptr(goal_count), _ptr(kin_ws)
+
+    def _args(self, start, n_remaining, ws, active, tail, stream):
+        return (*self.scene, *start, *self.goals, n_remaining, *self.cost, *ws, *self.layer, active, self.goal_count, *tail, stream)
+
+    def whole(self, start, n_remaining, active, schedule, work, stream):
+        """omgx_goalset_cost_layer: the workspace after the goal outputs, the dispatch schedule last."""
+        return self._args(start, n_remaining, (self.ws,), active, _schedule_args(schedule, work, self.items), stream)
+
+    def parts(self, start, n_remaining, active, schedule, work, NP, goal_parts, poses, stream):
+        """omgx_goalset_cost_layer_parts: the schedule over the (scene, goal, part) items, then goal_parts, layer_poses, workspace."""
+        return self._args(start, n_remaining, (), active, (*_schedule_args(schedule, work, self.items * NP), goal_parts, poses, self.ws), stream)
+
+    def tiled(self, start, n_remaining, active, tiling, poses, stream):
+        """omgx_goalset_cost_layer_tiled: (goal_parts, layer_link_groups, layer_config_block, spread), then layer_poses, workspace."""
+        return self._args(start, n_remaining, (), active, (*tiling, poses, self.ws), stream)
+
+
 def sdf_loss_forward(pose_init, sdf_grids, sdf_limits, points, epsilons, padding_scales, clearances, disables):
     """omg_cuda.sdf_loss_forward (layers/omg_layers.cpp:24-49): -> [potentials[N], potential_grads[N,3], collides[N]]."""
     for n, t in (("pose_init", pose_init), ("sdf_grids", sdf_grids), ("sdf_limits", sdf_limits), ("points", points),
@@ -368,10 +479,7 @@ def goalset_cost(robot, P, scenes: DeviceScenes, traj_start, goals, n_remaining,
     goal set are skipped; their outputs keep their previous contents.
     prepass: the goals' kinematics and row masks as a launch of their own (k_goalset_kin, ABI 10) through a scratch workspace
     — same bits, two launches; a torch tensor of omgx_goalset_workspace_bytes is taken as that workspace."""
-    if not (traj_start.is_cuda and traj_start.dtype == torch.float64 and traj_start.dim() == 2 and traj_start.shape[1] == 9
-            and traj_start.stride(1) == 1 and (traj_start.shape[0] == 1 or traj_start.stride(0) >= 9)):
-        raise _lib.OmgHipError("traj_start must be a float64 device tensor [S,9] with unit inner stride")
-    ts_stride = traj_start.stride(0) if traj_start.shape[0] > 1 else 9
+    ts, ts_stride = _traj_start(traj_start)
     _need(goals, torch.float64, "goals")
     S, G = goals.shape[0], goals.shape[1]
     dev = goals.device
@@ -381,12 +489,13 @@ def goalset_cost(robot, P, scenes: DeviceScenes, traj_start, goals, n_remaining,
     else:
         cost, col = out
     pots = torch.empty((S, G, n_remaining, 10, P), dtype=torch.float32, device=dev) if want_potentials else None
+    cost_p, col_p = _goal_out((cost, col), S * G)
     l = _lib.lib()
     with torch.cuda.device(dev):
         ws = _kin_workspace(prepass, S, G, n_remaining, P, dev) if not want_potentials else None
         check(l.omgx_goalset_cost(_ptr(robot), P, _ptr(scenes.objects), _ptr(scenes.scene_begin), _ptr(scenes.pool),
-                                  _ptr(traj_start), ts_stride, _ptr(goals), S, G, n_remaining, float(dt), int(bool(soften_fingers)),
-                                  _ptr(cost), _ptr(pots), _ptr(col), _ptr(ws), _ptr(_active(active, S)), _ptr(_active(goal_count, S)),
+                                  ts, ts_stride, _ptr(goals), S, G, n_remaining, float(dt), int(bool(soften_fingers)),
+                                  cost_p, _ptr(pots), col_p, _ptr(ws), _ptr(_active(active, S)), _ptr(_active(goal_count, S)),
                                   _stream()), "omgx_goalset_cost")
     return cost, col, pots
 
@@ -400,18 +509,10 @@ def goalset_cost_layer(robot, P, scenes: DeviceScenes, traj_start, goals, n_rema
     goal_parts > 1 (omgx_goalset_cost_layer_parts): a goal's tiles dealt over NP = goalset_parts(n_remaining, goal_parts) workgroups
     of the batch kernel; `out` must then hold S * G * NP elements each and receives [S][G][NP] PARTIAL sums, schedule / work count
     the S * G * NP (scene, goal, part) items.  prepass: see goalset_cost.  Returns (cost, collides) as given / allocated."""
-    if not (traj_start.is_cuda and traj_start.dtype == torch.float64 and traj_start.dim() == 2 and traj_start.shape[1] == 9
-            and traj_start.stride(1) == 1 and (traj_start.shape[0] == 1 or traj_start.stride(0) >= 9)):
-        raise _lib.OmgHipError("traj_start must be a float64 device tensor [S,9] with unit inner stride")
-    ts_stride = traj_start.stride(0) if traj_start.shape[0] > 1 else 9
+    start = _traj_start(traj_start)
     _need(goals, torch.float64, "goals")
-    _need(traj, torch.float64, "traj")
-    lp, lg, lc = layer_out
-    for n_, t in (("layer potentials", lp), ("layer grads", lg), ("layer collides", lc)):
-        _need(t, torch.float32, n_)
-    S, G, n = goals.shape[0], goals.shape[1], traj.shape[1]
-    if traj.shape[0] != S or lp.numel() != S * n * 10 * P or lg.numel() != 3 * lp.numel() or lc.numel() != lp.numel():
-        raise _lib.OmgHipError("layer outputs must be [S,n,10,P], [S,n,10,P,3], [S,n,10,P]")
+    S, G = goals.shape[0], goals.shape[1]
+    layer = _layer(S, P, traj, layer_out, layer_poses)
     dev = goals.device
     NP = goalset_parts(n_remaining, goal_parts) if int(goal_parts) != 1 else 1
     if NP < 1:
@@ -422,35 +523,15 @@ def goalset_cost_layer(robot, P, scenes: DeviceScenes, traj_start, goals, n_rema
     else:
         cost, col = out
     l = _lib.lib()
-    if int(goal_parts) != 1 or layer_poses is not None:
-        for n_, t in (("goal_cost", cost), ("goal collides", col)):
-            _need(t, torch.float32, n_)
-            if t.numel() < S * G * NP:
-                raise _lib.OmgHipError(f"{n_} must hold S * G * parts = {S * G * NP} elements")
-        if layer_poses is not None:
-            _need(layer_poses, torch.float64, "layer_poses")
-            if layer_poses.numel() != S * n * 120:
-                raise _lib.OmgHipError("layer_poses must be [S,n,10,12]")
-        with torch.cuda.device(dev):
-            check(l.omgx_goalset_cost_layer_parts(_ptr(robot), P, _ptr(scenes.objects), _ptr(scenes.scene_begin), _ptr(scenes.pool),
-                                                  _ptr(traj_start), ts_stride, _ptr(goals), S, G, n_remaining, float(dt),
-                                                  int(bool(soften_fingers)), _ptr(cost), _ptr(col), _ptr(traj), n,
-                                                  int(bool(layer_soften_fingers)), _ptr(lp), _ptr(lg), _ptr(lc), _ptr(_active(active, S)),
-                                                  _ptr(_active(goal_count, S)), _ptr(_i32n(schedule, None, "schedule")),
-                                                  0 if schedule is None else schedule.numel(), _ptr(_i32n(work, S * G * NP, "work")),
-                                                  int(goal_parts), _ptr(layer_poses), _ptr(_kin_workspace(prepass, S, G, n_remaining, P, dev)),
-                                                  _stream()),
-                  "omgx_goalset_cost_layer_parts")
-        return cost, col
     with torch.cuda.device(dev):
-        ws = _kin_workspace(prepass, S, G, n_remaining, P, dev)
-        check(l.omgx_goalset_cost_layer(_ptr(robot), P, _ptr(scenes.objects), _ptr(scenes.scene_begin), _ptr(scenes.pool),
-                                        _ptr(traj_start), ts_stride, _ptr(goals), S, G, n_remaining, float(dt),
-                                        int(bool(soften_fingers)), _ptr(cost), _ptr(col), _ptr(ws), _ptr(traj), n,
-                                        int(bool(layer_soften_fingers)), _ptr(lp), _ptr(lg), _ptr(lc), _ptr(_active(active, S)),
-                                        _ptr(_active(goal_count, S)), _ptr(_i32n(schedule, None, "schedule")), 0 if schedule is None else schedule.numel(), _ptr(_i32n(work, S * G, "work")),
-                                        _stream()),
-              "omgx_goalset_cost_layer")
+        g = _GoalsetArgs(robot, P, scenes, goals, S, G, dt, soften_fingers, _goal_out((cost, col), S * G * NP), layer, layer_soften_fingers,
+                         _active(goal_count, S), _kin_workspace(prepass, S, G, n_remaining, P, dev))
+        active = _ptr(_active(active, S))
+        if int(goal_parts) != 1 or layer_poses is not None:
+            check(l.omgx_goalset_cost_layer_parts(*g.parts(start, n_remaining, active, schedule, work, NP, int(goal_parts), g.poses, _stream())),
+                  "omgx_goalset_cost_layer_parts")
+        else:
+            check(l.omgx_goalset_cost_layer(*g.whole(start, n_remaining, active, schedule, work, _stream())), "omgx_goalset_cost_layer")
     return cost, col
 
 
@@ -469,45 +550,24 @@ def goalset_cost_layer_tiled(robot, P, scenes: DeviceScenes, traj_start, goals, 
     poses (ChompParams.waypoint_poses of the step that follows).  Returns the number of parts per goal."""
     dev = (goals if goals is not None else traj).device
     S = (goals if goals is not None else traj).shape[0]
-    G, ts_stride, parts = 0, 9, 1
-    cost = col = None
+    G, start, parts, goal_out = 0, (None, 9), 1, (None, None)
     if goals is not None:
-        if not (traj_start.is_cuda and traj_start.dtype == torch.float64 and traj_start.dim() == 2 and traj_start.shape[1] == 9
-                and traj_start.stride(1) == 1 and (traj_start.shape[0] == 1 or traj_start.stride(0) >= 9)):
-            raise _lib.OmgHipError("traj_start must be a float64 device tensor [S,9] with unit inner stride")
-        ts_stride = traj_start.stride(0) if traj_start.shape[0] > 1 else 9
+        start = _traj_start(traj_start)
         _need(goals, torch.float64, "goals")
         G = goals.shape[1]
         parts = goalset_parts(n_remaining, goal_parts)
         if parts < 1:
             raise _lib.OmgHipError("goal_parts must be 1, 2, 4 or 8")
-        cost, col = out
-        for n_, t in (("goal_cost", cost), ("goal collides", col)):
-            _need(t, torch.float32, n_)
-            if t.numel() < S * G * parts:
-                raise _lib.OmgHipError(f"{n_} must hold S * G * parts = {S * G * parts} elements")
-    lp = lg = lc = None
-    n = 0
-    if layer_poses is not None:
-        _need(layer_poses, torch.float64, "layer_poses")
-        if traj is None or layer_poses.numel() != S * traj.shape[1] * 120:
-            raise _lib.OmgHipError("layer_poses must be [S,n,10,12] and needs the trajectory layer")
-    if traj is not None:
-        _need(traj, torch.float64, "traj")
-        lp, lg, lc = layer_out
-        for n_, t in (("layer potentials", lp), ("layer grads", lg), ("layer collides", lc)):
-            _need(t, torch.float32, n_)
-        n = traj.shape[1]
-        if traj.shape[0] != S or lp.numel() != S * n * 10 * P or lg.numel() != 3 * lp.numel() or lc.numel() != lp.numel():
-            raise _lib.OmgHipError("layer outputs must be [S,n,10,P], [S,n,10,P,3], [S,n,10,P]")
+        goal_out = _goal_out(out, S * G * parts)
+    else:
+        n_remaining, prepass = 1, None
+    layer = _layer(S, P, traj, layer_out, layer_poses)
     with torch.cuda.device(dev):
-        check(_lib.lib().omgx_goalset_cost_layer_tiled(
-            _ptr(robot), P, _ptr(scenes.objects), _ptr(scenes.scene_begin), _ptr(scenes.pool), _ptr(traj_start) if goals is not None else None,
-            ts_stride, _ptr(goals), S, G, int(n_remaining) if goals is not None else 1, float(dt), int(bool(soften_fingers)), _ptr(cost), _ptr(col),
-            _ptr(traj), n, int(bool(layer_soften_fingers)), _ptr(lp), _ptr(lg), _ptr(lc), _ptr(_active(active, S)),
-            _ptr(_active(goal_count, S)), int(goal_parts), int(layer_link_groups), int(layer_config_block), int(bool(spread)),
-            _ptr(layer_poses), _ptr(_kin_workspace(prepass, S, G, n_remaining, P, dev) if goals is not None else None), _stream()),
-            "omgx_goalset_cost_layer_tiled")
+        g = _GoalsetArgs(robot, P, scenes, goals, S, G, dt, soften_fingers, goal_out, layer, layer_soften_fingers, _active(goal_count, S),
+                         _kin_workspace(prepass, S, G, n_remaining, P, dev))
+        tiling = (int(goal_parts), int(layer_link_groups), int(layer_config_block), int(bool(spread)))
+        check(_lib.lib().omgx_goalset_cost_layer_tiled(*g.tiled(start, int(n_remaining), _ptr(_active(active, S)), tiling, g.poses, _stream())),
+              "omgx_goalset_cost_layer_tiled")
     return parts
 
 
@@ -695,25 +755,6 @@ def learner_state(S: int, G: int, device, goal_count=None) -> torch.Tensor:
     return torch.from_numpy(st).to(device)
 
 
-def _eta(eta, S):
-    if eta is not None and not (eta.is_cuda and eta.dtype == torch.float64 and eta.is_contiguous() and eta.numel() == S):
-        raise _lib.OmgHipError("eta must be a contiguous float64 device tensor [S]")
-    return eta
-
-
-def _i32n(t, n, name):
-    """Optional contiguous 4-byte integer device tensor of n elements (int32 schedules, uint32-as-int32 work counters)."""
-    if t is not None and not (t.is_cuda and t.dtype == torch.int32 and t.is_contiguous() and (n is None or t.numel() == n)):
-        raise _lib.OmgHipError(f"{name} must be a contiguous int32 device tensor" + (f" of {n} elements" if n is not None else ""))
-    return t
-
-
-def _active(active, S):
-    if active is not None and not (active.is_cuda and active.dtype == torch.int32 and active.is_contiguous() and active.numel() == S):
-        raise _lib.OmgHipError("active must be a contiguous int32 device tensor [S]")
-    return active
-
-
 def goal_update(params: LearnerParams, traj, goal_set, reach, goal_cost, state, goal_idx, end, goal_rows, goal_point,
                 cost_vector=None, active=None, goal_count=None, eta=None):
     """Learner.update_goal for S scenes in one launch (omgx_goal_update); all outputs are written in place.
@@ -734,15 +775,6 @@ def goal_update_optimize(lparams: LearnerParams, goal_set, reach, goal_cost, sta
                          start, end, goal, goal_point, pot, pgrad, col, active=None, out=None, aux=None, cost_vector=None,
                          scene_flags=None, ticket=0, stop_on_terminate=False, goal_count=None, eta=None):
     """goal_update followed by chomp_optimize in one launch (omgx_goal_update_optimize): same results as the two calls."""
-    for n_, t in (("traj", traj), ("start", start), ("end", end), ("goal", goal), ("goal_point", goal_point),
-                  ("goal_set", goal_set), ("state", state)):
-        _need(t, torch.float64, n_)
-    for n_, t in (("potentials", pot), ("grads", pgrad), ("collides", col)):
-        _need(t, torch.float32, n_)
-    if goal_idx.dtype != torch.int32:
-        raise _lib.OmgHipError("goal_idx must be int32")
-    if scene_flags is not None and (scene_flags.dtype != torch.int32 or scene_flags.numel() < traj.shape[0] or not scene_flags.is_cuda):
-        raise _lib.OmgHipError("scene_flags must be an int32 device tensor [S]")
     S, n = traj.shape[0], traj.shape[1]
     dev = traj.device
     if out is None:
@@ -751,13 +783,16 @@ def goal_update_optimize(lparams: LearnerParams, goal_set, reach, goal_cost, sta
         info = torch.zeros((S, _lib.INFO_STRIDE), dtype=torch.float64, device=dev)
     else:
         grad, cost_traj, info = out
+    _layer(S, params.n_points, traj, (pot, pgrad, col))
+    _iteration_tensors(S, goal_set, reach, state, goal_idx, cost_vector, start, end, goal, goal_point, (grad, cost_traj, info), active,
+                       goal_count, eta, scene_flags)
     with torch.cuda.device(dev):
         check(_lib.lib().omgx_goal_update_optimize(C.byref(lparams), _ptr(goal_set), _ptr(reach), _ptr(goal_cost), _ptr(state),
                                                    _ptr(goal_idx), _ptr(cost_vector), _ptr(robot), C.byref(params), _ptr(traj),
                                                    _ptr(start), _ptr(end), _ptr(goal), _ptr(goal_point), _ptr(pot), _ptr(pgrad),
                                                    _ptr(col), _ptr(active), S, _ptr(grad), _ptr(cost_traj), _ptr(info), _ptr(aux),
                                                    _ptr(scene_flags), int(ticket), int(bool(stop_on_terminate)),
-                                                   _ptr(_active(goal_count, S)), _ptr(_eta(eta, S)), _stream()),
+                                                   _ptr(goal_count), _ptr(eta), _stream()),
               "omgx_goal_update_optimize")
     return grad, cost_traj, info
 
@@ -773,39 +808,19 @@ class IterationCalls:
     def __init__(self, robot, P, scenes: DeviceScenes, goals, dt, traj, layer_out, goal_out, goal_set, reach, state, goal_idx,
                  start, end, goal_rows, goal_point, step_out, cost_vector, active, goal_count=None, eta=None, scene_flags=None,
                  layer_soften_fingers=False, tiling=None, layer_poses=None, goal_parts=1, prepass=False):
-        lp, lg, lc = layer_out
-        cost, col = goal_out
-        grad, cost_traj, info = step_out
-        for n_, t in (("goals", goals), ("traj", traj), ("goal_set", goal_set), ("state", state), ("start", start), ("end", end),
-                      ("goal", goal_rows), ("goal_point", goal_point), ("grad", grad), ("cost_traj", cost_traj), ("info", info),
-                      ("cost_vector", cost_vector)):
-            _need(t, torch.float64, n_)
-        if reach is not None:
-            _need(reach, torch.float64, "reach")
-        for n_, t in (("layer potentials", lp), ("layer grads", lg), ("layer collides", lc), ("goal_cost", cost), ("goal collides", col)):
-            _need(t, torch.float32, n_)
-        S, G, n = goals.shape[0], goals.shape[1], traj.shape[1]
-        if traj.shape[0] != S or lp.numel() != S * n * 10 * P or lg.numel() != 3 * lp.numel() or lc.numel() != lp.numel():
-            raise _lib.OmgHipError("layer outputs must be [S,n,10,P], [S,n,10,P,3], [S,n,10,P]")
+        _need(goals, torch.float64, "goals")
+        S, G = goals.shape[0], goals.shape[1]
+        layer = _layer(S, P, traj, layer_out, layer_poses)
+        n = layer[1]
         # tiling = (goal_parts, layer_link_groups, layer_config_block, spread): the launches go through omgx_goalset_cost_layer_tiled
         # (latency mode), goal_cost / collides then hold [S][G][parts] partial sums
         self._tiling = None if tiling is None else tuple(int(v) for v in tiling)
         # goal_parts > 1 without a tiling: the batch kernel with split goals (omgx_goalset_cost_layer_parts), schedules over (scene, goal, part)
         self._goal_parts = int(goal_parts) if self._tiling is None else 1
-        if layer_poses is not None:
-            _need(layer_poses, torch.float64, "layer_poses")
-            if layer_poses.numel() != S * n * 120:
-                raise _lib.OmgHipError("layer_poses must be [S,n,10,12]")
-        self._layer_poses = _ptr(layer_poses)
-        if self._tiling is not None or self._goal_parts > 1:
-            need = S * G * goalset_parts(n, self._tiling[0] if self._tiling is not None else self._goal_parts)
-            if cost.numel() < need or col.numel() < need:
-                raise _lib.OmgHipError(f"goal_cost / collides must hold S * G * parts = {need} elements")
-        if goal_idx.dtype != torch.int32 or not goal_idx.is_cuda or goal_idx.numel() != S:
-            raise _lib.OmgHipError("goal_idx must be an int32 device tensor [S]")
-        if scene_flags is not None and (scene_flags.dtype != torch.int32 or scene_flags.numel() < S or not scene_flags.is_cuda):
-            raise _lib.OmgHipError("scene_flags must be an int32 device tensor [S]")
-        _active(active, S); _active(goal_count, S); _eta(eta, S)
+        max_parts = self._tiling[0] if self._tiling is not None else self._goal_parts
+        goal_ptrs = _goal_out(goal_out, S * G * (goalset_parts(n, max_parts) if max_parts != 1 else 1))
+        _iteration_tensors(S, goal_set, reach, state, goal_idx, cost_vector, start, end, goal_rows, goal_point, step_out, active, goal_count,
+                           eta, scene_flags)
         self.S, self.G, self.n, self.P, self.dt = S, G, n, int(P), float(dt)
         self.device = traj.device
         self._dev_index = traj.device.index if traj.device.index is not None else torch.cuda.current_device()
@@ -814,71 +829,42 @@ class IterationCalls:
         self._f_gs, self._f_up = l.omgx_goalset_cost_layer, l.omgx_goal_update_optimize
         self._f_gst = l.omgx_goalset_cost_layer_tiled
         self._f_gsp = l.omgx_goalset_cost_layer_parts
-        self._layer_soft = int(bool(layer_soften_fingers))
-        p = _ptr
-        self._gs_head = (p(robot), self.P, p(scenes.objects), p(scenes.scene_begin), p(scenes.pool))
         # prepass: the goals' kinematics as a launch of their own (k_goalset_kin) through a workspace this object owns — launches of
         # different IterationCalls may run at once on different streams
         self.kin_workspace = (torch.empty(max(16, l.omgx_goalset_workspace_bytes(S, G, n, self.P)), dtype=torch.uint8, device=traj.device)
                               if prepass else None)
-        self._kin_ws = p(self.kin_workspace)
-        self._gs_mid = (p(cost), p(col), self._kin_ws, p(traj), n, self._layer_soft, p(lp), p(lg), p(lc))
-        self._goals, self._active_p, self._goal_count = p(goals), p(active), p(goal_count)
-        self._up_a = (p(goal_set), p(reach), p(cost), p(state), p(goal_idx), p(cost_vector), p(robot))
-        self._up_b = (p(traj), p(start), p(end), p(goal_rows), p(goal_point), p(lp), p(lg), p(lc), p(active), S, p(grad), p(cost_traj),
-                      p(info), None)
+        self._gs = _GoalsetArgs(robot, P, scenes, goals, S, G, dt, False, goal_ptrs, layer, layer_soften_fingers, goal_count, self.kin_workspace)
+        self._layer_alone = _GoalsetArgs(robot, P, scenes, None, S, 0, dt, False, (None, None), layer, layer_soften_fingers, None, None)
+        p = _ptr
+        self._active_p = p(active)
+        traj_p, _n, lp, lg, lc, _poses = layer
+        grad, cost_traj, info = step_out
+        self._up_a = (p(goal_set), p(reach), goal_ptrs[0], p(state), p(goal_idx), p(cost_vector), p(robot))
+        self._up_b = (traj_p, p(start), p(end), p(goal_rows), p(goal_point), lp, lg, lc, p(active), S, p(grad), p(cost_traj), p(info), None)
         self._flags, self._eta = p(scene_flags), p(eta)
         self.use_layer_poses = False  # set per launch by the owner: only while the step that follows takes the poses
-
-    def _on_device(self):
-        return torch.cuda.current_device() == self._dev_index
 
     def goalset_layer(self, start_idx: int, masked: bool, schedule, work, stream):
         """omgx_goalset_cost_layer for traj_start = traj[:, start_idx], n_remaining = n - start_idx.  schedule / work: checked
         int32 device tensors or None; stream: a HIP stream handle (int)."""
+        g, start, n_remaining = self._gs, (C.c_void_p(self._traj_addr + 72 * start_idx), self.n * 9), self.n - start_idx
+        active, poses, stream = self._active_p if masked else None, g.poses if self.use_layer_poses else None, C.c_void_p(stream)
         if self._tiling is not None:
             if schedule is not None or work is not None:
                 raise _lib.OmgHipError("a tiled goal-set launch takes no dispatch schedule")
-            cost, col, _ws, traj, n, soft, lp, lg, lc = self._gs_mid
-            args = (*self._gs_head, C.c_void_p(self._traj_addr + 72 * start_idx), self.n * 9, self._goals, self.S, self.G,
-                    self.n - start_idx, self.dt, 0, cost, col, traj, n, soft, lp, lg, lc, self._active_p if masked else None,
-                    self._goal_count, *self._tiling, self._layer_poses if self.use_layer_poses else None, self._kin_ws, C.c_void_p(stream))
-            if self._on_device():
-                check(self._f_gst(*args), "omgx_goalset_cost_layer_tiled")
-            else:
-                with torch.cuda.device(self.device):
-                    check(self._f_gst(*args), "omgx_goalset_cost_layer_tiled")
-            return
-        if self._goal_parts > 1 or self.use_layer_poses:
-            cost, col, _ws, traj, n, soft, lp, lg, lc = self._gs_mid
-            NP = goalset_parts(self.n - start_idx, self._goal_parts) if self._goal_parts > 1 else 1
-            args = (*self._gs_head, C.c_void_p(self._traj_addr + 72 * start_idx), self.n * 9, self._goals, self.S, self.G,
-                    self.n - start_idx, self.dt, 0, cost, col, traj, n, soft, lp, lg, lc, self._active_p if masked else None,
-                    self._goal_count, _ptr(_i32n(schedule, None, "schedule")), 0 if schedule is None else schedule.numel(),
-                    _ptr(_i32n(work, self.S * self.G * NP, "work")), self._goal_parts, self._layer_poses if self.use_layer_poses else None,
-                    self._kin_ws, C.c_void_p(stream))
-            if self._on_device():
-                check(self._f_gsp(*args), "omgx_goalset_cost_layer_parts")
-            else:
-                with torch.cuda.device(self.device):
-                    check(self._f_gsp(*args), "omgx_goalset_cost_layer_parts")
-            return
-        args = (*self._gs_head, C.c_void_p(self._traj_addr + 72 * start_idx), self.n * 9, self._goals, self.S, self.G,
-                self.n - start_idx, self.dt, 0, *self._gs_mid, self._active_p if masked else None, self._goal_count,
-                _ptr(_i32n(schedule, None, "schedule")), 0 if schedule is None else schedule.numel(), _ptr(_i32n(work, self.S * self.G, "work")),
-                C.c_void_p(stream))
-        if self._on_device():
-            check(self._f_gs(*args), "omgx_goalset_cost_layer")
+            self._call(self._f_gst, g.tiled(start, n_remaining, active, self._tiling, poses, stream))
+        elif self._goal_parts > 1 or self.use_layer_poses:
+            NP = goalset_parts(n_remaining, self._goal_parts) if self._goal_parts > 1 else 1
+            self._call(self._f_gsp, g.parts(start, n_remaining, active, schedule, work, NP, self._goal_parts, poses, stream))
         else:
-            with torch.cuda.device(self.device):
-                check(self._f_gs(*args), "omgx_goalset_cost_layer")
+            self._call(self._f_gs, g.whole(start, n_remaining, active, schedule, work, stream))
 
-    def _call(self, fn, args, what):
-        if self._on_device():
-            check(fn(*args), what)
+    def _call(self, fn, args):
+        if torch.cuda.current_device() == self._dev_index:
+            check(fn(*args), fn.__name__)
         else:
             with torch.cuda.device(self.device):
-                check(fn(*args), what)
+                check(fn(*args), fn.__name__)
 
     # (goal_parts, layer_link_groups, layer_config_block, spread) of a layer-ONLY launch in the batch layout (the smoothing iterations of a
     # plan): any split gives the same bits (every element is computed on its own).  Five workgroups per scene (2 links x all waypoints)
@@ -902,37 +888,31 @@ class IterationCalls:
     def layer_only(self, stream):
         """The SDF layer of the current trajectories alone (omgx_goalset_cost_layer_tiled with num_goals = 0): what omgx_fk_sdf
         computes for the step, with this object's tiling (latency mode) or five workgroups per scene (batch layout)."""
-        cost, col, _ws, traj, n, soft, lp, lg, lc = self._gs_mid
+        g = self._layer_alone
         tl = self._tiling if self._tiling is not None else self._layer_only_tiling()
-        args = (*self._gs_head, None, 9, None, self.S, 0, 1, self.dt, 0, None, None, traj, n, soft, lp, lg, lc, None, None, *tl,
-                self._layer_poses if self.use_layer_poses else None, None, C.c_void_p(stream))
-        self._call(self._f_gst, args, "omgx_goalset_cost_layer_tiled")
+        self._call(self._f_gst, g.tiled((None, 9), 1, None, tl, g.poses if self.use_layer_poses else None, C.c_void_p(stream)))
 
     def step(self, params: ChompParams, stop_on_terminate: bool, stream):
         """omgx_chomp_optimize on the layer outputs this object's launches write."""
-        robot = self._gs_head[0]
+        robot = self._up_a[6]
         traj, start, end, goal_rows, goal_point, lp, lg, lc, active, S, grad, cost_traj, info, _aux = self._up_b
         args = (robot, C.byref(params), traj, start, end, goal_rows, goal_point, lp, lg, lc, active, S, grad, cost_traj, info, None,
                 int(bool(stop_on_terminate)), C.c_void_p(stream))
-        self._call(_lib.lib().omgx_chomp_optimize, args, "omgx_chomp_optimize")
+        self._call(_lib.lib().omgx_chomp_optimize, args)
 
     def goal_update(self, lparams: LearnerParams, stream):
         """omgx_goal_update alone (the learner without the step) on the goal costs the last goalset_layer() left."""
         goal_set, reach, cost, state, goal_idx, cost_vector, _robot = self._up_a
         traj, _start, end, goal_rows, goal_point = self._up_b[:5]
         args = (C.byref(lparams), traj, goal_set, reach, cost, state, self.S, goal_idx, end, goal_rows, goal_point, cost_vector,
-                None, self._goal_count, self._eta, C.c_void_p(stream))
-        self._call(_lib.lib().omgx_goal_update, args, "omgx_goal_update")
+                None, self._gs.goal_count, self._eta, C.c_void_p(stream))
+        self._call(_lib.lib().omgx_goal_update, args)
 
     def update(self, lparams: LearnerParams, params: ChompParams, split: bool, ticket: int, stop_on_terminate: bool, stream):
         """omgx_goal_update_optimize."""
         args = (C.byref(lparams), *self._up_a, C.byref(params), *self._up_b, self._flags if split else None, int(ticket),
-                int(bool(stop_on_terminate)), self._goal_count, self._eta, C.c_void_p(stream))
-        if self._on_device():
-            check(self._f_up(*args), "omgx_goal_update_optimize")
-        else:
-            with torch.cuda.device(self.device):
-                check(self._f_up(*args), "omgx_goal_update_optimize")
+                int(bool(stop_on_terminate)), self._gs.goal_count, self._eta, C.c_void_p(stream))
+        self._call(self._f_up, args)
 
 
 def plan_persistent(robot, P, scenes: DeviceScenes, goals, dt, traj, layer_out, layer_poses, goal_out, lparams: LearnerParams, goal_set, reach,
@@ -943,27 +923,14 @@ def plan_persistent(robot, P, scenes: DeviceScenes, goals, dt, traj, layer_out, 
     same bytes; workspace: uint8 device tensor of omgx_plan_persistent_workspace_bytes(S, n).  The same tensors as
     goalset_cost_layer() + goal_update_optimize(); the pose hand-over (params.start_poses / end_poses, lparams.goal_pose_table /
     end_poses_out, layer_poses) is required."""
-    lp, lg, lc = layer_out
-    cost, col = goal_out
+    _need(goals, torch.float64, "goals")
+    S, G = goals.shape[0], goals.shape[1]
+    if layer_poses is None:
+        raise _lib.OmgHipError("plan_persistent needs layer_poses (the pose hand-over)")
+    traj_p, n, lp, lg, lc, poses = _layer(S, P, traj, layer_out, layer_poses)
+    cost, col = _goal_out(goal_out, S * G)
+    _iteration_tensors(S, goal_set, reach, state, goal_idx, cost_vector, start, end, goal_rows, goal_point, step_out, active, goal_count, eta)
     grad, cost_traj, info = step_out
-    for n_, t in (("goals", goals), ("traj", traj), ("goal_set", goal_set), ("state", state), ("start", start), ("end", end),
-                  ("goal", goal_rows), ("goal_point", goal_point), ("grad", grad), ("cost_traj", cost_traj), ("info", info),
-                  ("layer_poses", layer_poses)):
-        _need(t, torch.float64, n_)
-    if reach is not None:
-        _need(reach, torch.float64, "reach")
-    if cost_vector is not None:
-        _need(cost_vector, torch.float64, "cost_vector")
-    for n_, t in (("layer potentials", lp), ("layer grads", lg), ("layer collides", lc), ("goal_cost", cost), ("goal collides", col)):
-        _need(t, torch.float32, n_)
-    S, G, n = goals.shape[0], goals.shape[1], traj.shape[1]
-    if traj.shape[0] != S or lp.numel() != S * n * 10 * P or lg.numel() != 3 * lp.numel() or lc.numel() != lp.numel() or layer_poses.numel() != S * n * 120:
-        raise _lib.OmgHipError("layer outputs must be [S,n,10,P], [S,n,10,P,3], [S,n,10,P], layer_poses [S,n,10,12]")
-    if cost.numel() < S * G or col.numel() < S * G:
-        raise _lib.OmgHipError("goal_cost / collides must hold S * G elements")
-    if goal_idx.dtype != torch.int32 or not goal_idx.is_cuda or goal_idx.numel() != S:
-        raise _lib.OmgHipError("goal_idx must be an int32 device tensor [S]")
-    _active(active, S); _active(goal_count, S); _eta(eta, S)
     K = len(iters)
     if not (d_iters.is_cuda and d_iters.dtype == torch.uint8 and d_iters.numel() >= K * C.sizeof(_lib.PlanIter)):
         raise _lib.OmgHipError("d_iters must be a uint8 device tensor holding the iteration table")
@@ -973,8 +940,8 @@ def plan_persistent(robot, P, scenes: DeviceScenes, goals, dt, traj, layer_out, 
         raise _lib.OmgHipError(f"workspace must be a uint8 device tensor of {need} bytes")
     with torch.cuda.device(traj.device):
         check(l.omgx_plan_persistent(_ptr(robot), int(P), _ptr(scenes.objects), _ptr(scenes.scene_begin), _ptr(scenes.pool), _ptr(goals), S, G,
-                                     float(dt), int(bool(soften_fingers)), _ptr(cost), _ptr(col), _ptr(traj), n, int(bool(layer_soften_fingers)),
-                                     _ptr(lp), _ptr(lg), _ptr(lc), _ptr(layer_poses), _ptr(active), _ptr(goal_count),
+                                     float(dt), int(bool(soften_fingers)), cost, col, traj_p, n, int(bool(layer_soften_fingers)),
+                                     lp, lg, lc, poses, _ptr(active), _ptr(goal_count),
                                      C.byref(lparams), _ptr(goal_set), _ptr(reach), _ptr(state), _ptr(goal_idx), _ptr(cost_vector), _ptr(eta),
                                      C.byref(params), _ptr(start), _ptr(end), _ptr(goal_rows), _ptr(goal_point), _ptr(grad), _ptr(cost_traj), _ptr(info),
                                      iters, _ptr(d_iters), K, _ptr(workspace), workspace.numel(), int(max_workgroups), int(update_cus), _stream()),
