@@ -789,6 +789,72 @@ int omgx_grasp_poses(const omgx_mesh* meshes, const omgx_mesh* h_meshes, int32_t
                      double pad_depth, double clearance, double* poses, uint8_t* valid, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * (14) omgx_render_depth, omgx_pixel_count, omgx_pixel_gather: a depth camera on the scenes' own meshes
+ * Replaces the renderer of the reference's perception entry (omg/core.py:826-867: scene.renderer.rendered_frames of ycb_render/,
+ * an OpenGL/EGL pipeline, gives a mask and a point image; core.py:853 moves the points to the robot base frame) by a compute ray
+ * caster: one ray per pixel against the triangle meshes of the scene's instances, the nearest hit per pixel, then the hit
+ * pixels of one class as a packed cloud in the world frame, ready for omgx_point_cloud_sdf.  omg-planner_amd/camera.py
+ * (render_depth, pixel_clouds) is the specification; all arithmetic is float64 without contraction, dot products as
+ * (x*x' + y*y') + z*z', and the results have the specification's bits.  New entry points only: omgx_abi_version() stays 14.
+ *
+ * Camera of scene s: optical axis +z, image row r downwards, column c to the right; pixel (r, c) is the ray from the camera
+ * origin with dx = (c - cx) / fx, dy = (r - cy) / fy, dz = 1, so the hit parameter t is the depth along the axis.  The scene owns
+ * the instances [inst_begin, inst_begin + inst_count) of `instances`; ranges of two scenes may overlap (they are only read).
+ * Instance: m = rows of obj_from_cam [3,4] (any invertible affine map keeps t); (centre, q) a bounding ball of the instance in
+ * the camera frame, q = |centre|^2 - r^2 (camera.instance_records inflates r by 1e-6 r + 1e-9); mesh indexes `meshes`
+ * (the omgx_mesh records and the vertex / face pools of omgx_mesh_sdf; several instances may share a mesh); label >= 0.
+ *
+ * omgx_render_depth: per pixel, from best = +inf, inst = -1, face = -1, for the scene's instances i = 0, 1, ... in order:
+ *   cd = (c0*dx + c1*dy) + c2, dd = (dx*dx + dy*dy) + 1.0, active = (q <= 0) | ((cd > 0) & (cd*cd >= q*dd)); cull == 0: true
+ *   o' = (m[3], m[7], m[11]), d'_k = (m[4k]*dx + m[4k+1]*dy) + m[4k+2]
+ *   (t_i, f_i) = omgx_mesh_raycast's answer for (o', d', t_min, tol) on the instance's mesh
+ *   if active & (t_i < best): best = t_i, inst = i, face = f_i      (the lowest instance index wins a tie)
+ *   The cull is part of the contract: an inactive pixel ignores the instance even if its ray would hit.
+ *   t_out [S][H][W] double, inst_out [S][H][W] int32 (local to the scene), face_out [S][H][W] int32 (local to the mesh) or NULL;
+ *   every pixel is written, background as (+inf, -1, -1).
+ *   One workgroup of OMGX_CAMERA_PIXELS_PER_WORKGROUP threads per 16 x 16 pixel tile of a scene; an instance's faces are read
+ *   only by the tiles of which some pixel is active.
+ * omgx_pixel_count: for every scene the number of pixels a cloud of class cls keeps — inst >= 0 and the instance's label == cls;
+ *   cls < 0: every hit — per group of 256 row-major pixels into `workspace` (omgx_pixel_clouds_workspace_bytes bytes), turned
+ *   into exclusive offsets in place, and scene_begin [S + 1] int32 (device): scene s's rows of the packed cloud.  Two launches.
+ * omgx_pixel_gather: points[scene_begin[s] + k] = the k-th kept pixel of scene s in row-major order, p = (t*dx, t*dy, t),
+ *   w_k = ((W[4k]*p0 + W[4k+1]*p1) + W[4k+2]*p2) + W[4k+3] with W = world_from_cam.  `workspace` as omgx_pixel_count left it, the
+ *   same records, images and cls; rows >= cap are not written.  Deterministic, no atomics.
+ * `instances` / `cameras` are the records on the device, h_instances / h_cameras the same on the host; ALL checks are made on the
+ * host copies before any HIP call (omgx_pixel_gather, which has none, checks its scalars and pointers).
+ * OMGX_ERR_INVALID: a null pointer (instances may be NULL with num_instances == 0, the images and cameras with
+ * num_scenes == 0, points with cap == 0), num_meshes < 1, a negative count, H or W < 1, fx or fy zero or not finite, any other
+ * record field not finite, label < 0, a mesh index outside [0, num_meshes), a camera's instance range outside
+ * [0, num_instances], t_min or tol negative or not finite, a mesh without vertices or faces or with a negative begin, cap < 0.
+ * num_scenes == 0 is legal; a scene with zero instances gives all background.
+ * OMGX_ERR_UNSUPPORTED: more than 65535 scenes (gridDim.y of every kernel); omgx_render_depth: more than 2^23 tiles in one image
+ * (the tile index is its gridDim.x); omgx_pixel_count / omgx_pixel_gather: num_scenes * H * W > 2^31 - 1 (the offsets are int32).
+ * ------------------------------------------------------------------------------------------- */
+#define OMGX_CAMERA_PIXELS_PER_WORKGROUP 256
+typedef struct omgx_camera {
+    double fx, fy, cx, cy;
+    double world_from_cam[12];      /* rows of a 3x4 matrix                                     */
+    int32_t inst_begin, inst_count; /* the scene's rows of `instances`                          */
+} omgx_camera; /* sizeof == 136 */
+typedef struct omgx_instance {
+    double m[12];                   /* rows of obj_from_cam [3,4]                               */
+    double centre[3];               /* bounding ball, camera frame                              */
+    double q;                       /* |centre|^2 - r^2                                         */
+    int32_t mesh, label;
+} omgx_instance; /* sizeof == 136 */
+int omgx_render_depth(const double* verts, const int32_t* faces, const omgx_mesh* meshes, const omgx_mesh* h_meshes,
+                      int32_t num_meshes, const omgx_instance* instances, const omgx_instance* h_instances, int32_t num_instances,
+                      const omgx_camera* cameras, const omgx_camera* h_cameras, int32_t num_scenes, int32_t H, int32_t W,
+                      int32_t cull, double t_min, double tol, double* t_out, int32_t* inst_out, int32_t* face_out, void* stream);
+int64_t omgx_pixel_clouds_workspace_bytes(int32_t num_scenes, int32_t H, int32_t W);
+int omgx_pixel_count(const omgx_instance* instances, const omgx_instance* h_instances, int32_t num_instances,
+                     const omgx_camera* cameras, const omgx_camera* h_cameras, int32_t num_scenes, int32_t H, int32_t W,
+                     const int32_t* inst_img, int32_t cls, void* workspace, int32_t* scene_begin, void* stream);
+int omgx_pixel_gather(const omgx_instance* instances, int32_t num_instances, const omgx_camera* cameras, int32_t num_scenes,
+                      int32_t H, int32_t W, const double* t_img, const int32_t* inst_img, int32_t cls, const void* workspace,
+                      double* points, int64_t cap, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Diagnostics
  * ------------------------------------------------------------------------------------------- */
 const char* omgx_last_error(void); /* thread-local text of the last OMGX_ERR_LAUNCH               */

@@ -26,7 +26,8 @@ EXPORTS = ["omgx_sdf_loss_forward", "omgx_fk_sdf_workspace_bytes", "omgx_fk_sdf"
            "omgx_learner_state_doubles", "omgx_goal_update", "omgx_goal_update_optimize", "omgx_point_cloud_sdf", "omgx_last_error", "omgx_abi_version", "omgx_device_arch", "omgx_device_cu_count", "omgx_download_sync",
            "omgx_timing_enable", "omgx_timing_collect", "omgx_plan_persistent_workspace_bytes", "omgx_plan_persistent", "omgx_plan_persistent_status", "omgx_goal_ik",
            "omgx_select_goals_workspace_bytes", "omgx_select_goals", "omgx_mesh_sdf_tile", "omgx_mesh_sdf",
-           "omgx_mesh_raycast_chunks", "omgx_mesh_raycast_workspace_bytes", "omgx_mesh_raycast", "omgx_grasp_poses"]
+           "omgx_mesh_raycast_chunks", "omgx_mesh_raycast_workspace_bytes", "omgx_mesh_raycast", "omgx_grasp_poses",
+           "omgx_render_depth", "omgx_pixel_clouds_workspace_bytes", "omgx_pixel_count", "omgx_pixel_gather"]
 
 
 class OmgHipError(RuntimeError):
@@ -74,6 +75,20 @@ class RayWork(C.Structure):
 
 RAYCAST_RAYS_PER_WORKGROUP = 256  # OMGX_RAYCAST_RAYS_PER_WORKGROUP
 RAYCAST_MAX_CHUNKS = 64           # OMGX_RAYCAST_MAX_CHUNKS
+
+
+class Camera(C.Structure):
+    """Mirror of `omgx_camera` (include/omg_hip.h): one scene's camera of omgx_render_depth (136 bytes)."""
+    _fields_ = [(n, C.c_double) for n in ("fx", "fy", "cx", "cy")] + [("world_from_cam", C.c_double * 12), ("inst_begin", C.c_int32),
+                                                                     ("inst_count", C.c_int32)]
+
+
+class Instance(C.Structure):
+    """Mirror of `omgx_instance` (include/omg_hip.h): one (mesh, pose, label) of omgx_render_depth (136 bytes)."""
+    _fields_ = [("m", C.c_double * 12), ("centre", C.c_double * 3), ("q", C.c_double), ("mesh", C.c_int32), ("label", C.c_int32)]
+
+
+CAMERA_PIXELS_PER_WORKGROUP = 256  # OMGX_CAMERA_PIXELS_PER_WORKGROUP
 
 ALG = {"FTL": 0, "FTC": 1, "Exp": 2, "MD": 3, "Proj": 4}
 
@@ -187,6 +202,14 @@ def lib() -> C.CDLL:
         l.omgx_grasp_poses.argtypes = ([vp, vp, i32, vp, vp, vp, vp, i32, i32] + [vp] * 5 + [i32, vp, vp, i32, vp, i32, vp, i64] +
                                        [f64] * 5 + [vp, vp, vp])
         l.omgx_grasp_poses.restype = C.c_int
+        l.omgx_render_depth.argtypes = [vp, vp, vp, vp, i32, vp, vp, i32, vp, vp, i32, i32, i32, i32, f64, f64, vp, vp, vp, vp]
+        l.omgx_render_depth.restype = C.c_int
+        l.omgx_pixel_clouds_workspace_bytes.argtypes = [i32, i32, i32]
+        l.omgx_pixel_clouds_workspace_bytes.restype = i64
+        l.omgx_pixel_count.argtypes = [vp, vp, i32, vp, vp, i32, i32, i32, vp, i32, vp, vp, vp]
+        l.omgx_pixel_count.restype = C.c_int
+        l.omgx_pixel_gather.argtypes = [vp, i32, vp, i32, i32, i32, vp, vp, i32, vp, vp, i64, vp]
+        l.omgx_pixel_gather.restype = C.c_int
         for name in ("omgx_sdf_loss_forward", "omgx_fk_sdf", "omgx_forward_kinematics", "omgx_pose_table", "omgx_goalset_cost", "omgx_chomp_optimize",
                      "omgx_abi_version", "omgx_device_arch", "omgx_timing_enable", "omgx_timing_collect"):
             getattr(l, name).restype = C.c_int

@@ -1,0 +1,217 @@
+"""A depth camera for the project's own scenes: the specification of omgx_render_depth / omgx_pixel_count / omgx_pixel_gather
+(csrc/omg_camera.hip follows it operation by operation) and the device path `observe_scenes`.
+
+The reference's perception entry (omg/core.py:826-867, `python -m omg.core -p`) renders the scene with an OpenGL/EGL renderer
+(ycb_render/) to a mask and a point image, splits the pixels into target and non-target points, moves them to the robot base
+frame with the view matrix (core.py:853: V[:3,:3].T (p - V[:3,3])) and draws a fixed number with np.random.choice; the
+non-target cloud becomes the obstacle volume (PointEnv.compute_sdf_from_points, here ops.point_cloud_sdf).  An accelerator
+without a graphics pipeline casts rays instead: one ray per pixel against the triangle meshes of the scene's instances.
+
+Camera: intrinsics fx, fy, cx, cy and world_from_cam (12 doubles, the rows of a 3x4 matrix: the inverse of the reference's
+renderer.V).  Optical axis +z, image row r downwards, column c to the right.  Pixel (r, c) is the ray from the camera origin
+with dx = (c - cx) / fx, dy = (r - cy) / fy, dz = 1, so the hit parameter t is the depth along the axis.
+
+Instance: one (mesh, pose, label), see INSTANCE_DTYPE and instance_records.
+
+Everything specified is plain numpy float64 with every dot product written (x*x' + y*y') + z*z', so that the device can equal
+the bits.  Not part of the contract: colour, textures, lighting, a far plane, noise, the robot's own links in the image.
+"""
+from __future__ import annotations
+
+import numpy as np
+
+from . import grasps as _gr
+
+# omgx_instance (include/omg_hip.h section 14), 136 bytes
+INSTANCE_DTYPE = np.dtype([("m", np.float64, 12),       # rows of obj_from_cam [3,4]
+                           ("centre", np.float64, 3),   # bounding ball in the camera frame
+                           ("q", np.float64),           # |centre|^2 - r2
+                           ("mesh", np.int32), ("label", np.int32)])
+# omgx_camera, 136 bytes
+CAMERA_DTYPE = np.dtype([("fx", np.float64), ("fy", np.float64), ("cx", np.float64), ("cy", np.float64),
+                         ("world_from_cam", np.float64, 12), ("inst_begin", np.int32), ("inst_count", np.int32)])
+assert INSTANCE_DTYPE.itemsize == 136 and CAMERA_DTYPE.itemsize == 136
+
+
+def camera_rows(intrinsics, cam_from_world) -> np.ndarray:
+    """One row of `cameras` [16]: fx, fy, cx, cy and the rows of world_from_cam = inv(cam_from_world) [3,4]."""
+    k = np.asarray(intrinsics, np.float64).reshape(4)
+    w = np.linalg.inv(np.asarray(cam_from_world, np.float64).reshape(4, 4))
+    return np.concatenate([k, w[:3].ravel()])
+
+
+def instance_records(meshes, mesh_idx, poses, labels, cam_from_world) -> np.ndarray:
+    """INSTANCE_DTYPE records of one scene's instances as one camera sees them.  meshes: the pool [(verts, faces)]; mesh_idx,
+    poses [I,4,4] (object -> world), labels [I] (>= 0): one per instance; cam_from_world [4,4].
+
+    m = rows of inv(cam_from_world @ pose) (np.linalg.inv; any invertible affine map keeps t).  The bounding ball: the
+    instance's vertices in the camera frame, centre = the midpoint of their bounding box, r = the largest vertex distance
+    from it, r2 = (r * (1 + 1e-6) + 1e-9) ** 2, q = ((c0*c0 + c1*c1) + c2*c2) - r2.  The kernel's contract starts at the
+    records: how the host rounds m and the ball is not part of it."""
+    cam_from_world = np.asarray(cam_from_world, np.float64).reshape(4, 4)
+    rec = np.zeros(len(mesh_idx), INSTANCE_DTYPE)
+    for i, (mi, pose, label) in enumerate(zip(mesh_idx, poses, labels)):
+        if not 0 <= int(mi) < len(meshes):
+            raise ValueError(f"instance {i}: mesh {mi} outside the pool of {len(meshes)}")
+        if int(label) < 0:
+            raise ValueError(f"instance {i}: label {label} is negative")
+        cam_from_obj = cam_from_world @ np.asarray(pose, np.float64).reshape(4, 4)
+        rec["m"][i] = np.linalg.inv(cam_from_obj)[:3].ravel()
+        v = np.asarray(meshes[int(mi)][0], np.float64)
+        vc = v @ cam_from_obj[:3, :3].T + cam_from_obj[:3, 3]
+        c = 0.5 * (vc.min(0) + vc.max(0))
+        r = float(np.sqrt(((vc - c) ** 2).sum(1)).max())
+        r2 = (r * (1.0 + 1e-6) + 1e-9) ** 2
+        rec["centre"][i] = c
+        rec["q"][i] = ((c[0] * c[0] + c[1] * c[1]) + c[2] * c[2]) - r2
+        rec["mesh"][i], rec["label"][i] = int(mi), int(label)
+    return rec
+
+
+def pixel_directions(cam, H: int, W: int):
+    """(dx, dy) [H*W] of the pixels in row-major order: dx = (c - cx) / fx, dy = (r - cy) / fy."""
+    r, c = np.divmod(np.arange(int(H) * int(W), dtype=np.int64), int(W))
+    return (c.astype(np.float64) - cam[2]) / cam[0], (r.astype(np.float64) - cam[3]) / cam[1]
+
+
+def instance_active(rec, dx, dy):
+    """The cull of one instance record: can the pixel's ray meet the bounding ball?
+    cd = (c0*dx + c1*dy) + c2, dd = (dx*dx + dy*dy) + 1.0, active = (q <= 0) | ((cd > 0) & (cd*cd >= q*dd))."""
+    c, q = rec["centre"], float(rec["q"])
+    cd = (c[0] * dx + c[1] * dy) + c[2]
+    dd = (dx * dx + dy * dy) + 1.0
+    return (q <= 0.0) | ((cd > 0.0) & (cd * cd >= q * dd))
+
+
+def _check(instances, inst_begin, cameras):
+    instances = np.asarray(instances)
+    cameras = np.asarray(cameras, np.float64).reshape(-1, 16)
+    inst_begin = np.asarray(inst_begin, np.int64)
+    if instances.dtype != INSTANCE_DTYPE:
+        raise ValueError("instances must be INSTANCE_DTYPE records (instance_records)")
+    if len(inst_begin) != len(cameras) + 1 or inst_begin[0] < 0 or (np.diff(inst_begin) < 0).any() or inst_begin[-1] > len(instances):
+        raise ValueError("inst_begin must be [S+1], ascending, within the instances")
+    return instances, inst_begin, cameras
+
+
+def render_depth(meshes, instances, inst_begin, cameras, H: int, W: int, cull: bool = True, t_min: float = 1e-6, tol: float = 1e-9):
+    """Depth, instance and face images of S scenes -> (t [S,H,W] float64, inst [S,H,W] int32, face [S,H,W] int32); background:
+    (+inf, -1, -1).  The specification of omgx_render_depth.
+
+    meshes: the pool [(verts, faces)]; instances: INSTANCE_DTYPE records; scene s owns instances [inst_begin[s], inst_begin[s+1])
+    (inst is local to the scene); cameras [S,16] (camera_rows).  Per pixel, from best = +inf, inst = -1, face = -1, for the
+    scene's instances i = 0, 1, ... in order: active = instance_active (true everywhere with cull=False); the object-frame ray
+    o' = (m[3], m[7], m[11]), d'_k = (m[4k]*dx + m[4k+1]*dy) + m[4k+2]; (t_i, f_i) = grasps.mesh_raycast(o', d', t_min, tol) on
+    the instance's mesh; if active & (t_i < best): best = t_i, inst = i, face = f_i.  The strict < makes the lowest instance
+    index win a tie.  The cull is part of the contract: an inactive pixel ignores the instance even if its ray would hit."""
+    instances, inst_begin, cameras = _check(instances, inst_begin, cameras)
+    S, H, W = len(cameras), int(H), int(W)
+    t_img = np.full((S, H * W), np.inf)
+    inst_img = np.full((S, H * W), -1, np.int32)
+    face_img = np.full((S, H * W), -1, np.int32)
+    for s in range(S):
+        dx, dy = pixel_directions(cameras[s], H, W)
+        for i, rec in enumerate(instances[inst_begin[s]: inst_begin[s + 1]]):
+            active = instance_active(rec, dx, dy) if cull else np.ones(H * W, bool)
+            if not active.any():
+                continue  # (what the kernel skips too; the result is the same without this line)
+            m = rec["m"]
+            o = np.broadcast_to(np.array([m[3], m[7], m[11]]), (H * W, 3))
+            d = np.stack([(m[4 * k] * dx + m[4 * k + 1] * dy) + m[4 * k + 2] for k in range(3)], -1)
+            verts, faces = meshes[int(rec["mesh"])]
+            t_i, f_i = _gr.mesh_raycast(verts, faces, o, d, t_min, tol)
+            take = active & (t_i < t_img[s])
+            t_img[s] = np.where(take, t_i, t_img[s])
+            inst_img[s] = np.where(take, np.int32(i), inst_img[s])
+            face_img[s] = np.where(take, f_i, face_img[s])
+    return t_img.reshape(S, H, W), inst_img.reshape(S, H, W), face_img.reshape(S, H, W)
+
+
+def pixel_mask(inst, labels, cls: int):
+    """Which pixels of one scene's instance image [H,W] a cloud of class `cls` keeps: inst >= 0 and the instance's label equals
+    cls; with cls < 0 every hit.  labels: the scene's own instance labels."""
+    inst = np.asarray(inst)
+    hit = (inst >= 0) & (inst < len(labels))  # anything else names no instance
+    if int(cls) < 0 or len(labels) == 0:
+        return hit
+    return hit & (np.asarray(labels)[np.clip(inst, 0, len(labels) - 1)] == int(cls))
+
+
+def pixel_clouds(t, inst, labels, inst_begin, cameras, cls: int):
+    """The hit pixels of class `cls` as points in the world frame -> S arrays [N_s,3] float64.  The specification of
+    omgx_pixel_count / omgx_pixel_gather.  t, inst [S,H,W]: render_depth's images; labels: the label of every instance (all
+    scenes); the pixels are taken in row-major order (np.nonzero's); p = (t*dx, t*dy, t);
+    w_k = ((W[4k]*p0 + W[4k+1]*p1) + W[4k+2]*p2) + W[4k+3] with W = world_from_cam."""
+    cameras = np.asarray(cameras, np.float64).reshape(-1, 16)
+    t, inst = np.asarray(t, np.float64), np.asarray(inst)
+    S, H, W = t.shape
+    out = []
+    for s in range(S):
+        keep = pixel_mask(inst[s], np.asarray(labels)[int(inst_begin[s]): int(inst_begin[s + 1])], cls).reshape(-1)
+        dx, dy = pixel_directions(cameras[s], H, W)
+        ts = t[s].reshape(-1)[keep]
+        p = [ts * dx[keep], ts * dy[keep], ts]
+        Wm = cameras[s, 4:]
+        out.append(np.ascontiguousarray(np.stack([((Wm[4 * k] * p[0] + Wm[4 * k + 1] * p[1]) + Wm[4 * k + 2] * p[2]) + Wm[4 * k + 3]
+                                                  for k in range(3)], -1)))
+    return out
+
+
+def draw(cloud, n: int, rng):
+    """A fixed number of points of a cloud, as omg/core.py:855-856 draws them: cloud[rng.choice(len(cloud), n)].  On the host."""
+    return cloud[rng.choice(len(cloud), int(n))]
+
+
+def scene_records(scenes, meshes, cam_from_world, intrinsics):
+    """The pooled meshes and records of S scenes.Scene -> (pool [(verts, faces)], instances, inst_begin [S+1], cameras [S,16]).
+    meshes[s][o] is (verts, faces) in object o's frame or None (not drawn: the table); one instance per object that has a mesh,
+    in object order, label 0 for scene.target_idx and 1 otherwise; a mesh given (the same arrays) to several objects is pooled
+    once.  cam_from_world: [4,4] or [S,4,4]; intrinsics: (fx, fy, cx, cy) or [S,4]."""
+    S = len(scenes)
+    if len(meshes) != S:
+        raise ValueError("meshes must have one list per scene")
+    cfw = np.broadcast_to(np.asarray(cam_from_world, np.float64), (S, 4, 4))
+    intr = np.broadcast_to(np.asarray(intrinsics, np.float64), (S, 4))
+    pool, where, recs, begin = [], {}, [], [0]
+    for s, scene in enumerate(scenes):
+        if len(meshes[s]) != len(scene.objects):
+            raise ValueError(f"scene {s}: meshes must have one entry (or None) per object")
+        idx, poses, labels = [], [], []
+        for o, obj in enumerate(scene.objects):
+            if meshes[s][o] is None:
+                continue
+            key = (id(meshes[s][o][0]), id(meshes[s][o][1]))
+            if key not in where:
+                where[key] = len(pool)
+                pool.append(meshes[s][o])
+            idx.append(where[key]), poses.append(obj.pose_mat), labels.append(0 if o == scene.target_idx else 1)
+        recs.append(instance_records(pool, idx, poses, labels, cfw[s]))
+        begin.append(begin[-1] + len(idx))
+    cameras = np.stack([camera_rows(intr[s], cfw[s]) for s in range(S)]) if S else np.zeros((0, 16))
+    return pool, (np.concatenate(recs) if recs else np.zeros(0, INSTANCE_DTYPE)), np.array(begin, np.int64), cameras
+
+
+class Observation:
+    """observe_scenes' result: the images on the device (t [S,H,W] float64, inst and face [S,H,W] int32) and the batch."""
+
+    def __init__(self, batch, t, inst, face):
+        self.batch, self.t, self.inst, self.face = batch, t, inst, face
+
+    def clouds(self, cls: int):
+        """S contiguous float64 [N_s,3] device tensors in the world frame (what ops.point_cloud_sdf takes): class 0 is the
+        target, 1 everything else, < 0 every hit."""
+        from . import ops
+        points, begin = ops.pixel_clouds(self.batch, self.t, self.inst, cls)
+        return [points[int(begin[s]): int(begin[s + 1])] for s in range(len(begin) - 1)]
+
+
+def observe_scenes(scenes, meshes, cam_from_world, intrinsics, H: int, W: int, cull: bool = True, device="cuda:0") -> Observation:
+    """Depth and instance images of S scenes.Scene on the device, one launch (scene_records, ops.CameraBatch, ops.render_depth).
+    It does not call the planner."""
+    from . import ops
+    pool, instances, inst_begin, cameras = scene_records(scenes, meshes, cam_from_world, intrinsics)
+    if not pool:
+        raise ValueError("no object of any scene has a mesh")
+    batch = ops.CameraBatch(pool, instances, inst_begin, cameras, device=device)
+    t, inst, face = ops.render_depth(batch, H, W, cull=cull)
+    return Observation(batch, t, inst, face)

@@ -1,0 +1,44 @@
+// omg_camera_body.h — what k_render_depth, k_pixel_count and k_pixel_gather (omg_camera.hip) do for one pixel and one
+// (pixel, instance) pair, as functions that also compile for the host, so that the arithmetic can be stepped through and compared
+// with camera.render_depth / camera.pixel_clouds (omg-planner_amd/camera.py) without a GPU.  float64, one rounded operation per
+// operation of the specification, in its order.  The per-face step is mesh_raycast_pair (omg_grasp_body.h), unchanged.
+#pragma once
+#include <cmath>
+#include <cstdint>
+
+#include "omg_grasp_body.h"
+
+#pragma clang fp contract(off)
+
+// The ray of pixel (row r, column c): direction (dx, dy, 1) from the camera origin.
+GRASP_HD void camera_pixel_dir(int r, int c, double fx, double fy, double cx, double cy, double& dx, double& dy) {
+    dx = ((double)c - cx) / fx;
+    dy = ((double)r - cy) / fy;
+}
+
+// Can the ray meet the instance's bounding ball (centre, q = |centre|^2 - r2, camera frame)?  q <= 0: the camera is inside it.
+GRASP_HD bool camera_instance_active(const double* centre, double q, double dx, double dy) {
+    const double cd = (centre[0] * dx + centre[1] * dy) + centre[2];
+    const double dd = (dx * dx + dy * dy) + 1.0;
+    return (q <= 0.0) || ((cd > 0.0) && (cd * cd >= q * dd));
+}
+
+// The ray in the instance's frame: m = rows of obj_from_cam [3,4]; the origin is its translation column.
+GRASP_HD void camera_object_ray(const double* m, double dx, double dy, double* o, double* d) {
+    for (int k = 0; k < 3; ++k) {
+        o[k] = m[4 * k + 3];
+        d[k] = (m[4 * k] * dx + m[4 * k + 1] * dy) + m[4 * k + 2];
+    }
+}
+
+// The hit at depth t of the pixel's ray, in the world frame: W = rows of world_from_cam [3,4].
+GRASP_HD void camera_world_point(const double* W, double t, double dx, double dy, double* w) {
+    const double p0 = t * dx, p1 = t * dy, p2 = t;
+    for (int k = 0; k < 3; ++k) w[k] = ((W[4 * k] * p0 + W[4 * k + 1] * p1) + W[4 * k + 2] * p2) + W[4 * k + 3];
+}
+
+// Does a cloud of class cls keep a pixel whose instance image says `inst`?  label: that instance's (read only when
+// 0 <= inst < inst_count); cls < 0 keeps every hit.
+GRASP_HD bool camera_pixel_kept(int32_t inst, int32_t inst_count, int32_t label, int32_t cls) {
+    return inst >= 0 && inst < inst_count && (cls < 0 || label == cls);
+}

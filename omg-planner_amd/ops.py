@@ -1265,3 +1265,119 @@ def grasp_poses(batch: RayBatch, p1, n1, dirs, t, face2, normals, cs, probe, poo
         for x in (cs, probe):
             x.record_stream(torch.cuda.current_stream(dev))
     return poses, valid
+
+
+class CameraBatch:
+    """Host side of a camera launch over S scenes, shared by render_depth and pixel_clouds: the meshes pooled (MeshPool: vertex
+    pool [V,3] float64, face pool [F,3] int32, omgx_mesh records), the instance and camera records (omgx_instance, omgx_camera)
+    on the host and on the device.
+
+    meshes: the pool, a list of (verts [V,3], faces [F,3]) on the host; instances: camera.INSTANCE_DTYPE records
+    (camera.instance_records); inst_begin [S+1]: scene s owns instances [inst_begin[s], inst_begin[s+1]); cameras [S,16]:
+    fx, fy, cx, cy and the rows of world_from_cam (camera.camera_rows)."""
+
+    def __init__(self, meshes, instances, inst_begin, cameras, device="cuda:0"):
+        from . import camera as _cam
+        mp = MeshPool(meshes, drop_zero_area=False)  # dropping them here would renumber the faces the face image names
+        instances = np.ascontiguousarray(instances)
+        if instances.dtype != _cam.INSTANCE_DTYPE or instances.ndim != 1:
+            raise _lib.OmgHipError("instances must be a 1-d array of camera.INSTANCE_DTYPE records")
+        cameras = np.ascontiguousarray(cameras, np.float64)
+        if cameras.ndim != 2 or cameras.shape[1] != 16:
+            raise _lib.OmgHipError(f"cameras must be [S,16], got {cameras.shape}")
+        S, I = len(cameras), len(instances)
+        begin = np.asarray(inst_begin, np.int64).reshape(-1)
+        if len(begin) != S + 1 or begin[0] < 0 or (np.diff(begin) < 0).any() or begin[-1] > I:
+            raise _lib.OmgHipError(f"inst_begin must be [S+1] = [{S + 1}], ascending, inside the {I} instances")
+        if not np.isfinite(cameras).all() or (cameras[:, :2] == 0).any():
+            raise _lib.OmgHipError("a camera is not finite or has a focal length of zero")
+        for name in ("m", "centre", "q"):
+            if not np.isfinite(instances[name]).all():
+                raise _lib.OmgHipError(f"an instance's {name} is not finite")
+        if I and (instances["label"].min() < 0 or instances["mesh"].min() < 0 or instances["mesh"].max() >= len(meshes)):
+            raise _lib.OmgHipError(f"labels must be >= 0 and mesh indices inside the pool of {len(meshes)}")
+        self.device = torch.device(device)
+        self.num_meshes, self.num_instances, self.num_scenes = len(meshes), I, S
+        for m in range(self.num_meshes):
+            mp.set_volume(m, (0.0, 0.0, 0.0), 1.0, "centre", (1, 1, 1), 0)  # no volume is read; the fields stay defined
+        self.rec = mp.rec
+        self.h_instances = instances
+        self.h_inst_begin = begin
+        self.h_cameras = np.zeros(S, _cam.CAMERA_DTYPE)
+        self.h_cameras["fx"], self.h_cameras["fy"], self.h_cameras["cx"], self.h_cameras["cy"] = cameras[:, 0], cameras[:, 1], cameras[:, 2], cameras[:, 3]
+        self.h_cameras["world_from_cam"] = cameras[:, 4:]
+        self.h_cameras["inst_begin"], self.h_cameras["inst_count"] = begin[:-1], np.diff(begin)
+        self.verts, self.faces, self.d_rec = mp.upload(self.device)
+        as_bytes = lambda a: torch.from_numpy(np.frombuffer(a.tobytes(), np.uint8).copy()).to(self.device)
+        self.d_instances, self.d_cameras = as_bytes(self.h_instances), as_bytes(self.h_cameras)
+
+    def _records(self, host: bool = True):
+        """(instances, [h_instances,] num_instances, cameras, [h_cameras,] num_scenes) as the entry points take them."""
+        vp = C.c_void_p
+        hi = (vp(self.h_instances.ctypes.data if self.num_instances else None),) if host else ()
+        hc = (vp(self.h_cameras.ctypes.data if self.num_scenes else None),) if host else ()
+        return (_ptr(self.d_instances), *hi, self.num_instances, _ptr(self.d_cameras), *hc, self.num_scenes)
+
+    def _image(self, t, name, dtype, H=None, W=None):
+        _need(t, dtype, name)
+        if t.device != self.device or t.dim() != 3 or t.shape[0] != self.num_scenes or (H is not None and tuple(t.shape[1:]) != (H, W)):
+            raise _lib.OmgHipError(f"{name} must be [{self.num_scenes}, H, W] on {self.device}, got {tuple(t.shape)} on {t.device}")
+        return t
+
+
+def _image_size(H, W):
+    H, W = int(H), int(W)
+    if H < 1 or W < 1:
+        raise _lib.OmgHipError(f"H and W must be >= 1, got {H} and {W}")
+    return H, W
+
+
+def render_depth(batch: CameraBatch, H: int, W: int, cull: bool = True, want_face: bool = True, t_min: float = 1e-6, tol: float = 1e-9,
+                 out=None):
+    """Depth, instance and face images of the batch's S scenes in ONE launch (omgx_render_depth; camera.render_depth is the
+    specification: the same float64 t bit for bit, the same instance and face) -> (t [S,H,W] float64, inst [S,H,W] int32,
+    face [S,H,W] int32 or None without want_face); background is (+inf, -1, -1).  out: None or (t, inst, face or None),
+    contiguous device tensors written IN PLACE."""
+    H, W = _image_size(H, W)
+    if not (float(t_min) >= 0 and np.isfinite(float(t_min)) and float(tol) >= 0 and np.isfinite(float(tol))):
+        raise _lib.OmgHipError("t_min and tol must be finite and not negative")
+    S, dev = batch.num_scenes, batch.device
+    if out is None:
+        out = (torch.empty((S, H, W), dtype=torch.float64, device=dev), torch.empty((S, H, W), dtype=torch.int32, device=dev),
+               torch.empty((S, H, W), dtype=torch.int32, device=dev) if want_face else None)
+    t, inst, face = out
+    batch._image(t, "out[0]", torch.float64, H, W), batch._image(inst, "out[1]", torch.int32, H, W)
+    if face is not None:
+        batch._image(face, "out[2]", torch.int32, H, W)
+    with torch.cuda.device(dev):
+        check(_lib.lib().omgx_render_depth(_ptr(batch.verts), _ptr(batch.faces), _ptr(batch.d_rec), C.cast(batch.rec, C.c_void_p),
+                                           batch.num_meshes, *batch._records(), H, W, int(bool(cull)), float(t_min), float(tol), _ptr(t),
+                                           _ptr(inst), _ptr(face), _stream()), "omgx_render_depth")
+    return t, inst, face
+
+
+def pixel_clouds(batch: CameraBatch, t: torch.Tensor, inst: torch.Tensor, cls: int, out: "torch.Tensor | None" = None):
+    """The hit pixels of class `cls` (an instance label; < 0: every hit) of render_depth's images as world-frame points, in
+    pixel order (omgx_pixel_count, omgx_pixel_gather; camera.pixel_clouds is the specification: the same float64 bit for bit)
+    -> (points [N,3] float64 on the device, scene_begin [S+1] int64 numpy): scene s's cloud is points[scene_begin[s]:
+    scene_begin[s+1]], a contiguous tensor as point_cloud_sdf takes it.  Count, ONE download of scene_begin, an exact
+    allocation, gather.  out: a contiguous float64 [cap,3] device tensor written IN PLACE instead; rows >= cap are dropped."""
+    batch._image(t, "t", torch.float64)
+    H, W = int(t.shape[1]), int(t.shape[2])
+    batch._image(inst, "inst", torch.int32, H, W)
+    S, dev, l, cls = batch.num_scenes, batch.device, _lib.lib(), int(cls)
+    if not -(1 << 31) <= cls < (1 << 31):
+        raise _lib.OmgHipError(f"cls must fit int32, got {cls}")
+    if out is not None:
+        _need(out, torch.float64, "out")
+        if out.device != dev or out.dim() != 2 or out.shape[1] != 3:
+            raise _lib.OmgHipError(f"out must be [cap,3] on {dev}, got {tuple(out.shape)} on {out.device}")
+    ws = torch.empty(max(int(l.omgx_pixel_clouds_workspace_bytes(S, H, W)) // 4, 1), dtype=torch.int32, device=dev)
+    begin = torch.empty(S + 1, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        check(l.omgx_pixel_count(*batch._records(), H, W, _ptr(inst), cls, _ptr(ws), _ptr(begin), _stream()), "omgx_pixel_count")
+        h_begin = begin.cpu().numpy().astype(np.int64)
+        points = torch.empty((int(h_begin[-1]), 3), dtype=torch.float64, device=dev) if out is None else out
+        check(l.omgx_pixel_gather(*batch._records(host=False), H, W, _ptr(t), _ptr(inst), cls, _ptr(ws), _ptr(points), int(points.shape[0]),
+                                  _stream()), "omgx_pixel_gather")
+    return points, h_begin

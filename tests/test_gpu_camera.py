@@ -1,0 +1,216 @@
+"""The depth camera on the MI355X (csrc/omg_camera.hip): omgx_render_depth against camera.render_depth bit
+for bit around the pixel tile and the LDS face tile, with and without the cull and the face image; a launch of three scenes
+against single launches between sentinels; the clouds against camera.pixel_clouds around the group of 256 pixels; the render
+against the per-instance ray casts it replaces; and the chain from scenes to an obstacle volume."""
+from __future__ import annotations
+
+import numpy as np
+import pytest
+
+from tests import camera_cases as CC
+from tests import mesh_cases as MC
+
+pytestmark = pytest.mark.gpu
+
+torch = pytest.importorskip("torch")
+
+
+@pytest.fixture(scope="module")
+def dev():
+    if not torch.cuda.is_available():
+        pytest.fail("GPU tests need a GPU: torch.cuda.is_available() is False")
+    return torch.device("cuda:0")
+
+
+_BATCH = {}
+
+
+def batch_of(name, dev):
+    from omg_planner_amd import ops
+    if name not in _BATCH:
+        sc = CC.scene(name)
+        _BATCH[name] = ops.CameraBatch(sc["meshes"], sc["instances"], sc["inst_begin"], sc["cameras"], device=dev)
+    return _BATCH[name]
+
+
+def _same(got, want):
+    """t as int64 bits, inst and face (where asked for), device against specification."""
+    torch.cuda.synchronize()
+    ok = torch.equal(got[0].cpu().view(torch.int64), torch.from_numpy(np.array(want[0])).view(torch.int64))
+    ok = ok and torch.equal(got[1].cpu(), torch.from_numpy(np.array(want[1])))
+    return ok and (got[2] is None or torch.equal(got[2].cpu(), torch.from_numpy(np.array(want[2]))))
+
+
+def _mixed(name):
+    """A scene is only used once it shows hits and background (a single pixel: either)."""
+    inst = CC.spec(name)[1]
+    assert inst.size == 1 or ((inst >= 0).any() and (inst < 0).any()), name
+
+
+@pytest.mark.parametrize("name", ["1x1", "15x17", "16x16", "17x33", "25x41", "inside_sphere", "overlap", "duplicate", "box_behind"])
+def test_render_equals_the_specification_bit_for_bit(dev, name):
+    """Image sizes around the 16 x 16 pixel tile (17x33 with the principal point outside the image), meshes of T - 1, T, T + 1 and
+    2T + 1 faces for the LDS tile T and the box, a duplicate and an instance behind the camera; with the cull, without it, and
+    without the face image."""
+    from omg_planner_amd import _lib, ops
+    sc = CC.scene(name)
+    if name[0].isdigit():
+        T = int(_lib.lib().omgx_mesh_sdf_tile())
+        assert sorted(len(f) for _, f in sc["meshes"]) == [12, T - 1, T, T + 1, 2 * T + 1]
+        _mixed(name)
+    b = batch_of(name, dev)
+    for cull in (True, False):
+        got = ops.render_depth(b, sc["H"], sc["W"], cull=cull)
+        assert got[0].dtype == torch.float64 and got[1].dtype == torch.int32 and got[2].dtype == torch.int32
+        assert got[0].shape == (1, sc["H"], sc["W"])
+        assert _same(got, CC.spec(name, cull)), (name, cull)
+        bare = ops.render_depth(b, sc["H"], sc["W"], cull=cull, want_face=False)
+        assert bare[2] is None and _same(bare, CC.spec(name, cull)), (name, cull)
+
+
+@pytest.mark.parametrize("name", CC.RANDOM[:4])
+def test_random_scenes_equal_the_specification(dev, name):
+    from omg_planner_amd import ops
+    sc = CC.scene(name)
+    inst = CC.spec(name)[1][0]
+    seen = CC.labels(sc)[inst[inst >= 0]]
+    assert (inst >= 0).any() and (inst < 0).any() and (seen == 0).any() and (seen == 1).any()
+    for cull in (True, False):
+        assert _same(ops.render_depth(batch_of(name, dev), sc["H"], sc["W"], cull=cull), CC.spec(name, cull)), (name, cull)
+
+
+def _guarded(shape, dtype, fill, dev, pad=300):
+    """A tensor of `shape` inside a larger buffer of sentinels -> (view, buffer, pad)."""
+    n = int(np.prod(shape))
+    buf = torch.full((n + 2 * pad,), fill, dtype=dtype, device=dev)
+    return buf[pad: pad + n].view(shape), buf, pad
+
+
+def test_three_scenes_in_one_launch_equal_single_launches(dev):
+    """S = 3 scenes with 0, 1 and 6 instances (a duplicate and one behind the camera among them) and three cameras in one
+    launch: the specification's bits, the bits of three single-scene launches, and nothing written outside the images."""
+    from omg_planner_amd import ops
+    sc = CC.scene("multi")
+    H, W = sc["H"], sc["W"]
+    assert np.diff(sc["inst_begin"]).tolist() == [0, 1, 6]
+    want = CC.spec("multi")
+    assert (want[1][0] == -1).all() and (want[1][1] >= 0).any() and len(np.unique(want[1][2])) >= 4
+    for cull in (True, False):
+        (t, tb, pad), (ii, ib, _), (ff, fb, _) = (_guarded((3, H, W), dt, fill, dev) for dt, fill in
+                                                   ((torch.float64, -7.0), (torch.int32, -9), (torch.int32, -9)))
+        got = ops.render_depth(batch_of("multi", dev), H, W, cull=cull, out=(t, ii, ff))
+        assert got[0] is t and _same(got, CC.spec("multi", cull))
+        for buf, fill in ((tb, -7.0), (ib, -9), (fb, -9)):
+            assert (buf[:pad] == fill).all() and (buf[-pad:] == fill).all()
+        for s in range(3):
+            one = CC.single(sc, s)
+            b1 = ops.CameraBatch(one["meshes"], one["instances"], one["inst_begin"], one["cameras"], device=dev)
+            assert _same(ops.render_depth(b1, H, W, cull=cull), [a[s: s + 1] for a in CC.spec("multi", cull)]), (cull, s)
+
+
+def _spec_clouds(name, cls):
+    from omg_planner_amd import camera as cam
+    sc = CC.scene(name)
+    t, inst, _ = CC.spec(name)
+    return cam.pixel_clouds(t, inst, CC.labels(sc), sc["inst_begin"], sc["cameras"], cls)
+
+
+@pytest.mark.parametrize("name", ["15x17", "16x16", "1x257", "25x41", "multi"])
+def test_clouds_equal_the_specification_bit_for_bit(dev, name):
+    """H * W = 255, 256, 257 and 4 * 256 + 1 pixels, and the three scenes of `multi` packed into one list: for classes that select
+    nothing (9), a strict subset (0, 1, 2; 2 is everything in multi's second scene), and every hit (-1), the points in pixel order
+    as int64 bits, scene_begin, sentinels around the packed rows, and a cap below the total."""
+    from omg_planner_amd import ops
+    sc = CC.scene(name)
+    H, W = sc["H"], sc["W"]
+    assert H * W == {"15x17": 255, "16x16": 256, "1x257": 257, "25x41": 1025, "multi": 561}[name]
+    _mixed(name)
+    b = batch_of(name, dev)
+    t, inst, _ = (torch.from_numpy(np.array(a)).to(dev) for a in CC.spec(name))
+    totals = {}
+    for cls in (9, 0, 1, 2, -1):
+        want = _spec_clouds(name, cls)
+        begin = np.concatenate([[0], np.cumsum([len(w) for w in want])])
+        flat = np.concatenate(want)
+        totals[cls] = len(flat)
+        points, got_begin = ops.pixel_clouds(b, t, inst, cls)
+        torch.cuda.synchronize()
+        assert points.dtype == torch.float64 and points.shape == (len(flat), 3) and points.is_contiguous()
+        assert got_begin.tolist() == begin.tolist(), (name, cls)
+        assert np.array_equal(points.cpu().numpy().view(np.int64), flat.view(np.int64)), (name, cls)
+        # room for more rows than there are: the rest stays as it was; room for fewer: exactly `cap` rows are written
+        for cap in (len(flat) + 7, max(len(flat) - 5, 0)):
+            view, buf, pad = _guarded((cap, 3), torch.float64, -7.0, dev, pad=30)
+            out, _ = ops.pixel_clouds(b, t, inst, cls, out=view)
+            torch.cuda.synchronize()
+            n = min(cap, len(flat))
+            assert out is view and np.array_equal(view[:n].cpu().numpy().view(np.int64), flat[:n].view(np.int64)), (name, cls, cap)
+            assert (view[n:] == -7.0).all() and (buf[:pad] == -7.0).all() and (buf[-pad:] == -7.0).all(), (name, cls, cap)
+    assert totals[9] == 0 and 0 < totals[0] < totals[-1] and 0 < totals[1] < totals[-1] and totals[0] + totals[1] + totals[2] == totals[-1]
+    if name == "multi":
+        every = _spec_clouds(name, -1)
+        assert len(every[0]) == 0 and len(_spec_clouds(name, 2)[1]) == len(every[1]) > 0   # class 2 is all of the second scene
+
+
+def test_render_equals_the_per_instance_ray_casts_it_replaces(dev):
+    """One small scene: every instance's rays moved to its frame by the specification's formula and cast by ops.mesh_raycast, the
+    nearest over the instances taken in order with the strict <: the same t, instance and face as one render."""
+    from omg_planner_amd import camera as cam, ops
+    sc = CC.scene("15x17")
+    H, W = sc["H"], sc["W"]
+    dx, dy = cam.pixel_directions(sc["cameras"][0], H, W)
+    best = torch.full((H * W,), float("inf"), dtype=torch.float64, device=dev)
+    inst = torch.full((H * W,), -1, dtype=torch.int32, device=dev)
+    face = torch.full((H * W,), -1, dtype=torch.int32, device=dev)
+    for i, rec in enumerate(sc["instances"]):
+        m = rec["m"]
+        o = np.ascontiguousarray(np.broadcast_to(np.array([m[3], m[7], m[11]]), (H * W, 3)))
+        d = np.ascontiguousarray(np.stack([(m[4 * k] * dx + m[4 * k + 1] * dy) + m[4 * k + 2] for k in range(3)], -1))
+        t_i, f_i = ops.mesh_raycast(*sc["meshes"][int(rec["mesh"])], o, d, chunks=1, device=dev)
+        take = torch.from_numpy(cam.instance_active(rec, dx, dy)).to(dev) & (t_i < best)
+        best, inst, face = torch.where(take, t_i, best), torch.where(take, torch.full_like(inst, i), inst), torch.where(take, f_i, face)
+    got = ops.render_depth(batch_of("15x17", dev), H, W)
+    torch.cuda.synchronize()
+    assert torch.equal(got[0].view(-1).view(torch.int64), best.view(torch.int64)) and torch.equal(got[1].view(-1), inst)
+    assert torch.equal(got[2].view(-1), face) and (inst >= 0).any()
+
+
+def test_scenes_to_obstacle_volume(dev):
+    """observe_scenes on the two scenes of `observed` (a table without a mesh, a target, obstacles; two cameras): the images equal
+    the specification's, the label-1 cloud of each scene is a contiguous float64 tensor with the specification's bits, and
+    ops.point_cloud_sdf of it equals scenes.point_cloud_sdf of the specification's cloud."""
+    from omg_planner_amd import camera as cam, ops, scenes as S
+    sc = CC.scene("observed")
+    H, W = sc["H"], sc["W"]
+    assert len(sc["meshes"]) == 2 and sc["inst_begin"].tolist() == [0, 3, 5]
+    obs = cam.observe_scenes(sc["scenes"], sc["scene_meshes"], np.stack(sc["cam_from_world"]), sc["intrinsics"], H, W, device=dev)
+    assert obs.batch.h_instances.tobytes() == sc["instances"].tobytes()      # the records the neutrality test walks
+    want = CC.spec("observed")
+    assert _same((obs.t, obs.inst, obs.face), want)
+    spec_clouds = cam.pixel_clouds(want[0], want[1], CC.labels(sc), sc["inst_begin"], sc["cameras"], 1)
+    clouds = obs.clouds(1)
+    assert len(obs.clouds(0)) == 2 and all(len(c) > 0 for c in obs.clouds(0))
+    for s in range(2):
+        assert len(spec_clouds[s]) > 50 and clouds[s].is_contiguous() and clouds[s].dtype == torch.float64
+        assert np.array_equal(clouds[s].cpu().numpy().view(np.int64), spec_clouds[s].view(np.int64)), s
+        vol, origin, res = ops.point_cloud_sdf(clouds[s])
+        ref = S.point_cloud_sdf(spec_clouds[s])
+        torch.cuda.synchronize()
+        assert np.array_equal(origin, ref.origin) and res == ref.delta
+        assert torch.equal(vol.cpu(), torch.from_numpy(ref.data)), s
+
+
+def test_no_scene_at_all(dev):
+    """num_scenes == 0 is legal: the render launches nothing and returns empty images; the count writes scene_begin = [0] and the
+    gather nothing.  An inst_begin that does not fit is still rejected."""
+    from omg_planner_amd import _lib, ops
+    sc = CC.scene("box_axis")
+    b = ops.CameraBatch(sc["meshes"], sc["instances"], [0], np.zeros((0, 16)), device=dev)
+    t, inst, face = ops.render_depth(b, 5, 7)
+    assert t.shape == inst.shape == face.shape == (0, 5, 7)
+    points, begin = ops.pixel_clouds(b, t, inst, -1)
+    torch.cuda.synchronize()
+    assert points.shape == (0, 3) and begin.tolist() == [0]
+    for bad in ([5], [-1], [0, 0]):
+        with pytest.raises(_lib.OmgHipError, match="inst_begin"):
+            ops.CameraBatch(sc["meshes"], sc["instances"], bad, np.zeros((0, 16)), device=dev)
