@@ -129,7 +129,30 @@ def _observed():
                 scenes=scenes, scene_meshes=meshes, intrinsics=intr)
 
 
+def _many():
+    """70 scenes of 17 x 18 pixels (2 x 2 tiles each), every one with its own camera; 0..4 instances per scene in a cycle, of the box
+    and icosphere(1) at random affine poses (a scale per axis, the first instance of all mirrored) with z in [-0.1, 0.9] in front
+    of the scene's camera."""
+    rng = np.random.RandomState(70)
+    meshes = [BOX, MC.icosphere(1)]
+    scenes = []
+    for s in range(70):
+        intr = (rng.uniform(14.0, 30.0), rng.uniform(14.0, 30.0), rng.uniform(2.0, 16.0), rng.uniform(2.0, 15.0))
+        cfw = MC.pose(rng.uniform(-0.5, 0.5, 3), rng.uniform(-0.3, 0.3, 3))
+        items = []
+        for _ in range(s % 5):
+            P = MC.pose(rng.uniform(-1.5, 1.5, 3), (rng.uniform(-0.25, 0.25), rng.uniform(-0.25, 0.25), rng.uniform(-0.1, 0.9)))
+            scale = rng.uniform(0.6, 2.5, 3)
+            if not any(len(it) for _, _, it in scenes) and not items:
+                scale[0] = -scale[0]                                    # the mirrored one
+            P[:3, :3] = P[:3, :3] * scale
+            items.append((int(rng.randint(0, 2)), np.linalg.inv(cfw) @ P, int(rng.randint(0, 2))))
+        scenes.append((intr, cfw, items))
+    return build(meshes, scenes, 17, 18)
+
+
 SCENES["observed"] = _observed
+SCENES["many"] = _many
 SCENES.update({f"random{k}": _random(k) for k in range(12)})
 RANDOM = [f"random{k}" for k in range(12)]
 
@@ -176,3 +199,103 @@ def box_slab(pose, cfw, intr, H, W, half=MC.BOX_HALF):
     sign = -np.sign(np.take_along_axis(d, axis[..., None], -1)[..., 0])   # entering through the face the ray runs against
     quad = 2 * axis + (sign > 0)
     return np.where(hit, near, np.inf), np.where(hit, quad, -1)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# synthetic images for the cloud kernels: no render, the instance image is drawn directly
+# ---------------------------------------------------------------------------------------------------------------------
+EDGE_LANES = (0, 63, 64, 127, 128, 191, 192, 255)   # first and last lane of every wave of a group of 256 pixels
+PATTERNS = ("random", "full", "edges", "blocks")
+# (S, H, W) -> the scan entries n = S * groups k_pixel_scan walks (256 per pass, 64 per wave), and the patterns the device runs
+CLOUD_SHAPES = {
+    (63, 5, 7): (63, ("random", "full")), (64, 5, 7): (64, ("random", "edges")), (65, 5, 7): (65, ("random", "blocks")),
+    (255, 3, 3): (255, ("random", "blocks")), (256, 3, 3): (256, ("random", "full")), (257, 3, 3): (257, ("random", "edges")),
+    (600, 5, 7): (600, PATTERNS),
+    (86, 20, 30): (258, PATTERNS),            # 3 groups per scene: 256 = 85 * 3 + 1, a scene boundary off the pass boundary
+    (1, 257, 256): (257, PATTERNS),           # one scene across two passes
+    (2, 1, 33285): (262, ("random", "blocks")),
+    (3, 300, 300): (1056, ("random", "blocks")),
+}
+CLOUD_CASES = [(*shape, pattern) for shape, (_, patterns) in CLOUD_SHAPES.items() for pattern in patterns]
+CLOUD_CLASSES = (9, 0, 1, -1)
+
+
+def synthetic_count(s):
+    """Instances of scene s of a synthetic case: 3, 0, 1, 2, 3, 0, ...  Every fourth scene has none; the cycle starts at 3 so that
+    a case of one scene has the labels 0, 1 and 2 and a case of two has a scene without instances."""
+    return (s + 3) % 4
+
+
+def _random_inst(rng, n, count):
+    """n values uniform in [-2, count + 1]: out of range on both sides."""
+    return rng.randint(-2, count + 2, n).astype(np.int32)
+
+
+def synthetic(S, H, W, pattern, seed):
+    """A scene dict (one box in the pool; scene s owns synthetic_count(s) instances with the labels 0, 1, 2 in order; random
+    intrinsics with the principal point inside the image or outside it and a random posed camera per scene) plus the images
+    `t` [S,H,W] float64 and `inst` [S,H,W] int32 that ops.pixel_clouds / camera.pixel_clouds take.  inst by pattern:
+      random: uniform in [-2, count + 1], a handful of pixels INT32_MAX and INT32_MIN;
+      full:   0 everywhere, also in the scenes without instances (which keep nothing);
+      edges:  -1 except at the row-major pixels p with p % 256 in EDGE_LANES and at the last pixel, which name a valid instance
+              (0 in a scene without instances);
+      blocks: group g (256 row-major pixels) of scene s names valid instances everywhere when (g + s) % 3 == 0, is -1 when it is
+              1 and `random` otherwise.
+    t is uniform(0.1, 2) where a cloud of class -1 keeps the pixel, elsewhere +inf or (one in eight) NaN."""
+    rng = np.random.RandomState(seed)
+    HW = H * W
+    scenes = []
+    for s in range(S):
+        f = rng.uniform(0.5, 2.0) * max(H, W, 8)
+        cx, cy = (rng.uniform(0, W), rng.uniform(0, H)) if rng.rand() < 0.5 else (rng.uniform(-2.0 * W, -1.0), rng.uniform(H + 1.0, 3.0 * H))
+        cfw = MC.pose(rng.uniform(-1.0, 1.0, 3), rng.uniform(-0.5, 0.5, 3))
+        items = [(0, MC.pose(rng.uniform(-1.0, 1.0, 3), rng.uniform(-0.5, 0.5, 3)), i % 3) for i in range(synthetic_count(s))]
+        scenes.append(((f, rng.uniform(0.8, 1.2) * f, cx, cy), cfw, items))
+    sc = build([BOX], scenes, H, W)
+    inst = np.empty((S, HW), np.int32)
+    p = np.arange(HW)
+    for s in range(S):
+        count = synthetic_count(s)
+        valid = rng.randint(0, max(count, 1), HW).astype(np.int32)
+        if pattern == "random":
+            inst[s] = _random_inst(rng, HW, count)
+            at = rng.randint(0, HW, 4)
+            inst[s, at[:2]], inst[s, at[2:]] = np.iinfo(np.int32).max, np.iinfo(np.int32).min
+        elif pattern == "full":
+            inst[s] = 0
+        elif pattern == "edges":
+            inst[s] = np.where(np.isin(p % TILE, EDGE_LANES) | (p == HW - 1), valid, -1)
+        elif pattern == "blocks":
+            kind = (p // TILE + s) % 3
+            inst[s] = np.where(kind == 0, valid, np.where(kind == 1, -1, _random_inst(rng, HW, count)))
+        else:
+            raise ValueError(pattern)
+    counts = np.array([synthetic_count(s) for s in range(S)])[:, None]
+    kept = (inst >= 0) & (inst < counts)
+    t = np.where(kept, rng.uniform(0.1, 2.0, (S, HW)), np.where(rng.rand(S, HW) < 0.125, np.nan, np.inf))
+    return dict(sc, t=t.reshape(S, H, W), inst=inst.reshape(S, H, W), pattern=pattern)
+
+
+_CLOUD, _CLOUD_SPEC = {}, {}
+
+
+def cloud_case(S, H, W, pattern):
+    """synthetic() of a case of CLOUD_CASES, built once; the seed is the case's place in the list."""
+    key = (S, H, W, pattern)
+    if key not in _CLOUD:
+        _CLOUD[key] = synthetic(S, H, W, pattern, 1000 + CLOUD_CASES.index(key))
+        _CLOUD[key]["t"].setflags(write=False), _CLOUD[key]["inst"].setflags(write=False)
+    return _CLOUD[key]
+
+
+def cloud_spec(S, H, W, pattern, cls):
+    """camera.pixel_clouds of a synthetic case -> (scene_begin [S+1], the points of all scenes [N,3]), computed once."""
+    from omg_planner_amd import camera as cam
+    key = (S, H, W, pattern, cls)
+    if key not in _CLOUD_SPEC:
+        sc = cloud_case(S, H, W, pattern)
+        per = cam.pixel_clouds(sc["t"], sc["inst"], labels(sc), sc["inst_begin"], sc["cameras"], cls)
+        flat = np.concatenate(per)
+        flat.setflags(write=False)
+        _CLOUD_SPEC[key] = (np.concatenate([[0], np.cumsum([len(x) for x in per])]).astype(np.int64), flat)
+    return _CLOUD_SPEC[key]

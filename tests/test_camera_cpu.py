@@ -167,6 +167,78 @@ def test_random_scenes_have_hits_background_and_both_labels():
         assert (inst >= 0).any() and (inst < 0).any() and (seen == 0).any() and (seen == 1).any(), name
 
 
+def test_many_scenes_keep_their_promises():
+    """`many` (70 scenes, 0..4 instances in a cycle): a scene without instances is all background, some scene shows both labels,
+    most scenes show something, and the cull changes no bit."""
+    sc = CC.scene("many")
+    t, inst, face = CC.spec("many")
+    counts = np.diff(sc["inst_begin"])
+    assert len(counts) == 70 and counts.tolist() == [s % 5 for s in range(70)] and t.shape == (70, 17, 18)
+    assert {int(m) for m in sc["instances"]["mesh"]} == {0, 1} and len(sc["meshes"]) == 2
+    both = shown = 0
+    for s in range(70):
+        if counts[s] == 0:
+            assert np.isposinf(t[s]).all() and (inst[s] == -1).all() and (face[s] == -1).all(), s
+            continue
+        assert inst[s].max() < counts[s]
+        seen = CC.labels(sc)[sc["inst_begin"][s] + inst[s][inst[s] >= 0]]
+        shown += len(seen) > 0 and (inst[s] < 0).any()
+        both += (seen == 0).any() and (seen == 1).any()
+    assert both >= 1 and shown >= 28                               # at least half of the 56 scenes with instances: hits and background
+    a, b = CC.spec("many", True), CC.spec("many", False)
+    assert np.array_equal(_bits(a[0]), _bits(b[0])) and np.array_equal(a[1], b[1]) and np.array_equal(a[2], b[2])
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the synthetic images of the cloud tests
+# ---------------------------------------------------------------------------------------------------------------------
+def test_synthetic_cloud_cases_keep_their_promises(cam):
+    """Every (shape, pattern) test_gpu_camera.py runs, by the specification alone: the scan has the tabled number of entries; the
+    classes 0, 1 and -1 keep something (`full` names label 0 only) and class 9 nothing; with more than one scene one keeps nothing and one something; `blocks`
+    and `full` have a group with every pixel kept (256 of them wherever the image has as many) and, with more than one scene, a
+    group with none; `edges` keeps exactly the listed lanes and the last pixel; `random` names instances past the scene's count
+    and below -1; a NaN depth lies in no kept pixel."""
+    assert sorted({n for n, _ in CC.CLOUD_SHAPES.values()}) == [63, 64, 65, 255, 256, 257, 258, 262, 600, 1056]
+    assert all(p[0] == "random" and len(p) >= 2 for _, p in CC.CLOUD_SHAPES.values()) and len(CC.CLOUD_CASES) == 28
+    for S, H, W, pattern in CC.CLOUD_CASES:
+        case = (S, H, W, pattern)
+        sc = CC.cloud_case(*case)
+        HW, groups = H * W, -(-H * W // CC.TILE)
+        assert S * groups == CC.CLOUD_SHAPES[(S, H, W)][0], case
+        counts = np.diff(sc["inst_begin"])
+        assert counts.tolist() == [CC.synthetic_count(s) for s in range(S)] and sc["t"].shape == sc["inst"].shape == (S, H, W)
+        assert all(CC.labels(sc)[sc["inst_begin"][s]: sc["inst_begin"][s + 1]].tolist() == [0, 1, 2][: counts[s]] for s in range(S))
+        totals = {cls: int(CC.cloud_spec(*case, cls)[0][-1]) for cls in CC.CLOUD_CLASSES}
+        if pattern == "full":                                    # instance 0 everywhere, whose label is 0: class 1 keeps nothing
+            assert totals[9] == 0 == totals[1] and 0 < totals[0] == totals[-1], (case, totals)
+        else:
+            assert totals[9] == 0 and 0 < totals[0] < totals[-1] and 0 < totals[1] < totals[-1], (case, totals)
+        begin, flat = CC.cloud_spec(*case, -1)
+        per_scene = np.diff(begin)
+        assert np.isfinite(flat).all() and (np.isnan(sc["t"]).any() or totals[-1] == S * H * W), case   # NaN among the dropped pixels
+        if S > 1:
+            assert (per_scene == 0).any() and (per_scene > 0).any() and (per_scene[counts == 0] == 0).all(), case
+        inst = sc["inst"].reshape(S, HW)
+        kept = np.stack([cam.pixel_mask(inst[s], np.zeros(counts[s]), -1) for s in range(S)])
+        assert kept.sum() == totals[-1] and np.isfinite(sc["t"].reshape(S, HW)[kept]).all() and not np.isfinite(sc["t"].reshape(S, HW)[~kept]).any()
+        padded = np.zeros((S, groups * CC.TILE), bool)
+        padded[:, :HW] = kept
+        in_group = padded.reshape(S, groups, CC.TILE).sum(-1)
+        size = np.minimum(CC.TILE, HW - CC.TILE * np.arange(groups))          # pixels of each group: the last may be partial
+        if pattern in ("blocks", "full"):
+            assert (in_group == size).any() and (HW < CC.TILE or (in_group == CC.TILE).any()), case
+            assert S == 1 or (in_group == 0).any(), case
+        if pattern == "blocks" and groups >= 3:
+            assert (in_group == 0).any() and ((in_group > 0) & (in_group < size)).any(), case
+        if pattern == "edges":
+            p = np.arange(HW)
+            listed = np.isin(p % CC.TILE, CC.EDGE_LANES) | (p == HW - 1)
+            assert all(np.array_equal(kept[s], listed if counts[s] else np.zeros(HW, bool)) for s in range(S)), case
+        if pattern == "random":
+            assert (inst >= counts[:, None]).any() and (inst <= -2).any() and (inst == -1).any(), case
+            assert (inst == np.iinfo(np.int32).max).any() and (inst == np.iinfo(np.int32).min).any(), case
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # the kernel bodies compiled for the host
 # ---------------------------------------------------------------------------------------------------------------------

@@ -214,3 +214,111 @@ def test_no_scene_at_all(dev):
     for bad in ([5], [-1], [0, 0]):
         with pytest.raises(_lib.OmgHipError, match="inst_begin"):
             ops.CameraBatch(sc["meshes"], sc["instances"], bad, np.zeros((0, 16)), device=dev)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the cloud kernels on synthetic images: every path of k_pixel_scan, many scenes, instance values that name nothing
+# ---------------------------------------------------------------------------------------------------------------------
+_CLOUD_BATCH = {}
+
+
+def _cloud_batch(S, H, W, pattern, dev):
+    """(CameraBatch, t, inst on the device) of a synthetic case; the batch is shared by the patterns of a shape (the records of
+    CC.synthetic depend on the seed, so it is keyed by the whole case)."""
+    from omg_planner_amd import ops
+    key = (S, H, W, pattern)
+    if key not in _CLOUD_BATCH:
+        sc = CC.cloud_case(*key)
+        b = ops.CameraBatch(sc["meshes"], sc["instances"], sc["inst_begin"], sc["cameras"], device=dev)
+        _CLOUD_BATCH[key] = (b, torch.from_numpy(np.array(sc["t"])).to(dev), torch.from_numpy(np.array(sc["inst"])).to(dev))
+    return _CLOUD_BATCH[key]
+
+
+@pytest.mark.parametrize("S,H,W,pattern", CC.CLOUD_CASES)
+def test_clouds_of_synthetic_images_equal_the_specification(dev, S, H, W, pattern):
+    """Instance images drawn on the host (CC.synthetic: values outside [0, inst_count) on both sides, INT32_MAX and INT32_MIN,
+    scenes without instances, NaN depths in dropped pixels) at the smallest shapes whose scan of S * groups entries reaches the
+    second wave (63, 64, 65 entries), a second pass and its carry (255, 256, 257), three and five passes (600, 1 056), a scene
+    boundary inside a pass (86 scenes of 3 groups, 2 scenes of 131) and one scene across passes (257 groups): scene_begin, the
+    points as int64 bits in pixel order, and a cap above and below the total between sentinels, for a class that keeps nothing
+    (9), labels 0 and 1, and every hit (-1)."""
+    from omg_planner_amd import ops
+    b, t, inst = _cloud_batch(S, H, W, pattern, dev)
+    assert b.num_scenes == S and S * -(-H * W // CC.TILE) == CC.CLOUD_SHAPES[(S, H, W)][0]
+    for cls in CC.CLOUD_CLASSES:
+        begin, flat = CC.cloud_spec(S, H, W, pattern, cls)
+        points, got_begin = ops.pixel_clouds(b, t, inst, cls)
+        torch.cuda.synchronize()
+        assert got_begin.tolist() == begin.tolist(), (cls, np.flatnonzero(got_begin != begin)[:5].tolist())
+        assert points.dtype == torch.float64 and points.shape == (len(flat), 3) and points.is_contiguous()
+        assert np.array_equal(points.cpu().numpy().view(np.int64), flat.view(np.int64)), cls
+        for cap in (len(flat) + 7, max(len(flat) - 5, 0)):
+            view, buf, pad = _guarded((cap, 3), torch.float64, -7.0, dev, pad=30)
+            out, got_begin = ops.pixel_clouds(b, t, inst, cls, out=view)
+            torch.cuda.synchronize()
+            n = min(cap, len(flat))
+            assert out is view and got_begin.tolist() == begin.tolist(), (cls, cap)
+            assert np.array_equal(view[:n].cpu().numpy().view(np.int64), flat[:n].view(np.int64)), (cls, cap)
+            assert (view[n:] == -7.0).all() and (buf[:pad] == -7.0).all() and (buf[-pad:] == -7.0).all(), (cls, cap)
+
+
+def test_cloud_entry_points_stay_inside_exact_buffers(dev):
+    """omgx_pixel_count and omgx_pixel_gather called as ops.pixel_clouds calls them, on 86 scenes of 3 groups (`blocks`), with a
+    workspace of exactly omgx_pixel_clouds_workspace_bytes / 4 int32 and a scene_begin of exactly S + 1, both views inside
+    sentinels: the sentinels on both sides survive each call, and scene_begin and the points are the specification's."""
+    import ctypes as C
+    from omg_planner_amd import _lib
+    from omg_planner_amd.ops import _ptr
+    S, H, W, pattern = 86, 20, 30, "blocks"
+    b, t, inst = _cloud_batch(S, H, W, pattern, dev)
+    l = _lib.lib()
+    n = int(l.omgx_pixel_clouds_workspace_bytes(S, H, W)) // 4
+    assert n == 258
+    for cls in (-1, 1):
+        want_begin, flat = CC.cloud_spec(S, H, W, pattern, cls)
+        ws, ws_buf, pad = _guarded((n,), torch.int32, -9, dev)
+        begin, begin_buf, _ = _guarded((S + 1,), torch.int32, -9, dev)
+        points, points_buf, _ = _guarded((len(flat), 3), torch.float64, -7.0, dev)
+
+        def intact():
+            torch.cuda.synchronize()
+            return all(bool((x[:pad] == fill).all()) and bool((x[-pad:] == fill).all())
+                       for x, fill in ((ws_buf, -9), (begin_buf, -9), (points_buf, -7.0)))
+        assert l.omgx_pixel_count(*b._records(), H, W, _ptr(inst), cls, _ptr(ws), _ptr(begin), None) == _lib.OMGX_OK
+        assert intact(), cls
+        assert begin.cpu().tolist() == want_begin.tolist(), cls
+        assert (ws >= 0).all() and (ws <= len(flat)).all() and (ws[1:] >= ws[:-1]).all()      # the exclusive offsets
+        assert l.omgx_pixel_gather(*b._records(host=False), H, W, _ptr(t), _ptr(inst), cls, _ptr(ws), _ptr(points), len(flat), None) == _lib.OMGX_OK
+        assert intact(), cls
+        assert np.array_equal(points.cpu().numpy().view(np.int64), flat.view(np.int64)), cls
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# many scenes in one render
+# ---------------------------------------------------------------------------------------------------------------------
+def test_seventy_scenes_in_one_render(dev):
+    """`many`: 70 scenes of 2 x 2 tiles with 0..4 instances in a cycle, a camera each, affine poses and a mirrored one: the
+    images equal the specification's with and without the cull, the clouds of the device images (140 scan entries) equal the
+    specification's, and scenes 3, 35 and 69 rendered alone give the bits they have in the batch."""
+    from omg_planner_amd import camera as cam, ops
+    sc = CC.scene("many")
+    H, W, S = sc["H"], sc["W"], 70
+    assert len(sc["cameras"]) == S and (H, W) == (17, 18) and np.diff(sc["inst_begin"]).tolist() == [s % 5 for s in range(S)]
+    assert min(np.linalg.det(np.asarray(p)[:3, :3]) for ps in sc["poses"] for p in ps) < 0       # the mirrored instance
+    b = batch_of("many", dev)
+    for cull in (True, False):
+        got = ops.render_depth(b, H, W, cull=cull)
+        assert got[0].shape == (S, H, W) and _same(got, CC.spec("many", cull)), cull
+        for s in (3, 35, 69):
+            one = CC.single(sc, s)
+            b1 = ops.CameraBatch(one["meshes"], one["instances"], one["inst_begin"], one["cameras"], device=dev)
+            assert _same(ops.render_depth(b1, H, W, cull=cull), [a[s: s + 1] for a in CC.spec("many", cull)]), (cull, s)
+    t, inst, _ = ops.render_depth(b, H, W)
+    want_t, want_inst, _ = CC.spec("many")
+    for cls in (0, 1, -1):
+        want = cam.pixel_clouds(want_t, want_inst, CC.labels(sc), sc["inst_begin"], sc["cameras"], cls)
+        flat = np.concatenate(want)
+        points, begin = ops.pixel_clouds(b, t, inst, cls)
+        torch.cuda.synchronize()
+        assert len(flat) > 0 and begin.tolist() == np.concatenate([[0], np.cumsum([len(w) for w in want])]).tolist(), cls
+        assert np.array_equal(points.cpu().numpy().view(np.int64), flat.view(np.int64)), cls

@@ -16,7 +16,7 @@ def _load(name):
     return mod
 
 
-@pytest.mark.parametrize("tool,trials", [("fuzz_parity", 25), ("fuzz_sdf", 40), ("fuzz_chomp", 80), ("fuzz_learner", 120), ("fuzz_misc", 12)])
+@pytest.mark.parametrize("tool,trials", [("fuzz_parity", 25), ("fuzz_sdf", 40), ("fuzz_chomp", 80), ("fuzz_learner", 120), ("fuzz_misc", 12), ("fuzz_mesh", 12)])
 def test_fuzz_smoke(tool, trials, capsys):
     rc = _load(tool).main(trials=trials, seed=12345)
     out = capsys.readouterr().out

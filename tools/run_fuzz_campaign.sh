@@ -2,12 +2,13 @@
 # Differential fuzz campaigns on the GPU box, one JSON line per campaign (tool, seed, trials, agreeing trials, the tool's own
 # summary line) under gpurun_out/fuzz/ — copy into profiles/fuzz/ so that DESIGN.md section 2's figures can be checked:
 #   gpurun --timeout 3000 -- 'bash tools/run_fuzz_campaign.sh r02 300 400 1000 1000 60 7'
-# arguments: tag, trials of fuzz_parity / fuzz_sdf / fuzz_chomp / fuzz_learner / fuzz_misc, seed
-TAG=${1:-r02}; NP=${2:-200}; NS=${3:-300}; NC=${4:-800}; NL=${5:-800}; NM=${6:-40}; SEED=${7:-7}
+# arguments: tag, trials of fuzz_parity / fuzz_sdf / fuzz_chomp / fuzz_learner / fuzz_misc, seed, trials of fuzz_mesh (0 trials: the tool is left out)
+TAG=${1:-r02}; NP=${2:-200}; NS=${3:-300}; NC=${4:-800}; NL=${5:-800}; NM=${6:-40}; SEED=${7:-7}; NMESH=${8:-40}
 R=${GRAFT_REPO_ROOT:-$(pwd)}
 O=$R/gpurun_out/fuzz
 mkdir -p $O
 run() {  # tool trials
+  [ "$2" = 0 ] && return
   local log=$O/${TAG}_$1_seed${SEED}.log
   local t0=$(date +%s)
   timeout 1500 python3 $R/tests/fuzz/$1.py $2 $SEED > $log 2>&1
@@ -34,3 +35,4 @@ run fuzz_sdf $NS
 run fuzz_chomp $NC
 run fuzz_learner $NL
 run fuzz_misc $NM
+run fuzz_mesh $NMESH
