@@ -2,7 +2,8 @@
 
 Layout (only what the path needs):
   csrc/        hand-written HIP kernels for gfx950 + the C ABI of include/omg_hip.h  -> libomg_hip.so
-  _lib.py      ctypes loader of libomg_hip.so (fails loudly when the library is missing)
+  _header.py   reader of include/omg_hip.h: constants, structs and signatures for the bindings
+  _lib.py      ctypes loader of libomg_hip.so, bound from the header (fails loudly when the library is missing)
   ops.py       thin tensor-level wrappers over the C ABI (torch tensors own the device memory)
   cost.py      `Cost`      — host-side mirror of omg/cost.py's class surface
   optimizer.py `Optimizer` — host-side mirror of omg/optimizer.py's class surface

@@ -20,17 +20,10 @@ from __future__ import annotations
 
 import numpy as np
 
-from . import grasps as _gr
+from . import _lib, grasps as _gr
 
-# omgx_instance (include/omg_hip.h section 14), 136 bytes
-INSTANCE_DTYPE = np.dtype([("m", np.float64, 12),       # rows of obj_from_cam [3,4]
-                           ("centre", np.float64, 3),   # bounding ball in the camera frame
-                           ("q", np.float64),           # |centre|^2 - r2
-                           ("mesh", np.int32), ("label", np.int32)])
-# omgx_camera, 136 bytes
-CAMERA_DTYPE = np.dtype([("fx", np.float64), ("fy", np.float64), ("cx", np.float64), ("cy", np.float64),
-                         ("world_from_cam", np.float64, 12), ("inst_begin", np.int32), ("inst_count", np.int32)])
-assert INSTANCE_DTYPE.itemsize == 136 and CAMERA_DTYPE.itemsize == 136
+# records of omgx_instance and omgx_camera (include/omg_hip.h section 14 explains the fields), 136 bytes each
+INSTANCE_DTYPE, CAMERA_DTYPE = np.dtype(_lib.Instance), np.dtype(_lib.Camera)
 
 
 def camera_rows(intrinsics, cam_from_world) -> np.ndarray:

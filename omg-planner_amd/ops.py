@@ -420,16 +420,16 @@ class DeviceScenes:
         from . import scenes as _sc
         _sc.finish_records(one)  # host mirror: derived constants + the loose region
         l = _lib.lib()
-        fp, ip = C.POINTER(C.c_float), C.POINTER(C.c_int32)
+        vp = C.c_void_p
         with torch.cuda.device(self.device):
-            check(l.omgx_object_set_grid(self._record_ptr(idx), lo.ctypes.data_as(fp), hi.ctypes.data_as(fp), dims.ctypes.data_as(ip),
+            check(l.omgx_object_set_grid(self._record_ptr(idx), lo.ctypes.data_as(vp), hi.ctypes.data_as(vp), dims.ctypes.data_as(vp),
                                          float(np.float32(delta)), int(rec["grid_offset"]), _stream()), "omgx_object_set_grid")
             if fit == "device":
                 need = int(l.omgx_region_scratch_bytes(*shape))
                 if self._scratch is None or self._scratch.numel() < need:
                     self._scratch = torch.empty(need, dtype=torch.uint8, device=self.device)
-                check(l.omgx_fit_influence_region(self._record_ptr(idx), C.c_void_p(slot.data_ptr()), dims.ctypes.data_as(ip),
-                                                  lo.ctypes.data_as(fp), hi.ctypes.data_as(fp), float(rec["epsilon"]), float(rec["clearance"]),
+                check(l.omgx_fit_influence_region(self._record_ptr(idx), C.c_void_p(slot.data_ptr()), dims.ctypes.data_as(vp),
+                                                  lo.ctypes.data_as(vp), hi.ctypes.data_as(vp), float(rec["epsilon"]), float(rec["clearance"]),
                                                   _ptr(self._scratch), _stream()), "omgx_fit_influence_region")
 
     def sync_host(self) -> np.ndarray:
@@ -657,7 +657,7 @@ def goal_ik(robot, P, targets: torch.Tensor, grasp_begin, seeds: torch.Tensor, u
     sols = torch.empty((N, K, T, 7), dtype=torch.float64, device=dev)
     its = torch.empty((N, K, 1 + T if use_standoff else 1), dtype=torch.int32, device=dev) if want_iterations else None
     with torch.cuda.device(dev):
-        check(_lib.lib().omgx_goal_ik(_ptr(robot), P, _ptr(targets), _ptr(d_begin), h_begin.ctypes.data_as(C.POINTER(C.c_int32)), S, N,
+        check(_lib.lib().omgx_goal_ik(_ptr(robot), P, _ptr(targets), _ptr(d_begin), h_begin.ctypes.data_as(C.c_void_p), S, N,
                                       _ptr(seeds), K, T, int(bool(use_standoff)), int(bool(attached)), int(max_iter), float(eps),
                                       float(pinv_eps), float(accept_diff), _ptr(status), _ptr(sols), _ptr(its), _stream()),
               "omgx_goal_ik")
@@ -710,7 +710,7 @@ def select_goals(goals: torch.Tensor, goal_count, collide: "torch.Tensor | None"
     l = _lib.lib()
     with torch.cuda.device(dev):
         ws = _workspace(l.omgx_select_goals_workspace_bytes(S, G), dev) if filter_diversity else None
-        check(l.omgx_select_goals(_ptr(goals), _ptr(d_count), None if h_count is None else h_count.ctypes.data_as(C.POINTER(C.c_int32)),
+        check(l.omgx_select_goals(_ptr(goals), _ptr(d_count), None if h_count is None else h_count.ctypes.data_as(C.c_void_p),
                                   S, G, _ptr(collide), allow, int(bool(filter_diversity)), _ptr(cand), _ptr(counts[0]),
                                   _ptr(counts[1]), _ptr(ws), _stream()), "omgx_select_goals")
     return cand, counts[0], counts[1]
@@ -977,8 +977,8 @@ def point_cloud_sdf(points: torch.Tensor, grid_resolution: float = 0.02, margin:
         torch.autograd.graph.increment_version(out)
     origin = np.ascontiguousarray(lo, np.float64)
     with torch.cuda.device(points.device):
-        check(_lib.lib().omgx_point_cloud_sdf(_ptr(points), points.shape[0], origin.ctypes.data_as(C.POINTER(C.c_double)),
-                                              float(grid_resolution), dims.ctypes.data_as(C.POINTER(C.c_int32)), _ptr(out),
+        check(_lib.lib().omgx_point_cloud_sdf(_ptr(points), points.shape[0], origin.ctypes.data_as(C.c_void_p),
+                                              float(grid_resolution), dims.ctypes.data_as(C.c_void_p), _ptr(out),
                                               _stream()), "omgx_point_cloud_sdf")
     return out, origin, float(grid_resolution)
 

@@ -19,28 +19,9 @@ from dataclasses import dataclass, field
 
 import numpy as np
 
-# numpy mirror of `omgx_object` (include/omg_hip.h), 184 bytes
-OBJECT_DTYPE = np.dtype([
-    ("pose_inv", np.float32, (12,)),
-    ("lo", np.float32, (3,)),
-    ("hi", np.float32, (3,)),
-    ("dim", np.int32, (3,)),
-    ("delta", np.float32),
-    ("epsilon", np.float32),
-    ("padding_scale", np.float32),
-    ("clearance", np.float32),
-    ("disabled", np.int32),
-    ("grid_offset", np.int64),
-    ("inv_extent", np.float64, (3,)),
-    ("rb_c", np.float32, (3,)),
-    ("rb_h", np.float32, (3,)),
-    ("rb_r", np.float32),
-    ("rb_r2", np.float32),
-    ("inv_delta", np.float64),
-    ("inv_2eps", np.float32),
-    ("inv_eps", np.float32),
-], align=True)
-assert OBJECT_DTYPE.itemsize == 184
+from . import _lib
+
+OBJECT_DTYPE = np.dtype(_lib.Object)  # records of `omgx_object` (include/omg_hip.h explains the fields), 184 bytes
 
 
 def finish_records(rec: np.ndarray) -> np.ndarray:

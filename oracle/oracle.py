@@ -11,6 +11,10 @@ from pathlib import Path
 
 import numpy as np
 
+# omgx_chomp_params, omgx_learner_params and OMGX_ALG_* as the package reads them from include/omg_hip.h; omg_oracle.c declares
+# its own, and lib() below checks the two against each other (orc_sizeof_*)
+from omg_planner_amd._lib import ALG, ChompParams, LearnerParams  # noqa: F401
+
 _HERE = Path(__file__).resolve().parent
 _SO = _HERE / "_build" / "libomg_oracle.so"
 
@@ -18,27 +22,6 @@ NUM_LINKS, NUM_DOF, INFO_STRIDE = 10, 9, 16
 INFO_KEYS = ["cost", "obs", "smooth", "weighted_obs", "weighted_smooth", "weighted_obs_grad",
              "weighted_smooth_grad", "grad", "collide", "reach", "terminate", "failure_terminate",
              "execute", "standoff_idx", "violate_limit", "limit_steps"]
-
-
-class ChompParams(C.Structure):
-    """Mirror of `omgx_chomp_params` (include/omg_hip.h)."""
-    _fields_ = [(n, C.c_int32) for n in (
-        "n_waypoints", "n_points", "top_k", "consider_finger", "goal_set_proj", "constraint_num",
-        "use_standoff", "uncheck_finger_collision", "joint_limit_max_steps", "allow_collision_point",
-        "pre_terminate", "do_update")] + [(n, C.c_double) for n in (
-        "time_interval", "obstacle_weight", "smoothness_weight", "step_size", "clip_grad_scale",
-        "terminate_smooth_loss")] + [("link_smooth_weight", C.c_double * NUM_DOF)] + [(n, C.c_void_p) for n in (
-        "waypoint_poses", "start_poses", "end_poses")]
-
-
-class LearnerParams(C.Structure):
-    """Mirror of `omgx_learner_params` (include/omg_hip.h)."""
-    _fields_ = [(n, C.c_int32) for n in ("alg", "num_goals", "n_waypoints", "start_idx", "constraint_num", "use_standoff",
-                                          "normalize_cost", "cost_parts")] + [(n, C.c_double) for n in (
-        "base_obstacle_weight", "smooth_weight", "eta")] + [(n, C.c_void_p) for n in ("goal_pose_table", "end_poses_out")]
-
-
-ALG = {"FTL": 0, "FTC": 1, "Exp": 2, "MD": 3, "Proj": 4}
 
 
 def learner_state_init(S: int, G: int) -> np.ndarray:
