@@ -61,7 +61,6 @@ class ChompEngine:
     # learner and step of a scene in different workgroups of omgx_goal_update_optimize (None: whenever both sets are resident
     # at once, 2 S <= CUs — beyond that the single-workgroup kernel is a little faster; True / False force it)
     split_update = None
-    HOT_FIXED_GOAL = True  # fixed-goal iterations through the prepared calls (_iterate_hot_fixed); False: the general path (A/B, tests)
     # True: iterate() goes through iterate_separate(), the five separate entry points (cross-checks)
     separate_launches = False
     # Under early stop: iterations between rebuilds of the schedule without the terminated scenes (omgx_goalset_schedule, one
@@ -314,6 +313,7 @@ class ChompEngine:
         # a ticket must differ from every value still stored in the flags it is compared with (include/omg_hip.h), whoever
         # launched last — the whole engine, a part, parts of an earlier split.  A one-element list, shared by reference.
         self._ticket_src = [0]
+        self._measure_fence = [None]  # the event behind the last measuring launch of this engine or one of its parts (_goalset_layer)
         with torch.cuda.device(dev):
             self._num_cus = int(_lib.lib().omgx_device_cu_count())  # (torch.cuda.get_device_properties costs 110 ms on its first call)
         if self._num_cus <= 0:
@@ -558,70 +558,103 @@ class ChompEngine:
         """Learner.update_goal (online_learner.py:237-249): omgx_goalset_cost + omgx_goal_update, no host sync.
         defer_update=True launches only the goal-set batch and returns the learner parameters: the caller then runs
         the goal update fused with the optimiser step (omgx_goal_update_optimize)."""
-        self.join()
-        self.t += 1
-        if self.ol_alg == "Baseline":
+        with torch.cuda.stream(self.stream):  # an engine with a stream of its own keeps every launch on it, the one-shot ones too
+            self.join()
+            self.t += 1
+            if self.ol_alg == "Baseline":
+                return None
+            prm = self._learner_params()
+            if self.ol_alg != "Proj":  # cost_vector's obstacle batch (online_learner.py:128-148)
+                n_rem = self.cfg.timesteps - prm.start_idx
+                traj_start = self.traj[:, prm.start_idx]  # strided view into the trajectory tensor: no copy kernel
+                if with_layer:  # the SDF layer of the current trajectories rides on the goal-set launch
+                    self._goalset_layer(prm, self._hot_calls(), self._stream_handle())
+                elif self.latency or self.goal_parts > 1:  # the batch alone as partial sums: the same ones as the fused launch writes
+                    goal_parts, link_groups, block, spread = self._tiling() if self.latency else (self.goal_parts, 5, 0, 0)
+                    self._parts_last = ops.goalset_cost_layer_tiled(
+                        self.robot, self.P, self.scenes, traj_start, self.cv_goals, n_rem, self.cfg.time_interval, None, None,
+                        (self.goal_cost, self.goal_col), soften_fingers=False, active=self._mask(), goal_count=self.goal_count,
+                        goal_parts=goal_parts, layer_link_groups=link_groups, layer_config_block=block, spread=bool(spread), prepass=self.prepass)
+                else:
+                    ops.goalset_cost(self.robot, self.P, self.scenes, traj_start, self.cv_goals, n_rem, self.cfg.time_interval,
+                                     soften_fingers=False, out=(self.goal_cost, self.goal_col), active=self._mask(),
+                                     goal_count=self.goal_count, prepass=self.prepass)
+            elif with_layer:
+                self._layer()
+            if defer_update:
+                return prm
+            ops.goal_update(prm, self.traj, self.goal_set, self.reach, self.goal_cost, self.learner_state, self.goal_idx,
+                            self.end, self.goal_rows, self.goal_point, self.cost_vec, active=self._mask(),
+                            goal_count=self.goal_count, eta=self.eta_s)
             return None
-        prm = self._learner_params()
-        if self.ol_alg != "Proj":  # cost_vector's obstacle batch (online_learner.py:128-148)
-            n_rem = self.cfg.timesteps - prm.start_idx
-            traj_start = self.traj[:, prm.start_idx]  # strided view into the trajectory tensor: no copy kernel
-            if self.latency:
-                self._gs_launches += 1
-                self._parts_last = ops.goalset_cost_layer_tiled(
-                    self.robot, self.P, self.scenes, traj_start, self.cv_goals, n_rem, self.cfg.time_interval,
-                    self.traj if with_layer else None, (self.pot, self.pgrad, self.col), (self.goal_cost, self.goal_col),
-                    soften_fingers=False, layer_soften_fingers=self.cfg.uncheck_finger_collision == -1, active=self._mask(),
-                    goal_count=self.goal_count, goal_parts=self.LAT_GOAL_PARTS, layer_link_groups=self.LAT_LAYER_LINK_GROUPS,
-                    layer_config_block=self.LAT_LAYER_BLOCK, spread=True,
-                    layer_poses=self.wp_pose if (self._poses_on and with_layer) else None, prepass=self.prepass)
-            elif with_layer:  # the SDF layer of the current trajectories rides on the goal-set launch
-                # the second launch is the measuring one (the first runs on cold caches and would distort the weights);
-                # until then the items are split evenly by count.  Small batches keep the even split: measuring only pays
-                # when the launch has several rounds of workgroups per CU.
-                # With an active mask (early stop) the launch goes back to scene-major order, or — `reschedule_every` > 0 — the
-                # schedule is rebuilt from the same measured durations without the scenes that have terminated.
-                self._gs_launches += 1
-                NP = self._np(n_rem)
-                self._parts_last = NP
-                use_sched = self.auto_schedule and (not self._masked or (self._measured and bool(self.reschedule_every)))
-                measure = use_sched and not self._measured and self._gs_launches >= 2 and self.S * self.G * NP >= self.MEASURE_MIN_ITEMS and NP == self._parts_max
-                if use_sched and self._masked:
-                    if self._sched_age is None or self._sched_age >= self.reschedule_every or self._sched_np != NP:
-                        self.schedule = self.build_schedule(active=self._mask(), parts=NP, uniform=(NP != self._parts_max or not self._measured))
-                        self._sched_age = 0
-                    self._sched_age += 1
-                if use_sched and (self.schedule is None or self._sched_np != NP):
-                    # nothing measured yet, or the window has shrunk to another number of parts per goal (the last few iterations
-                    # of a plan): the items in scene-major order, equal counts per XCD
+
+    @staticmethod
+    def _dispatch_rule(auto_schedule: bool, masked: bool, measured: bool, reschedule_every: int, launches: int, items: int, min_items: int,
+                       np_is_max: bool, has_schedule: bool, sched_np_ok: bool, sched_age: "int | None"):
+        """The dispatch-schedule policy of a batch-layout goal-set launch, from plain values -> (use, rebuild, measure, sched_age):
+        does the launch take a schedule, which one is built first (None, "uniform", "masked-uniform", "masked-measured"), does the
+        launch record its workgroups' durations, and the schedule's age afterwards.  `launches` counts this launch, `items` its
+        (scene, goal, part) workgroups, measured from `min_items` (MEASURE_MIN_ITEMS) on; np_is_max: the window still has the plan's
+        first part count; sched_np_ok: the schedule at hand was built for this part count.
+        The second launch is the measuring one (the first runs on cold caches and would distort the weights); until then the items
+        are split evenly by count.  Small batches keep the even split: measuring only pays when the launch has several rounds of
+        workgroups per CU.  With an active mask (early stop) the launch goes back to scene-major order, or — `reschedule_every` > 0 —
+        the schedule is rebuilt from the same measured durations without the scenes that have terminated."""
+        use = auto_schedule and (not masked or (measured and bool(reschedule_every)))
+        measure = use and not measured and launches >= 2 and items >= min_items and np_is_max
+        rebuild = None
+        if use and masked:
+            if sched_age is None or sched_age >= reschedule_every or not sched_np_ok:
+                rebuild = "masked-measured" if np_is_max and measured else "masked-uniform"
+                sched_age = 0
+            sched_age += 1
+        if use and rebuild is None and not (has_schedule and sched_np_ok):
+            # nothing measured yet, or the window has shrunk to another number of parts per goal (the last few iterations of a
+            # plan): the items in scene-major order, equal counts per XCD
+            rebuild = "uniform"
+        return use, rebuild, measure, sched_age
+
+    def _dispatch(self, NP: int):
+        """(schedule, work) of the goal-set launch to come, with NP workgroups per goal: _dispatch_rule's decision carried out.  A
+        schedule is built by a small launch of its own, on this engine's stream like the launch that reads it."""
+        items = self.S * self.G * NP
+        use, rebuild, measure, self._sched_age = self._dispatch_rule(
+            self.auto_schedule, self._masked, self._measured, self.reschedule_every, self._gs_launches, items, self.MEASURE_MIN_ITEMS,
+            NP == self._parts_max, self.schedule is not None, self._sched_np == NP, self._sched_age)
+        if rebuild is not None:
+            with torch.cuda.stream(self.stream):
+                if rebuild == "uniform":
                     self.schedule = self.build_schedule(uniform=True, parts=NP)
-                ops.goalset_cost_layer(self.robot, self.P, self.scenes, traj_start, self.cv_goals, n_rem, self.cfg.time_interval,
-                                       self.traj, (self.pot, self.pgrad, self.col), soften_fingers=False,
-                                       layer_soften_fingers=self.cfg.uncheck_finger_collision == -1,
-                                       out=(self.goal_cost, self.goal_col), active=self._mask(), goal_count=self.goal_count,
-                                       schedule=self.schedule if use_sched else None, work=self.work[: self.S * self.G * NP] if measure else None,
-                                       goal_parts=self.goal_parts, layer_poses=self.wp_pose if self._poses_on else None,
-                                       prepass=self.prepass)
-                if measure:
-                    self._measured = True
-                    self.schedule = self.build_schedule(parts=NP)
-            elif self.goal_parts > 1:  # the batch alone, split goals: the same partial sums as the fused launch writes
-                self._parts_last = ops.goalset_cost_layer_tiled(
-                    self.robot, self.P, self.scenes, traj_start, self.cv_goals, n_rem, self.cfg.time_interval, None, None,
-                    (self.goal_cost, self.goal_col), soften_fingers=False, active=self._mask(), goal_count=self.goal_count,
-                    goal_parts=self.goal_parts, layer_link_groups=5, layer_config_block=0, spread=False, prepass=self.prepass)
-            else:
-                ops.goalset_cost(self.robot, self.P, self.scenes, traj_start, self.cv_goals, n_rem, self.cfg.time_interval,
-                                 soften_fingers=False, out=(self.goal_cost, self.goal_col), active=self._mask(),
-                                 goal_count=self.goal_count, prepass=self.prepass)
-        elif with_layer:
-            self._layer()
-        if defer_update:
-            return prm
-        ops.goal_update(prm, self.traj, self.goal_set, self.reach, self.goal_cost, self.learner_state, self.goal_idx,
-                        self.end, self.goal_rows, self.goal_point, self.cost_vec, active=self._mask(),
-                        goal_count=self.goal_count, eta=self.eta_s)
-        return None
+                else:
+                    self.schedule = self.build_schedule(active=self._mask(), parts=NP, uniform=rebuild == "masked-uniform")
+        return (self.schedule if use else None), (self.work[:items] if measure else None)
+
+    def _dispatch_measured(self, NP: int):
+        """After the measuring launch: all later launches run in the order its durations give."""
+        self._measured = True
+        with torch.cuda.stream(self.stream):
+            self.schedule = self.build_schedule(parts=NP)
+
+    def _goalset_layer(self, prm: _lib.LearnerParams, calls: "ops.IterationCalls", stream: int):
+        """The goal-set batch of the learner's window with the SDF layer of the current trajectories on it (omgx_goalset_cost_layer,
+        _parts or _tiled) through the prepared calls."""
+        self._gs_launches += 1
+        NP = self._parts_last = max(1, int(prm.cost_parts))
+        schedule, work = (None, None) if self.latency else self._dispatch(NP)  # latency mode: tiles spread over the chip, no schedule
+        calls.use_layer_poses = self._poses_on
+        if work is None:
+            calls.goalset_layer(prm.start_idx, self._masked, schedule, None, stream)
+            return
+        # The measuring launch.  The pipeline's parts reach theirs in the same iteration, microseconds apart; side by side they
+        # would time each other's load, and the order built from that stays for the engine's life (bench.py's headline: -0.7 %).
+        # So a part's measuring launch waits for the one before it (one event, shared like the tickets).
+        mine = self.stream if self.stream is not None else torch.cuda.current_stream(self.device)
+        fence = self._measure_fence
+        if fence[0] is not None:
+            mine.wait_event(fence[0])
+        calls.goalset_layer(prm.start_idx, self._masked, schedule, work, stream)
+        fence[0] = mine.record_event()
+        self._dispatch_measured(NP)
 
     def _uniform_schedule(self, parts: int = 1) -> torch.Tensor:
         """The schedule before anything has been measured: the (scene, goal[, part]) items in scene-major order, cut into 8 pieces
@@ -689,19 +722,7 @@ class ChompEngine:
         ops.fk_sdf(self.robot, self.P, self.scenes, self.traj, soften_fingers=self.cfg.uncheck_finger_collision == -1,
                    out=(self.pot, self.pgrad, self.col))
 
-    def _step(self, do_update: bool, learner_prm=None, stop_on_terminate: bool = False):
-        if learner_prm is not None:  # goal update + step in one launch
-            # learner and step in different workgroups of the launch: pays while both sets are resident at once (one
-            # 92 KB-LDS workgroup per CU); beyond that the single-workgroup kernel is a little faster (measured at 200 / 400 scenes)
-            split = 2 * self.S <= self._num_cus if self.split_update is None else bool(self.split_update)
-            ticket = self._next_ticket()
-            ops.goal_update_optimize(learner_prm, self.goal_set, self.reach, self.goal_cost, self.learner_state, self.goal_idx,
-                                     self.robot, self._params(do_update), self.traj, self.start, self.end, self.goal_rows,
-                                     self.goal_point, self.pot, self.pgrad, self.col, active=self.active,
-                                     out=(self.grad, self.cost_traj, self.info), cost_vector=self.cost_vec,
-                                     scene_flags=self._scene_flags if split else None, ticket=ticket,
-                                     stop_on_terminate=stop_on_terminate, goal_count=self.goal_count, eta=self.eta_s)
-            return self.info
+    def _step(self, do_update: bool, stop_on_terminate: bool = False):
         ops.chomp_optimize(self.robot, self._params(do_update), self.traj, self.start, self.end, self.goal_rows,
                            self.goal_point, self.pot, self.pgrad, self.col, active=self.active,
                            out=(self.grad, self.cost_traj, self.info), stop_on_terminate=stop_on_terminate)
@@ -714,95 +735,62 @@ class ChompEngine:
         self._layer()
         return self._step(do_update)
 
+    def _selects(self, t: int) -> bool:
+        """planner.py:609-618: the learner runs only for the online-learning rules and only for the first optim_steps iterations;
+        "Proj" and "Baseline" keep the goal that was fixed before planning (select_initial_goal)."""
+        return bool(self.cfg.goal_set_proj and t < self.cfg.optim_steps and self.ol_alg not in ("Baseline", "Proj"))
+
+    def _split(self) -> bool:
+        """Learner and step in different workgroups of omgx_goal_update_optimize: pays while both sets are resident at once (one
+        92 KB-LDS workgroup per CU); beyond that the single-workgroup kernel is a little faster (measured at 200 / 400 scenes)."""
+        return 2 * self.S <= self._num_cus if self.split_update is None else bool(self.split_update)
+
+    def _stream_handle(self) -> int:
+        """The HIP stream of this engine's launches: its own, else torch's current one."""
+        return (self.stream if self.stream is not None else torch.cuda.current_stream(self.device)).cuda_stream
+
     def iterate(self, t: int, early_stop: bool = False):
-        """One pass of the planner loop body (planner.py:612-621) over all scenes: two launches on one stream —
-        omgx_goalset_cost_layer (goal-set batch + SDF layer of the current trajectories) and omgx_goal_update_optimize
-        (Learner.update_goal + Optimizer.optimize); once the goal is fixed (t >= optim_steps, "Proj", "Baseline") the layer
-        launch and the step."""
+        """One pass of the planner loop body (planner.py:612-621) over all scenes: two launches on one stream through the prepared
+        calls (ops.IterationCalls) — omgx_goalset_cost_layer (goal-set batch + SDF layer of the current trajectories) and
+        omgx_goal_update_optimize (Learner.update_goal + Optimizer.optimize); once the goal is fixed (t >= optim_steps, "Proj",
+        "Baseline") the layer launch and the step."""
         k = self._pipeline_parts()
-        cfg = self.cfg
-        if k > 1 and self.SMOOTH_SINGLE_PART_BELOW > self.S and not (cfg.goal_set_proj and t < cfg.optim_steps and self.ol_alg not in ("Baseline", "Proj")) \
-                and self.HOT_FIXED_GOAL and not self.separate_launches and self.stream is None:
+        select = self._selects(t)
+        if k > 1 and self.SMOOTH_SINGLE_PART_BELOW > self.S and not select and not self.separate_launches and self.stream is None:
             self.join()  # (the side streams are joined once, at the phase's first iteration; scenes are independent: the same bits)
             k = 1
         if k > 1:
             return self._iterate_pipelined(t, early_stop, k)
-        # planner.py:609-618: the learner runs only for the online-learning rules and only for the first optim_steps iterations
-        select = cfg.goal_set_proj and t < cfg.optim_steps and self.ol_alg not in ("Baseline", "Proj")
-        if not self.separate_launches and select and not self._forked:
-            if early_stop:
-                self._masked = True
-            if self._iterate_hot(bool(early_stop and t > 0)):
-                return None
-        elif self.HOT_FIXED_GOAL and not self.separate_launches and not self._forked and not select:
-            # the goal is fixed (the plan's last cfg.extra_smooth_steps iterations; "Proj" / "Baseline" throughout): layer launch + step
-            # through the prepared calls
-            if early_stop:
-                self._masked = True
-            self._iterate_hot_fixed(bool(early_stop and t > 0))
-            return None
-        if self.stream is not None and torch.cuda.current_stream(self.device) != self.stream:
-            with torch.cuda.stream(self.stream):
-                return self._iterate_general(t, early_stop)
-        return self._iterate_general(t, early_stop)
-
-    def _iterate_general(self, t: int, early_stop: bool):
         self.join()
         if self.separate_launches:
-            return self.iterate_separate(t, early_stop)
-        cfg = self.cfg
-        # planner.py:609-618: the learner runs only for the online-learning rules; "Proj" and "Baseline" keep the goal that
-        # was fixed before planning (select_initial_goal)
-        select = cfg.goal_set_proj and t < cfg.optim_steps and self.ol_alg not in ("Baseline", "Proj")
+            with torch.cuda.stream(self.stream):  # the one-shot wrappers enqueue on torch's current stream
+                return self.iterate_separate(t, early_stop)
+        if early_stop:
+            self._masked = True
         # planner.py:626-627 (a scene that terminates at t > 0 leaves the loop): the step itself clears active[s] — no extra
         # kernels between iterations; the goal-set launch, the goal update and the step skip scenes with active[s] == 0
         stop = bool(early_stop and t > 0)
-        if early_stop:
-            self._masked = True
+        calls, stream = self._hot_calls(), self._stream_handle()
         if select:
-            lprm = self.update_goal(defer_update=True, with_layer=True)
+            self.t += 1
+            prm = self._learner_params()
+            self._goalset_layer(prm, calls, stream)
             self._schedule()
-            self._step(True, lprm, stop_on_terminate=stop)
+            calls.update(prm, self._params(True), self._split(), self._next_ticket(), stop, stream)
         else:
-            self._layer()
+            calls.use_layer_poses = self._poses_on
+            calls.layer_only(stream)
             self._schedule()
-            self._step(True, None, stop_on_terminate=stop)
+            calls.step(self._params(True), stop, stream)
 
-    _HOT_TENSORS = ("robot", "cv_goals", "traj", "pot", "pgrad", "col", "goal_cost", "goal_col", "goal_set", "reach", "learner_state",
-                    "goal_idx", "start", "end", "goal_rows", "goal_point", "grad", "cost_traj", "info", "cost_vec", "_active",
-                    "goal_count", "eta_s", "_scene_flags")
-
-    def _iterate_hot(self, stop: bool) -> bool:
-        """A goal-selecting iteration in its steady state — schedule settled (or none), nothing to measure — through
-        ops.IterationCalls: the same two launches with argument lists prepared once, on this engine's stream without
-        switching torch's current stream.  Returns False when the general path has to run (first launches of a plan, schedule
-        rebuilds, the rules without a goal-set batch)."""
-        if self.ol_alg in ("Baseline", "Proj"):
-            return False
-        use_sched = self.auto_schedule and not self._masked and not self.latency
-        if not self.latency and self._masked and self.auto_schedule and self._measured and self.reschedule_every:
-            return False
-        if use_sched:
-            cfg = self.cfg
-            NP = self._np(cfg.timesteps - min(int(((self.t + 1) / cfg.optim_steps) * cfg.timesteps), cfg.timesteps - 1))  # the window of the launch to come
-            if self.schedule is None or self._sched_np != NP or (not self._measured and self._gs_launches >= 1 and self.S * self.G * self._parts_max >= self.MEASURE_MIN_ITEMS):
-                return False
-        calls = self._hot_calls()
-        stream = (self.stream if self.stream is not None else torch.cuda.current_stream(self.device)).cuda_stream
-        self.t += 1
-        prm = self._learner_params()
-        self._gs_launches += 1
-        self._parts_last = max(1, int(prm.cost_parts))
-        calls.use_layer_poses = self._poses_on
-        calls.goalset_layer(prm.start_idx, self._masked, self.schedule if use_sched else None, None, stream)
-        self._schedule()
-        split = 2 * self.S <= self._num_cus if self.split_update is None else bool(self.split_update)
-        calls.update(prm, self._params(True), split, self._next_ticket(), stop, stream)
-        return True
+    # the tensors the prepared calls hold pointers of (one C-level fetch per iteration)
+    _HOT_TENSORS = operator.attrgetter("robot", "cv_goals", "traj", "pot", "pgrad", "col", "goal_cost", "goal_col", "goal_set", "reach", "learner_state",
+                                       "goal_idx", "start", "end", "goal_rows", "goal_point", "grad", "cost_traj", "info", "cost_vec", "_active",
+                                       "goal_count", "eta_s", "_scene_flags", "scenes.scene_begin")
 
     def _hot_calls(self) -> "ops.IterationCalls":
         # the prepared calls belong to these very tensor objects (held here, so none of them can be freed and its identity reused)
-        key = [getattr(self, k) for k in self._HOT_TENSORS] + [self.scenes.scene_begin]
+        key = self._HOT_TENSORS(self)
         baked = (float(self.cfg.time_interval), self.cfg.uncheck_finger_collision == -1)  # the scalars the calls carry
         hot = self._hot
         if hot is None or hot[2] != baked or not all(map(operator.is_, hot[0], key)):
@@ -817,33 +805,17 @@ class ChompEngine:
             hot = self._hot = (key, calls, baked)
         return hot[1]
 
-    def _iterate_hot_fixed(self, stop: bool):
-        """An iteration with the goal fixed — the layer launch and the step (`_layer()` + `_step()` of the general path: the same two
-        entry points on the same tensors) — through ops.IterationCalls, on this engine's stream without switching torch's current
-        stream.  The general path costs ~50 us of host time per part and iteration (argument checks, stream context), more than
-        the two launches need on the device: the last 20 iterations of a pipelined plan were bound by the host (kernel trace of a
-        100-scene plan: a part's period 150 us against 58 us of kernels)."""
-        calls = self._hot_calls()
-        stream = (self.stream if self.stream is not None else torch.cuda.current_stream(self.device)).cuda_stream
-        calls.use_layer_poses = self._poses_on
-        calls.layer_only(stream)
-        self._schedule()
-        calls.step(self._params(True), stop, stream)
-
     def iterate_separate(self, t: int, early_stop: bool = False):
         """The same iteration composed from the separate entry points the drop-in classes use — omgx_goalset_cost,
         omgx_goal_update, omgx_fk_sdf, omgx_chomp_optimize (five launches).  Same results as iterate(); kept as the
         cross-check of the fused launches (tests) and as the reference composition for callers of the C ABI."""
-        cfg = self.cfg
-        select = cfg.goal_set_proj and t < cfg.optim_steps and self.ol_alg not in ("Baseline", "Proj")
-        stop = bool(early_stop and t > 0)
         if early_stop:
             self._masked = True
         self._layer()
-        if select:
+        if self._selects(t):
             self.update_goal()
         self._schedule()
-        self._step(True, None, stop_on_terminate=stop)
+        self._step(True, stop_on_terminate=bool(early_stop and t > 0))
 
     # ---------------------------------------------------------------------------------------------
     # The persistent planner launch (omgx_plan_persistent, csrc/omg_persist.h): K iterations of iterate() for all scenes in ONE
@@ -861,7 +833,7 @@ class ChompEngine:
         cfg = self.cfg
         recs = (_lib.PlanIter * len(ts))()
         for k, t in enumerate(ts):
-            select = bool(cfg.goal_set_proj and t < cfg.optim_steps and self.ol_alg not in ("Baseline", "Proj"))
+            select = self._selects(t)
             r = recs[k]
             if select:
                 if pin_window:

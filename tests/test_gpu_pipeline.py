@@ -123,7 +123,7 @@ def test_prepared_iteration_calls_check_their_tensors(dev):
         build(goal_idx=e.goal_idx.long())
     with pytest.raises(_lib.OmgHipError):
         build(active=e._active[:-1])
-    # the engine builds new calls when one of its tensors is rebound, and the result stays that of the general path
+    # the engine builds new calls when one of its tensors is rebound, and the result stays that of the separate entry points
     ref = make()
     for t in range(5):
         e.iterate(t)
@@ -177,20 +177,17 @@ def test_whole_plan_at_bench_size_follows_the_oracle(dev):
 
 @pytest.mark.parametrize("S,early,alg", [(48, True, "MD"), (3, False, "MD"), (6, True, "Proj")])
 def test_fixed_goal_iterations_through_the_prepared_calls_leave_the_same_bits(dev, S, early, alg):
-    """The plan's last cfg.extra_smooth_steps iterations (goal fixed: layer launch + step) run through ops.IterationCalls
-    (ChompEngine._iterate_hot_fixed) instead of the general path's checked calls: same entry points, same tensors, same bits —
-    pipelined and not, with and without the early stop, and for a rule that never selects a goal."""
+    """The plan's last cfg.extra_smooth_steps iterations (goal fixed: layer launch + step) run through ops.IterationCalls; the
+    engine with separate_launches composes the same plan from the checked one-shot wrappers: same tensors, same bits — pipelined
+    and not, with and without the early stop, and for a rule that never selects a goal."""
     import bench
     from omg_planner_amd.engine import ChompEngine
     cfg, model, batch, start, goals = bench.build_workload(S, 64, 30, 32, 0, False)
     out = []
-    try:
-        for hot in (True, False):
-            ChompEngine.HOT_FIXED_GOAL = hot
-            e = ChompEngine.auto(model, batch, copy.deepcopy(cfg), start, goals, device=dev, ol_alg=alg)
-            e.plan(early_stop=early)
-            torch.cuda.synchronize()
-            out.append(e)
-    finally:
-        ChompEngine.HOT_FIXED_GOAL = True
+    for separate in (False, True):
+        e = ChompEngine.auto(model, batch, copy.deepcopy(cfg), start, goals, device=dev, ol_alg=alg)
+        e.separate_launches = separate
+        e.plan(early_stop=early)
+        torch.cuda.synchronize()
+        out.append(e)
     _assert_same(out[0], out[1])

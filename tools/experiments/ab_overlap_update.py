@@ -47,7 +47,7 @@ def main():
                 prm = e.update_goal(defer_update=True, with_layer=True)   # the goal-set + layer launch
             with torch.cuda.stream(U):
                 e._schedule()
-                e._step(True, prm)                                        # the update launch, beside it (no dependency: timing only)
+                e._hot_calls().update(prm, e._params(True), e._split(), e._next_ticket(), False, e._stream_handle())  # the update launch, beside it (no dependency: timing only)
             A.wait_stream(U)                                              # the next goal-set launch waits for both
             U.wait_stream(A)
 
