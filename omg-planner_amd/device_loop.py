@@ -17,7 +17,12 @@ Through the classes' stand-alone paths that loop costs an upload, two launches, 
   — goal-set + layer launch, omgx_goal_update, a small download — and optimize() then runs the step alone on the layer that
   launch left;
 * host-side changes between the calls (a new `traj.data`, start, goal index, goal set) are found by comparing against the
-  mirrors of what the device holds (a few hundred doubles) and uploaded.
+  mirrors of what the device holds (a few hundred doubles) and uploaded;
+* a deferred update_goal() is a promise about the host state AT THE MOMENT IT WAS CALLED (the reference did the work there and
+  then).  Whatever would change what the update reads — an upload of the trajectory or the start, a rebuilt object table, a
+  rebuilt loop, a host override of `traj.goal_idx` / `traj.end` — first runs the pending update on its own (flush()) against
+  the device state it was promised on, which the device still holds in all these cases.  The one thing the device does not
+  keep is an SDF volume written in place through env.sdf_torch between the two calls: the update then sees the new values.
 
 Same kernels, same arithmetic as the stand-alone paths (one scene in the latency-mode tiling: a goal's cost is the float32
 sum of its parts' sums); there is no CPU path here either.
@@ -124,13 +129,17 @@ class LazyBool(_Promise):
 class _LazyEnd:
     """`traj.end` after a deferred update: the chosen goal configuration [9], a numpy array on first use."""
 
-    def __init__(self, loop, promise):
-        self._loop, self._promise, self._value = loop, promise, None
+    def __init__(self, loop, promise, goal_set=None):
+        # goal_set: the array traj.goal_set named when update_goal() was called.  The reference's `traj.end = traj.goal_set[idx]`
+        # is a view of THAT array: it follows a later in-place edit of it and keeps its values when traj.goal_set is replaced.
+        self._loop, self._promise, self._goal_set, self._value = loop, promise, goal_set, None
         self.shape, self.dtype, self.ndim = (9,), np.dtype(np.float64), 1
 
     def _get(self):
         if self._value is None:
-            self._value = np.array(self._loop.traj_obj.goal_set[int(self._promise)], np.float64)
+            row = (self._goal_set if self._goal_set is not None else self._loop.traj_obj.goal_set)[int(self._promise)]
+            self._value = row if type(row) is np.ndarray and row.dtype == np.float64 else np.array(row, np.float64)
+            self._goal_set = None
         return self._value
 
     def __array__(self, dtype=None, copy=None):
@@ -202,6 +211,7 @@ class DeviceLoop:
         c = self.c
         # private copies: an in-place edit of traj.goal_set / reach_grasps on the host is found by comparing bytes (matches())
         self._goal_set_host, self._reach_host = goal_set.copy(), (np.array(reach, np.float64) if self.reach is not None else None)
+        self._goal_set_bytes, self._reach_bytes = self._goal_set_host.tobytes(), (self._reach_host.tobytes() if self.reach is not None else None)
         # ---- one device buffer, one pinned mirror: [start | traj | grad | cost_traj | info | end | goal rows | goal point | goal index]
         slots = [("start", (1, 9)), ("traj", (1, n, 9)), ("grad", (1, n, 9)), ("cost_traj", (1, n)), ("info", (1, _lib.INFO_STRIDE)),
                  ("end", (1, 9)), ("rows", (1, c, 9)), ("gp", (1, 9)), ("idx", (2,))]
@@ -252,16 +262,31 @@ class DeviceLoop:
     def h(self, name):
         return self._h[name]
 
+    def release(self, traj):
+        """Optimizer.optimize() found that matches(traj) fails.  If this is still the loop of `traj`, the goal arrays (or the
+        window, or the robot's points) changed under it: a pending update runs now, on the device state it was promised on, and
+        the learner builds its next loop from the host arrays — so that both halves of an iteration read the same goals."""
+        if traj is self.traj_obj:
+            if self._pending is not None:
+                self.flush()
+            if self.learner.__dict__.get("_loop") is self:
+                self.learner._goals_key = None
+
     def matches(self, traj) -> bool:
         """Is this loop still about `traj` with the goal arrays (and the robot points) it was built from?"""
         if traj is not self.traj_obj or int(self.cfg.timesteps) != self.n or self.cost._robot_model()[1] is not self.robot:
             return False
-        gs = traj.goal_set
-        if gs is not None and (len(gs) != self.G or not np.array_equal(np.asarray(gs, np.float64), self._goal_set_host)):
-            return False
+        gs = traj.goal_set  # (bytes, not np.array_equal: one memcmp instead of several microseconds of numpy dispatch per call)
+        if gs is not None:
+            if not (type(gs) is np.ndarray and gs.dtype == np.float64):
+                gs = np.asarray(gs, np.float64)
+            if gs.shape != self._goal_set_host.shape or gs.tobytes() != self._goal_set_bytes:
+                return False
         if self._reach_host is not None:
-            r = np.asarray(self.learner.env.objects[self.learner.env.target_idx].reach_grasps, np.float64)
-            if r.shape != self._reach_host.shape or not np.array_equal(r, self._reach_host):
+            r = self.learner.env.objects[self.learner.env.target_idx].reach_grasps
+            if not (type(r) is np.ndarray and r.dtype == np.float64):
+                r = np.asarray(r, np.float64)
+            if r.shape != self._reach_host.shape or r.tobytes() != self._reach_bytes:
                 return False
         return True
 
@@ -270,6 +295,8 @@ class DeviceLoop:
         scenes = self.cost._scenes()
         key = (id(scenes), id(self.robot), float(self.cfg.time_interval), self.cfg.uncheck_finger_collision == -1)
         if self._calls is None or self._calls_key != key:
+            if self._pending is not None and self._calls is not None:
+                self.flush()  # promised on the table of the moment update_goal() was called: self._calls still addresses it
             self._calls = ops.IterationCalls(self.robot, self.P, scenes, self.cv_goals, self.cfg.time_interval, self.d("traj"),
                                              (self.pot, self.pgrad, self.col), (self.gcost, self.gcol), self.goal_set, self.reach,
                                              self.state, self.d("idx")[:1], self.d("start"), self.d("end"), self.d("rows"), self.d("gp"),
@@ -305,11 +332,15 @@ class DeviceLoop:
             raise _lib.OmgHipError(f"trajectory has shape {data.shape}, cfg.timesteps is {self.n}")
         b = data.tobytes()
         if b != self._m_traj:
+            if self._pending is not None:
+                self.flush()  # the pending update is about the trajectory the device still holds
             self._upload("traj", data)
             self._m_traj = b
             self._layer_valid = False
         b = np.asarray(traj.start, np.float64).tobytes()
         if b != self._m_start:
+            if self._pending is not None:
+                self.flush()
             self._upload("start", np.frombuffer(b, np.float64))
             self._m_start = b
 
@@ -335,6 +366,7 @@ class DeviceLoop:
         if self._pending is not None:
             self.flush()
         self.sync_inputs(self.traj_obj)  # the update is about the trajectory of THIS moment
+        self._prepared()                 # ... and about the scene of this moment: flush() uses the table this leaves
         old = self.traj_obj.goal_idx
         idx, changed = LazyIndex(self), LazyBool(self)
         self._pending = (lprm, idx, changed, old)
@@ -365,7 +397,7 @@ class DeviceLoop:
         if pend is None:
             return
         lprm = pend[0]
-        calls, st = self._prepared(), self._stream()
+        calls, st = self._calls, self._stream()  # the calls defer_update() prepared, NOT those of the scene as it is now
         with self._on_device():
             if lprm.alg != _lib.ALG["Proj"]:
                 calls.goalset_layer(lprm.start_idx, False, None, None, st)
@@ -380,7 +412,14 @@ class DeviceLoop:
     def optimize(self, traj, prm, goal_rows, goal_point):
         """One Optimizer.optimize call; the results are in the host views until the next call.  goal_rows / goal_point: callables
         giving the reference's host-side choice (optimizer.py:93-99), evaluated only when the step runs without the learner."""
-        self.sync_inputs(traj)
+        pend = self._pending
+        if pend is not None:
+            # a host override of the goal after update_goal() (traj.goal_idx = k; traj.end = traj.goal_set[k]) rules the step, as in
+            # the reference: the learner's update runs on its own and the step takes the host's goal
+            end = traj.end
+            if traj.goal_idx is not pend[1] or not (type(end) is _LazyEnd and end._promise is pend[1]):
+                self.flush()
+        self.sync_inputs(traj)  # (either of these two runs a pending update first if it finds something to upload / rebuild)
         calls, st = self._prepared(), self._stream()
         pend = self._pending
         with self._on_device():

@@ -72,13 +72,15 @@ class Learner(object):
         reach = self.env.objects[self.env.target_idx].reach_grasps
         key = (id(self.traj.goal_set), np.asarray(self.traj.goal_set).shape, id(reach), bool(self.cfg.use_standoff), int(self.cfg.timesteps))
         loop = self._loop
-        if loop is None or self._goals_key != key or self.cost._robot_model()[1] is not loop.robot:
+        # matches(): the CONTENTS of the goal arrays too — an in-place edit of traj.goal_set / reach_grasps keeps every id
+        if loop is None or self._goals_key != key or not loop.matches(self.traj):
             old = loop
             if old is not None and old._pending is not None:
-                old.flush()
+                old.flush()  # on the goals the update was promised on
             loop = DeviceLoop(self.cost, self)
             if old is not None and old.state.shape == loop.state.shape:
                 loop.state.copy_(old.state)
+                loop.state_dirty = old.state_dirty
             elif self.__dict__.pop("_push_state", False):  # reset(): the host attributes are the truth, the device follows
                 import torch
                 hv, G = self.__dict__["_hv"], self.N
@@ -195,7 +197,7 @@ class Learner(object):
             from .device_loop import _LazyEnd
             idx, changed = loop.defer_update(self._params(self.alg_name, tiled=True))
             self.traj.goal_idx = idx
-            self.traj.end = _LazyEnd(loop, idx)
+            self.traj.end = _LazyEnd(loop, idx, self.traj.goal_set)
             return changed
         goal_idx_old = self.traj.goal_idx
         self.traj.goal_idx = self.update_goal_dist()  # np.argmax(self.p) with numpy's NaN / tie rules, taken on the device

@@ -68,7 +68,10 @@ class Optimizer(object):
             return np.asarray(traj.goal_set[idx], np.float64)[None]
         do_update = 0 if info_only else (1 if force_update else 2)
         loop = getattr(cost, "_loop", None)
-        if loop is not None and loop.matches(traj):
+        if loop is not None and not loop.matches(traj):
+            loop.release(traj)  # goal arrays edited under the loop: a pending update runs first, the learner rebuilds its loop
+            loop = None
+        if loop is not None:
             # the planner loop's fast path (device_loop.DeviceLoop): trajectory, goal set and learner state stay on the device; a
             # deferred Learner.update_goal() rides on this call's launches; one download
             if cfg.goal_set_proj:

@@ -25,6 +25,9 @@ branches), compute_smooth_loss, compute_total_loss, batch_obstacle_cost, Optimiz
 of the small numpy methods (Optimizer.update / goal_set_projection / compute_traj_v / handle_joint_limit / check_joint_limit,
 Cost.forward_points / color_point).
 
+plan_edit_*.npz: the planner loop under the host-edit scripts of tests/plan_edits.py (run_plan_edit_cases; the two scenes they use
+are stored once, plan_edit_scene_<seed>.npz).
+
 The fixtures are data only (inputs + the reference's outputs); no reference source is stored.
 """
 from __future__ import annotations
@@ -571,7 +574,10 @@ def main(out_dir=OUT, script=None):
         print(f"learner_{alg}_{int(use_standoff)}{tag}.npz  goal_idx {idxs}")
 
     # ---- (ix) the whole planner loop: Learner.__init__ + Planner.plan (omg/planner.py:600-653), free-running ----------
-    def run_plan_case(name, scene_seed, G, alg, use_standoff, cfg_over=None):
+    def run_plan_case(name, scene_seed, G, alg, use_standoff, cfg_over=None, edits=None, iters=None, save=True):
+        """edits: a script of tests/plan_edits.py, applied to the reference's own objects at the two points of each iteration
+        (window 0 before update_goal(), window 1 between update_goal() and optimize()); iters caps the loop.  Returns the record."""
+        from tests import plan_edits as PE
         reset_cfg(cfg, timesteps=30, ol_alg=alg, use_standoff=use_standoff, **(cfg_over or {}))
         scene = small_scene(sc, scene_seed)
         env, sdf, lim = make_env(cfg, kin, model, scene)
@@ -579,24 +585,58 @@ def main(out_dir=OUT, script=None):
         goals = goal[None] + np.concatenate([r.normal(0, 0.15, size=(G, 7)), np.zeros((G, 2))], 1)
         reach = np.stack([np.concatenate([sc.linear_init(g - np.array([0.1, -0.05, 0.1, 0.15, 0, -0.1, 0.1, 0, 0]), g, 4), g[None]], 0)
                           for g in goals])
+        # the loop's inputs as they are BEFORE any edit: the edits work in place on the very arrays the objects hold
+        inputs = dict(goal_set=goals.copy(), reach_grasps=reach.copy(), start=start.copy())
+        scene_rec = {k: np.array(v) for k, v in scene_arrays(scene, sdf, lim).items()}
+        if edits is not None:  # a moved object must not move the scene of the next case
+            for o in env.objects:
+                o.pose_mat = np.array(o.pose_mat)
         env.objects[env.target_idx].reach_grasps = reach
         c = cost_mod.Cost(env)
-        traj = Traj(cfg, np.zeros((30, 9)), start, goals[0], goal_set=goals, goal_idx=0)
-        # Trajectory.interpolate_waypoints (core.py:60-76) with the reference's own util function
-        traj.interpolate_waypoints = lambda waypoints=None, mode="cubic": traj.set(
-            util.interpolate_waypoints(np.stack([traj.start, traj.end]), cfg.timesteps, 9, mode=mode))
-        traj.interpolate_waypoints()
-        learner = LEARNER_MOD.Learner(env, traj, c)  # picks the initial goal and re-interpolates (online_learner.py:96-102)
-        optim = opt_mod.Optimizer(types.SimpleNamespace(config=cfg, robot=env.robot), c)
-        rec = dict(goal_set=goals, reach_grasps=reach, start=start, collision_points=model.collision_points, alg=np.array(alg),
+
+        def new_traj(s, gs):
+            # Trajectory.interpolate_waypoints (core.py:60-76) with the reference's own util function
+            tr = Traj(cfg, np.zeros((30, 9)), s, gs[0], goal_set=gs, goal_idx=0)
+            tr.interpolate_waypoints = lambda waypoints=None, mode="cubic": tr.set(
+                util.interpolate_waypoints(np.stack([tr.start, tr.end]), cfg.timesteps, 9, mode=mode))
+            tr.interpolate_waypoints()
+            return tr
+
+        def new_optimizer():
+            return opt_mod.Optimizer(types.SimpleNamespace(config=cfg, robot=env.robot), c)
+
+        def new_learner(tr):
+            return LEARNER_MOD.Learner(env, tr, c)
+
+        traj = new_traj(start, goals)
+        learner = new_learner(traj)  # picks the initial goal and re-interpolates (online_learner.py:96-102)
+        optim = new_optimizer()
+        rec = dict(inputs, collision_points=model.collision_points, alg=np.array(alg),
                    init_goal_idx=np.int64(traj.goal_idx), init_traj=np.array(traj.data), cfg_dt=np.float64(cfg.time_interval),
                    cfg_use_standoff=np.int64(use_standoff), optim_steps=np.int64(cfg.optim_steps),
                    extra_smooth_steps=np.int64(cfg.extra_smooth_steps))
-        history, infos, selected = [], [], []
+        history, infos, selected, picked, changed, ps = [], [], [], [], [], []
         alg_switch = alg not in ("Baseline", "Proj")
-        for t in range(cfg.optim_steps + cfg.extra_smooth_steps):  # planner.py:612-630
+        rng, applied = PE.make_rng(), 0
+
+        def apply(t, window):
+            nonlocal traj, learner, optim, applied
+            for f in PE.due(edits or [], t, window):
+                out = f(env, traj, learner, c, cfg, rng)
+                applied += 1
+                if isinstance(out, PE.Replan):
+                    traj, learner, optim = PE.apply_replan(out, env, c, learner, optim, new_traj, new_optimizer, new_learner)
+
+        total = cfg.optim_steps + cfg.extra_smooth_steps
+        for t in range(total if iters is None else min(iters, total)):  # planner.py:612-630
+            apply(t, 0)
             if cfg.goal_set_proj and alg_switch and t < cfg.optim_steps:
-                learner.update_goal()
+                changed.append(bool(learner.update_goal()))
+            picked.append(int(traj.goal_idx))
+            p = np.full(G, np.nan)
+            p[: learner.N] = learner.p
+            ps.append(p)
+            apply(t, 1)
             selected.append(int(traj.goal_idx))
             infos.append(optim.optimize(traj, force_update=True))
             history.append(np.copy(traj.data))
@@ -609,10 +649,66 @@ def main(out_dir=OUT, script=None):
                    iterations=np.int64(len(history)))
         for k in INFO_NUMERIC + INFO_BOOL:
             rec["info_" + k] = np.array([float(i[k]) for i in infos])
-        rec.update(scene_arrays(scene, sdf, lim))
+        if edits is None and iters is None:
+            rec.update(scene_rec)
+        else:  # the edit cases share one scene file per seed (plan_edit_scene_<seed>.npz) and record the learner as well
+            del rec["collision_points"]
+            rec.update(scene=np.int64(scene_seed), edits_applied=np.int64(applied), picked_goals=np.array(picked),
+                       changed=np.array(changed), p=np.stack(ps), final_p=np.array(learner.p, np.float64),
+                       final_sum_costs=np.array(learner.sum_costs, np.float64), final_q=np.array(learner.q, np.float64),
+                       final_experts_p=np.stack(learner.experts_p), final_goal_set=np.array(traj.goal_set))
         rec.update(cfg_record())
-        np.savez_compressed(out_dir / f"plan_{name}.npz", **rec)
-        print(f"plan_{name}.npz  iterations {len(history)} terminated {terminated} goals {sorted(set(selected))} final cost {infos[-1]['cost']:.4f}")
+        if save:
+            np.savez_compressed(out_dir / f"plan_{name}.npz", **rec)
+            print(f"plan_{name}.npz  iterations {len(history)} terminated {terminated} goals {sorted(set(selected))} final cost {infos[-1]['cost']:.4f}")
+        rec["_scene"] = dict(scene_rec, collision_points=model.collision_points)
+        return rec
+
+    def run_plan_edit_cases():
+        """The planner loop under the edit scripts of tests/plan_edits.py.  A fixture is written only if (a) every edit of its
+        script was applied before the loop ended, (b) the recording differs from the unedited run by more than 1e-3 in some
+        trajectory entry and (c) the window-0 and window-1 recordings of one script differ from each other by more than 1e-3,
+        in the history or in some recorded p — so that no test can pass by ignoring an edit or by treating both windows alike."""
+        from tests import plan_edits as PE
+
+        def apart(a, b, keys):
+            worst = 0.0
+            for k in keys:
+                m = min(len(a[k]), len(b[k]))
+                x, y = np.asarray(a[k][:m], np.float64), np.asarray(b[k][:m], np.float64)
+                if x.shape != y.shape:
+                    return np.inf
+                both = np.isfinite(x) & np.isfinite(y)  # p is padded with NaN to the larger goal count
+                worst = max(worst, float(np.abs(x[both] - y[both]).max(initial=0.0)))
+            return worst
+
+        plain, scenes_done = {}, set()
+        for name, spec in PE.SCRIPTS.items():
+            over = spec.get("cfg_over", {})
+            key = (spec["seed"], spec["alg"], spec["standoff"], tuple(sorted(over.items())))
+            if key not in plain:
+                plain[key] = run_plan_case(None, spec["seed"], 8, spec["alg"], spec["standoff"], cfg_over=over, iters=PE.ITERATIONS, save=False)
+            recs = {}
+            for w in (0, 1):
+                _, script, iters = PE.case(f"{name}_w{w}")
+                recs[w] = run_plan_case(f"edit_{name}_w{w}", spec["seed"], 8, spec["alg"], spec["standoff"], cfg_over=over, edits=script, iters=iters, save=False)
+                d = apart(recs[w], plain[key], ["history"])
+                print(f"plan_edit_{name}_w{w}: iterations {int(recs[w]['iterations'])}, {int(recs[w]['edits_applied'])}/{len(script)} edits, "
+                      f"{d:.3g} from the unedited run, goals {recs[w]['selected_goals'].tolist()}")
+                assert int(recs[w]["edits_applied"]) == len(script), f"{name}_w{w}: the loop ended before the last edit"
+                assert d > 1e-3, f"{name}_w{w}: the edits do not move the plan"
+                for it, win, f in script:  # an override that equals the learner's pick overrides nothing
+                    if f.__name__ == "override_goal_k" and win == 1:
+                        assert recs[w]["selected_goals"][it] != recs[w]["picked_goals"][it], f"{name}_w{w}: override == pick at {it}"
+            d = apart(recs[0], recs[1], ["history", "p"])
+            print(f"plan_edit_{name}: windows {d:.3g} apart (history {apart(recs[0], recs[1], ['history']):.3g}, p {apart(recs[0], recs[1], ['p']):.3g})")
+            assert d > 1e-3, f"{name}: both windows give the same recording"
+            for w in (0, 1):
+                scene_rec = recs[w].pop("_scene")
+                if spec["seed"] not in scenes_done:
+                    np.savez_compressed(out_dir / f"plan_edit_scene_{spec['seed']}.npz", **scene_rec)
+                    scenes_done.add(spec["seed"])
+                np.savez_compressed(out_dir / f"plan_edit_{name}_w{w}.npz", **recs[w])
 
     if fixed:
         run_plan_case("md_switch_70", 44, 8, "MD", False)          # 70 iterations, the goal changes on the way, never terminates
@@ -620,6 +716,8 @@ def main(out_dir=OUT, script=None):
         run_plan_case("exp_standoff_41", 47, 8, "Exp", True)       # standoff tails, goal change late, terminates at iteration 41
     if fixed:
         run_plan_case("md_early_2", 43, 8, "MD", False)            # terminates after two iterations (planner.py:626)
+    if fixed:
+        run_plan_edit_cases()
 
     for alg in (("FTL", "FTC", "Exp", "MD") if fixed else ()):
         run_learner_case(alg, 31, 8, 6, False)
@@ -644,7 +742,7 @@ def main(out_dir=OUT, script=None):
         run_batch_case("arc_attached_g4_n12", 24, 4, 12, True, 0, attached=True)
     if script is not None:
         script(types.SimpleNamespace(run_cost_case=run_cost_case, run_opt_case=run_opt_case, run_batch_case=run_batch_case,
-                                     run_learner_case=run_learner_case, run_plan_case=run_plan_case, cfg=cfg, sc=sc, model=model))
+                                     run_learner_case=run_learner_case, run_plan_case=run_plan_case, run_plan_edit_cases=run_plan_edit_cases, cfg=cfg, sc=sc, model=model))
 
 
 if __name__ == "__main__":

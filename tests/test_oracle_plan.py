@@ -1,80 +1,182 @@
 """The whole planner loop — Learner.__init__'s goal pick, then per iteration Learner.update_goal + Optimizer.optimize
 (force_update) with the break on `terminate`, then the final info-only evaluation (omg/planner.py:600-653) — free-running
 from the reference's start, restated with the oracle's entry points and compared with the reference's own run
-(tests/golden/plan_*.npz, written by make_golden.py:run_plan_case)."""
+(tests/golden/plan_*.npz, written by make_golden.py:run_plan_case).  The loop keeps its inputs in small host objects and re-reads
+them in every call, so the edit scripts of tests/plan_edits.py apply to it as they do to the reference's objects
+(tests/golden/plan_edit_*.npz, make_golden.py:run_plan_edit_cases)."""
+import types
+
 import numpy as np
 import pytest
 
 from oracle import oracle as orc
 from omg_planner_amd import scenes as sc
 from tests import helpers as H
+from tests import plan_edits as PE
 
 PLAN_CASES = ["md_switch_70", "exp_standoff_41", "md_early_2"]
 
 
-def oracle_plan(fx):
-    """-> init goal, init trajectory, per-iteration (goal index, trajectory, info record), final info record or None."""
-    m, batch = H.model_from(fx), H.batch_from(fx)
-    blob, P = m.blob(), m.points_per_link
-    goals, reach, start = fx["goal_set"], fx["reach_grasps"], fx["start"]
-    standoff = bool(int(fx["cfg_use_standoff"]))
-    G, n, dt = goals.shape[0], 30, float(fx["cfg_dt"])
-    T, extra = int(fx["optim_steps"]), int(fx["extra_smooth_steps"])
-    c = 5 if standoff else 1
-    cv_goals = reach[:, -1, :] if standoff else goals
-    alg = str(fx["alg"])
+class OracleLoop:
+    """The loop's inputs as small host objects — env (objects with pose_mat / reach_grasps, target_idx, sdf_torch), traj (data,
+    start, end, goal_set, goal_idx, interpolate_waypoints), cost, cfg — that the learner and the optimiser below RE-READ on every
+    call, as the reference's classes do.  An edit script of tests/plan_edits.py therefore works on them as it does on the
+    reference's objects."""
 
-    def lparams(t):
+    def __init__(self, fx):
+        self.fx = fx
+        self.model = H.model_from(fx)
+        self.blob, self.P = self.model.blob(), self.model.points_per_link
+        self.standoff = bool(int(fx["cfg_use_standoff"]))
+        self.n, self.dt, self.alg = 30, float(fx["cfg_dt"]), str(fx["alg"])
+        self.cfg = types.SimpleNamespace(optim_steps=int(fx["optim_steps"]), extra_smooth_steps=int(fx["extra_smooth_steps"]), timesteps=self.n)
+        objs = [types.SimpleNamespace(name=str(nm), pose_mat=np.array(fx["obj_pose"][i]), attached=bool(fx["attached"][i]), reach_grasps=[])
+                for i, nm in enumerate(fx["obj_names"])]
+        self.env = types.SimpleNamespace(objects=objs, target_idx=int(fx["target_idx"]), config=self.cfg,
+                                         sdf_torch=np.array(fx["sdf"], np.float32), sdf_limits=fx["limits"])
+        objs[self.env.target_idx].reach_grasps = np.array(fx["reach_grasps"])
+        self.cost = types.SimpleNamespace(env=self.env, target_obj=objs[self.env.target_idx])
+        self.fxp = dict(fx, cfg_top_k=1000, cfg_goal_set_proj=1)
+
+    def batch(self):
+        env = self.env
+        return H.batch_from(dict(obj_names=[o.name for o in env.objects], obj_pose=np.stack([o.pose_mat for o in env.objects]),
+                                 attached=[o.attached for o in env.objects], target_idx=env.target_idx, limits=env.sdf_limits,
+                                 sdf=env.sdf_torch))
+
+    def reach(self):
+        return np.asarray(self.env.objects[self.env.target_idx].reach_grasps, np.float64)
+
+    def new_traj(self, start, goal_set):
+        n = self.n
+        traj = types.SimpleNamespace(start=np.array(start), goal_set=goal_set, goal_idx=0, end=np.array(goal_set[0]), data=None)
+        traj.interpolate_waypoints = lambda: setattr(traj, "data", sc.cubic_init(np.asarray(traj.start), np.asarray(traj.end), n))
+        traj.interpolate_waypoints()
+        return traj
+
+    def new_learner(self, traj):
+        return _Learner(self, traj)
+
+    def new_optimizer(self):
+        return _Optimizer(self)
+
+
+class _Learner:
+    def __init__(self, loop, traj):
+        """Learner.__init__ (online_learner.py:96-102): argmin of one cost vector at t = 0, re-interpolate."""
+        self.loop, self.traj, self.t = loop, traj, 0.0
+        self.N = G = len(traj.goal_set)
+        self.eta = float(np.sqrt(np.log(G + 1) / loop.cfg.optim_steps))
+        self.state = orc.learner_state_init(1, G)
+        idx = self._update(self._params(0, "FTC"), orc.learner_state_init(1, G))
+        traj.goal_idx = idx
+        traj.end = traj.goal_set[idx]
+        traj.interpolate_waypoints()
+
+    p = property(lambda self: self.state[0, self.N:2 * self.N])
+    sum_costs = property(lambda self: self.state[0, :self.N])
+    experts_p = property(lambda self: self.state[0, 2 * self.N:7 * self.N].reshape(5, self.N))
+    q = property(lambda self: self.state[0, 7 * self.N:7 * self.N + 5])
+
+    def _params(self, t, alg):
+        loop, T, n = self.loop, self.loop.cfg.optim_steps, self.loop.n
         lp = orc.LearnerParams()
-        lp.alg, lp.num_goals, lp.n_waypoints = orc.ALG[alg], G, n
+        lp.alg, lp.num_goals, lp.n_waypoints = orc.ALG[alg], self.N, n
         lp.start_idx = min(int((t / T) * n), n - 1)
-        lp.constraint_num, lp.use_standoff, lp.normalize_cost = c, int(standoff), 1
+        lp.constraint_num, lp.use_standoff, lp.normalize_cost = (5 if loop.standoff else 1), int(loop.standoff), 1
         lp.base_obstacle_weight, lp.smooth_weight = 1.0, 0.1 * 0.1  # smoothness_base_weight * dist_eps
-        lp.eta = float(np.sqrt(np.log(G + 1) / T))
+        lp.eta = self.eta
         return lp
 
-    # Learner.__init__ (online_learner.py:96-102): trajectory towards goal 0, argmin of one cost vector, re-interpolate
-    traj = sc.cubic_init(start, goals[0], n)[None]
-    lp = lparams(0)
-    lp.alg = orc.ALG["FTC"]
-    cost, _ = orc.goalset_cost(blob, P, batch, traj[:, 0], cv_goals[None], n, dt)
-    idx, end, rows, gp, _ = orc.goal_update(lp, traj, goals[None], reach[None] if standoff else None, cost, orc.learner_state_init(1, G))
-    init_idx = int(idx[0])
-    traj = sc.cubic_init(start, end[0], n)[None]
-    init_traj = traj[0].copy()
-    state = orc.learner_state_init(1, G)
-    fxp = dict(fx, cfg_top_k=1000, cfg_goal_set_proj=1)
-    steps, out, info = 0, [], None
-    for t in range(T + extra):
-        if t < T:
-            lp = lparams(t + 1)  # update_goal increments Learner.t first
-            cost, _ = orc.goalset_cost(blob, P, batch, traj[:, lp.start_idx], cv_goals[None], n - lp.start_idx, dt)
-            idx, end, rows, gp, _ = orc.goal_update(lp, traj, goals[None], reach[None] if standoff else None, cost, state)
-        steps += 1
-        prm = H.params_from(fxp, orc.ChompParams, n, P, 1, 1.0, 0.1 * 1.02 ** steps)
-        pot, pg, col = orc.fk_sdf(blob, P, batch, traj)
-        traj, _, _, info = orc.chomp_optimize(blob, prm, traj, start[None], end, rows, gp, pot, pg, col, None)
-        out.append((int(idx[0]), traj[0].copy(), info[0].copy()))
-        if info[0, H.INFO_IDX["terminate"]] > 0.5 and t > 0:
+    def _update(self, lp, state):
+        loop, traj = self.loop, self.traj
+        goals, reach = np.asarray(traj.goal_set, np.float64), loop.reach()
+        cv_goals = reach[:, -1, :] if loop.standoff else goals
+        data = np.ascontiguousarray(traj.data, np.float64)[None]
+        cost, _ = orc.goalset_cost(loop.blob, loop.P, loop.batch(), data[:, lp.start_idx], cv_goals[None], loop.n - lp.start_idx, loop.dt)
+        idx = orc.goal_update(lp, data, goals[None], reach[None] if loop.standoff else None, cost, state)[0]
+        return int(idx[0])
+
+    def update_goal(self):
+        self.t += 1  # update_goal increments Learner.t first
+        old = self.traj.goal_idx
+        self.traj.goal_idx = self._update(self._params(self.t, self.loop.alg), self.state)
+        self.traj.end = self.traj.goal_set[self.traj.goal_idx]  # a view, as in the reference (online_learner.py:246)
+        return self.traj.goal_idx != old
+
+    def reset(self, traj):
+        """online_learner.py:251-263: t, p, sum_costs start again; the experts and the mixture weights stay."""
+        self.traj, self.t, G = traj, 0.0, self.N
+        assert len(traj.goal_set) == G
+        self.state[0, :G], self.state[0, G:2 * G] = 0.0, 1.0 / G
+
+
+class _Optimizer:
+    def __init__(self, loop):
+        self.loop, self.step = loop, 0
+
+    def reset(self):
+        self.step = 0
+
+    def optimize(self, traj, do_update):
+        loop = self.loop
+        self.step += 1
+        prm = H.params_from(loop.fxp, orc.ChompParams, loop.n, loop.P, do_update, 1.0, 0.1 * 1.02 ** self.step)
+        data = np.ascontiguousarray(traj.data, np.float64)[None]
+        pot, pg, col = orc.fk_sdf(loop.blob, loop.P, loop.batch(), data)
+        gi, goals = int(traj.goal_idx), np.asarray(traj.goal_set, np.float64)
+        rows = loop.reach()[gi] if loop.standoff else goals[gi][None]  # optimizer.py:93-99
+        new, _, _, info = orc.chomp_optimize(loop.blob, prm, data, np.asarray(traj.start, np.float64)[None], np.asarray(traj.end, np.float64)[None],
+                                             rows[None], goals[gi][None], pot, pg, col, None)
+        if do_update:
+            traj.data = new[0]
+        return info[0]
+
+
+def oracle_plan(fx, script=(), iters=None):
+    """-> init goal, init trajectory, per-iteration (goal index, trajectory, info record, changed, p), final info record or None,
+    the final learner."""
+    loop = OracleLoop(fx)
+    env, cost, cfg = loop.env, loop.cost, loop.cfg
+    traj = loop.new_traj(fx["start"], np.array(fx["goal_set"]))
+    learner, optim = loop.new_learner(traj), loop.new_optimizer()
+    init_idx, init_traj = int(traj.goal_idx), traj.data.copy()
+    rng = PE.make_rng()
+
+    def apply(t, window):
+        nonlocal traj, learner, optim
+        for f in PE.due(script, t, window):
+            r = f(env, traj, learner, cost, cfg, rng)
+            if isinstance(r, PE.Replan):
+                traj, learner, optim = PE.apply_replan(r, env, cost, learner, optim, loop.new_traj, loop.new_optimizer, loop.new_learner)
+
+    T, total = cfg.optim_steps, cfg.optim_steps + cfg.extra_smooth_steps
+    out, info = [], None
+    for t in range(total if iters is None else min(iters, total)):
+        apply(t, 0)
+        changed = learner.update_goal() if t < T else None
+        p = learner.p.copy()
+        apply(t, 1)
+        idx = int(traj.goal_idx)
+        info = optim.optimize(traj, 1)
+        out.append((idx, traj.data.copy(), info.copy(), changed, p))
+        if info[H.INFO_IDX["terminate"]] > 0.5 and t > 0:
             break
     final = None
-    if not info[0, H.INFO_IDX["terminate"]] > 0.5:
-        steps += 1
-        prm = H.params_from(fxp, orc.ChompParams, n, P, 0, 1.0, 0.1 * 1.02 ** steps)
-        pot, pg, col = orc.fk_sdf(blob, P, batch, traj)
-        _, _, _, final = orc.chomp_optimize(blob, prm, traj.copy(), start[None], end, rows, gp, pot, pg, col, None)
-    return init_idx, init_traj, out, final
+    if not info[H.INFO_IDX["terminate"]] > 0.5:
+        final = optim.optimize(traj, 0)[None]
+    return init_idx, init_traj, out, final, learner
 
 
 @pytest.mark.parametrize("case", PLAN_CASES)
 def test_oracle_plan_matches_reference_planner_loop(case):
     fx = H.load(f"plan_{case}.npz")
-    init_idx, init_traj, out, final = oracle_plan(fx)
+    init_idx, init_traj, out, final, _ = oracle_plan(fx)
     assert init_idx == int(fx["init_goal_idx"])
     np.testing.assert_allclose(init_traj, fx["init_traj"], rtol=0, atol=1e-12)
     assert len(out) == int(fx["iterations"])
     assert [o[0] for o in out] == fx["selected_goals"].tolist()
-    for t, (_, traj, info) in enumerate(out):
+    for t, (_, traj, info, _, _) in enumerate(out):
         # free-running over up to 70 iterations: 1e-6 (the task's bar is 1e-4)
         np.testing.assert_allclose(traj, fx["history"][t], rtol=0, atol=1e-6, err_msg=f"iteration {t}")
         np.testing.assert_allclose(info[H.INFO_IDX["cost"]], fx["info_cost"][t], rtol=1e-5, err_msg=f"iteration {t}")
@@ -84,3 +186,31 @@ def test_oracle_plan_matches_reference_planner_loop(case):
     if final is not None:
         np.testing.assert_allclose(final[0, H.INFO_IDX["cost"]], fx["info_cost"][-1], rtol=1e-5)
         np.testing.assert_allclose(final[0, H.INFO_IDX["smooth"]], fx["info_smooth"][-1], rtol=1e-6)
+
+
+@pytest.mark.parametrize("case", PE.CASES)
+def test_oracle_plan_follows_host_edits_like_the_reference(case):
+    """The same loop under the edit scripts of tests/plan_edits.py (goal arrays permuted in place and replaced, trajectory and
+    start edited, goal overridden, object moved, volume raised, re-plan with new and with reset objects; each before
+    update_goal() and between update_goal() and optimize()) against the reference's own classes under the same scripts
+    (tests/golden/plan_edit_*.npz).  This pins the oracle where the GPU tests of the drop-in classes lean on the recordings."""
+    fx = PE.load(case)
+    _, script, iters = PE.case(case)
+    init_idx, init_traj, out, final, learner = oracle_plan(fx, script, iters)
+    assert init_idx == int(fx["init_goal_idx"])
+    np.testing.assert_allclose(init_traj, fx["init_traj"], rtol=0, atol=1e-12)
+    assert len(out) == int(fx["iterations"])
+    assert [o[0] for o in out] == fx["selected_goals"].tolist()
+    assert [bool(o[3]) for o in out if o[3] is not None] == fx["changed"].astype(bool).tolist()
+    for t, (_, traj, info, _, p) in enumerate(out):
+        np.testing.assert_allclose(traj, fx["history"][t], rtol=0, atol=1e-6, err_msg=f"iteration {t}")
+        np.testing.assert_allclose(info[H.INFO_IDX["cost"]], fx["info_cost"][t], rtol=1e-5, err_msg=f"iteration {t}")
+        np.testing.assert_allclose(p, fx["p"][t][: len(p)], rtol=1e-4, atol=1e-6, err_msg=f"p, iteration {t}")
+        assert np.isnan(fx["p"][t][len(p):]).all()
+    assert (final is None) == bool(int(fx["terminated"]))
+    if final is not None:
+        np.testing.assert_allclose(final[0, H.INFO_IDX["cost"]], fx["info_cost"][-1], rtol=1e-5)
+    np.testing.assert_allclose(learner.p, fx["final_p"], rtol=1e-4, atol=1e-6)
+    np.testing.assert_allclose(learner.sum_costs, fx["final_sum_costs"], rtol=2e-5)
+    np.testing.assert_allclose(learner.experts_p, fx["final_experts_p"], rtol=1e-4, atol=1e-6)
+    np.testing.assert_allclose(learner.q, fx["final_q"], rtol=1e-4, atol=1e-7)
