@@ -855,6 +855,55 @@ int omgx_pixel_gather(const omgx_instance* instances, int32_t num_instances, con
                       double* points, int64_t cap, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * (15) omgx_register_clouds: refine the poses of known objects against observed clouds
+ * The reference takes object poses from an outside estimator (real_world/trial.py) or from the scene file.  Here every known
+ * object has a signed distance volume in the pool, and a cloud that belongs to it (omgx_pixel_gather's points of its instance)
+ * fixes its pose: the pose at which the volume is zero on the points.  M instances (object, start pose, range of points) are
+ * refined in ONE launch, one workgroup of OMGX_REGISTER_THREADS threads per instance, the whole Levenberg-Marquardt iteration
+ * inside it.  omg-planner_amd/registration.py (register_clouds) is the specification; all arithmetic is float64 without
+ * contraction, the sums have a fixed shape, the loop uses + - * / only, and poses and stats have the specification's bits.
+ * New entry point only: omgx_abi_version() stays 14.
+ *
+ * objects: only lo, dim, inv_delta and grid_offset are read (pose_inv is float32 and ignored).  poses0 [M][12]: rows 0..2 of
+ * world_from_obj = [R t], row-major.  points [num_points][3] in the world frame.  ranges [M][2] = (begin, end) rows of points;
+ * ranges may be empty, overlap or be equal (one cloud from several starts).  Instance m uses begin, begin + stride, ... < end.
+ * One pass at (R, t), per used point p: q = R^T (p - t); u_a = (q_a - (double)lo_a) * inv_delta - 0.5; inside iff every
+ *   u_a >= 0 and u_a < dim_a - 1 (in double: NaN, inf and 1e300 are outside); v = the trilinear value of the eight corners,
+ *   g = the gradient of that interpolant times inv_delta (registration.value_gradient has the order of operations); inlier iff
+ *   inside and |v| <= trunc.  An inlier adds v*v to cost, 1 to count, j j^T to H (upper triangle, 21 numbers) and j v to b with
+ *   j = -(g, q x g); every other point adds trunc*trunc to cost.  Lane l adds its points l, l + 256, ... in order from +0.0;
+ *   inside each wave x[l] += x[l + s] for s = 32 ... 1; the total is ((w0 + w1) + w2) + w3.
+ * Iteration: pass 0 at poses0, lam = lambda0; then trials: A = H + lam*diag(H) + floor*I, A xi = -b by LDL^T without pivoting
+ *   (a pivot not > 0 or not finite rejects the trial), t' = t + R xi_v, R' = R C(xi_w / 2) with the Cayley map C, one pass at
+ *   the trial; cost' < cost accepts it and lam = max(lam / 8, lam_min), otherwise lam = min(8 lam, lam_max).  It stops after
+ *   max_passes trials, with fewer than six inliers, after an accepted step with max|xi| < step_tol, or with lam at lam_max.
+ *   floor = 1e-9, lam_min = 2^-20, lam_max = 2^20 (registration.FLOOR, LAMBDA_MIN, LAMBDA_MAX).
+ * poses_out [M][12]; stats_out [M][OMGX_REGISTER_STATS] double: cost at poses0, final cost, inliers at poses0, final inliers,
+ *   accepted trials, trials run, final lam, status (the OMGX_REGISTER_* bits).  With max_passes == 0 or fewer than six inliers
+ *   poses_out has the bits of poses0.  No atomics, no communication between workgroups.
+ * `objects`, `obj_index`, `ranges` are on the device, h_objects, h_obj_index, h_ranges the same on the host; ALL checks are made
+ * on the host copies before any HIP call.  OMGX_ERR_INVALID: a null pointer (everything per instance may be NULL with
+ * num_instances == 0, points with num_points == 0), a negative size, stride < 1, max_passes outside
+ * [0, OMGX_REGISTER_MAX_PASSES], trunc or lambda0 not finite or not > 0, an object index outside
+ * [0, num_objects), a range outside [0, num_points] or with end < begin, a referenced record with a dim below 2 or whose grid
+ * leaves [0, pool_elems).  num_instances == 0 returns OMGX_OK and launches nothing.
+ * ------------------------------------------------------------------------------------------- */
+#define OMGX_REGISTER_THREADS 256
+#define OMGX_REGISTER_MAX_PASSES 64
+#define OMGX_REGISTER_STATS 8
+#define OMGX_REGISTER_FEW_INLIERS 1
+#define OMGX_REGISTER_SINGULAR 2
+#define OMGX_REGISTER_LAMBDA_AT_MAX 4
+#define OMGX_REGISTER_CONVERGED 8
+int omgx_register_clouds(const omgx_object* objects, const omgx_object* h_objects, int32_t num_objects,
+                         const float* pool, int64_t pool_elems,
+                         const int32_t* obj_index, const int32_t* h_obj_index,
+                         const double* poses0, const double* points, int64_t num_points,
+                         const int32_t* ranges, const int32_t* h_ranges, int32_t num_instances,
+                         int32_t stride, double trunc, double lambda0, double step_tol, int32_t max_passes,
+                         double* poses_out, double* stats_out, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Diagnostics
  * ------------------------------------------------------------------------------------------- */
 const char* omgx_last_error(void); /* thread-local text of the last OMGX_ERR_LAUNCH               */

@@ -348,6 +348,31 @@ class DeviceScenes:
         off = idx * self.host_objects.dtype.itemsize
         self.objects[off: off + 48].copy_(inv.reshape(-1).view(torch.uint8))
 
+    def set_object_poses(self, indices, poses) -> None:
+        """Move several objects at once: indices [n,2] (scene, obj) pairs, no pair twice; poses [n,4,4] (object -> world; numpy, or
+        a tensor, which is brought to the host first).  The batched form of set_object_pose: the same float32 rows
+        (scenes.se3_inverse of every pose), ONE upload and ONE scatter into the record buffer on the device, one update of the
+        host mirror; record bytes and mirror end up as after set_object_pose(scene, obj, pose) with every pose given as a numpy
+        array.  (set_object_pose inverts a TENSOR pose on the device with torch, whose rounding of R^T t is its own; here a
+        tensor takes the numpy path, so the equality is with set_object_pose's numpy path whatever the input type.)"""
+        from . import scenes as _sc
+        pairs = np.asarray(indices, np.int64).reshape(-1, 2)
+        if isinstance(poses, torch.Tensor):
+            poses = poses.detach().cpu().numpy()
+        poses = np.asarray(poses, np.float64).reshape(-1, 4, 4)
+        if len(poses) != len(pairs):
+            raise ValueError(f"{len(pairs)} pairs but {len(poses)} poses")
+        idx = np.array([self._index(int(s), int(o)) for s, o in pairs], np.int64)
+        if len(np.unique(idx)) != len(idx):
+            raise ValueError("a (scene, obj) pair is named twice")
+        if not len(idx):
+            return
+        inv = np.stack([_sc.se3_inverse(P)[:3, :4] for P in poses]).reshape(-1, 12).astype(np.float32)
+        self.host_objects["pose_inv"][idx] = inv
+        rows = self.objects.view(-1, self.host_objects.dtype.itemsize)
+        d_inv = torch.from_numpy(inv.view(np.uint8).reshape(-1, 48)).to(self.device, non_blocking=True)
+        rows[:, :48].index_copy_(0, torch.from_numpy(idx).to(self.device, non_blocking=True), d_inv)
+
     def grid_slot(self, scene: int, obj: int, shape) -> torch.Tensor:
         """A float32 [X,Y,Z] view into the pool where the object's NEXT volume can be written in place (e.g. by
         point_cloud_sdf(out=...)): the object's own slot if the shape fits and no other object shares it, else a slot nobody
@@ -1381,3 +1406,60 @@ def pixel_clouds(batch: CameraBatch, t: torch.Tensor, inst: torch.Tensor, cls: i
         check(l.omgx_pixel_gather(*batch._records(host=False), H, W, _ptr(t), _ptr(inst), cls, _ptr(ws), _ptr(points), int(points.shape[0]),
                                   _stream()), "omgx_pixel_gather")
     return points, h_begin
+
+
+def register_clouds(scenes: DeviceScenes, pairs, poses0, points: torch.Tensor, ranges, stride: int = 1, trunc: float = 0.03,
+                    lambda0: float = 2.0 ** -10, step_tol: float = 1e-6, max_passes: int = 30, out=None):
+    """Refine the poses of M (scene, obj) instances against their clouds in ONE launch (omgx_register_clouds;
+    registration.register_clouds is the specification: the same float64 bit for bit) -> (poses [M,12], stats [M,8]) float64 on
+    the device.  pairs [M,2] (scene, obj) and ranges [M,2] (begin, end) rows of `points`: host integers; poses0 [M,12]: rows 0..2
+    of world_from_obj, a float64 device tensor (or a host array, uploaded); points [N,3]: a contiguous float64 device tensor
+    (pixel_clouds' points).  Ranges may be empty, overlap or be equal.  out: None or (poses, stats) written IN PLACE."""
+    from . import registration as _reg
+    dev = scenes.device
+    # what does not depend on where a tensor lies comes first: the scalars, the index lists, the shapes, the ranges
+    if int(stride) < 1 or not 0 <= int(max_passes) <= _reg.MAX_PASSES:
+        raise _lib.OmgHipError(f"stride must be >= 1 and max_passes in [0, {_reg.MAX_PASSES}], got {stride} and {max_passes}")
+    if not (np.isfinite(float(trunc)) and float(trunc) > 0 and np.isfinite(float(lambda0)) and float(lambda0) > 0):
+        raise _lib.OmgHipError("trunc and lambda0 must be finite and positive")
+    pairs = np.asarray(pairs, np.int64).reshape(-1, 2)
+    M = len(pairs)
+    h_index = np.ascontiguousarray([scenes._index(int(s), int(o)) for s, o in pairs], np.int32).reshape(M)
+    h_ranges = np.asarray(ranges, np.int64).reshape(-1, 2)
+    if len(h_ranges) != M:
+        raise _lib.OmgHipError(f"ranges must be [{M},2], got {h_ranges.shape}")
+    if not isinstance(points, torch.Tensor) or points.dim() != 2 or points.shape[1] != 3:
+        raise _lib.OmgHipError(f"points must be a tensor [N,3], got {tuple(getattr(points, 'shape', ()))}")
+    N = int(points.shape[0])
+    if M and ((h_ranges < 0).any() or (h_ranges > N).any() or (h_ranges[:, 1] < h_ranges[:, 0]).any()):
+        raise _lib.OmgHipError(f"a range is outside [0, {N}] or ends before it begins")
+    h_ranges = np.ascontiguousarray(h_ranges, np.int32)  # (inside [0, N], and N fits the int32 rows of pixel_clouds)
+    if N > 0x7fffffff:
+        raise _lib.OmgHipError(f"points has {N} rows: ranges are int32")
+    if not isinstance(poses0, torch.Tensor):
+        h_poses0 = np.ascontiguousarray(poses0, np.float64)
+        if h_poses0.shape != (M, 12):
+            raise _lib.OmgHipError(f"poses0 must be [{M},12], got {h_poses0.shape}")
+        poses0 = torch.from_numpy(h_poses0).to(dev)
+    if tuple(poses0.shape) != (M, 12):
+        raise _lib.OmgHipError(f"poses0 must be [{M},12], got {tuple(poses0.shape)}")
+    _need(points, torch.float64, "points")
+    _need(poses0, torch.float64, "poses0")
+    if points.device != dev or poses0.device != dev:
+        raise _lib.OmgHipError(f"points and poses0 must be on {dev}, got {points.device} and {poses0.device}")
+    if out is None:
+        out = (torch.empty((M, 12), dtype=torch.float64, device=dev), torch.empty((M, _reg.STATS), dtype=torch.float64, device=dev))
+    poses, stats = out
+    for t, name, cols in ((poses, "out[0]", 12), (stats, "out[1]", _reg.STATS)):
+        _need(t, torch.float64, name)
+        if t.device != dev or tuple(t.shape) != (M, cols):
+            raise _lib.OmgHipError(f"{name} must be [{M},{cols}] on {dev}, got {tuple(t.shape)} on {t.device}")
+    vp = C.c_void_p
+    with torch.cuda.device(dev):
+        d_index, d_ranges = torch.from_numpy(h_index).to(dev), torch.from_numpy(h_ranges).to(dev)
+        check(_lib.lib().omgx_register_clouds(_ptr(scenes.objects), vp(scenes.host_objects.ctypes.data), len(scenes.host_objects), _ptr(scenes.pool),
+                                              int(scenes.pool.numel()), _ptr(d_index), vp(h_index.ctypes.data if M else None), _ptr(poses0),
+                                              _ptr(points) if N else None, N, _ptr(d_ranges), vp(h_ranges.ctypes.data if M else None), M,
+                                              int(stride), float(trunc), float(lambda0), float(step_tol), int(max_passes), _ptr(poses), _ptr(stats),
+                                              _stream()), "omgx_register_clouds")
+    return poses, stats
