@@ -204,9 +204,8 @@ struct ChunkArgs {
     // scene (2 links x all waypoints each), a scene's workgroups on one XCD.  Latency mode (a few scenes): a goal's tiles dealt over
     // NP workgroups (chunk = goal * NP + part; NCH = NG * NP chunks per scene), layer_lg x layer_nb layer workgroups per scene
     // (10 / layer_lg links x layer_cb waypoints), workgroups in plain order over all XCDs (spread).
-    int NG, NP;
-    int range_h;  // k_goalset_range: a goal's window cut into two RANGES of waypoints — part 0 the first range_h, part 1 the rest (omg_goalset_queue.h: RANGE)
-    int layer_parts, layer_lg, layer_nb, layer_cb, spread;
+    int NG, NP, spread;  // (spread: read by the launcher only — the kernels have it as LAT)
+    int layer_parts, layer_lg, layer_nb, layer_cb;
     double* wp_pose_out;       // [S][wp_n][10][12] or null: the layer workgroups of link group 0 leave the waypoints' poses here
     uint32_t* work;
     // kinematics pre-pass (k_goalset_kin -> k_goalset_queue<..., PRE>; omg_goalset_kin.h): the goals' link poses
@@ -821,21 +820,6 @@ extern "C" int64_t omgx_goalset_workspace_bytes(int32_t num_scenes, int32_t num_
 #ifndef GS_LAYER_FOLLOW_MIN
 #define GS_LAYER_FOLLOW_MIN 16  // waypoints per trajectory-layer piece at least, when the pieces follow the goal window (launch_goalset)
 #endif
-#ifndef GS_RANGE_MIN_WINDOW
-#define GS_RANGE_MIN_WINDOW (1 << 20)  // windows beyond this many configurations: two parts of a goal are waypoint ranges — never, by default (launch_goalset)
-#endif
-static int g_range_min = -1;  // -1: not read yet (OMGX_GS_RANGE_MIN, omgx_debug_set_range)
-// test / experiment hook (tests/test_gpu_parts.py, tools/experiments/ab_range.sh; not part of the ABI); negative: the built-in rule
-extern "C" void omgx_debug_set_range(int min_window) { g_range_min = min_window >= 0 ? min_window : GS_RANGE_MIN_WINDOW; }
-#ifndef GS_WIDE8_MAX_ITEMS
-#define GS_WIDE8_MAX_ITEMS 0    // (set by measurement: DESIGN.md section 4.5)
-#endif
-#ifndef GS_WIDE6_MAX_ITEMS
-#define GS_WIDE6_MAX_ITEMS 0
-#endif
-#ifndef GS_WIDE6_LONG_MAX_ITEMS
-#define GS_WIDE6_LONG_MAX_ITEMS 0  // windows beyond 32 waypoints
-#endif
 // How a k_goalset_queue launch is cut into workgroups (ChunkArgs: NP, layer_*, spread).  The default is the batch layout.
 struct GsTiling {
     int goal_parts = 1;  // workgroups per goal (1, 2, 4 or 8) at most: omgx_goalset_parts picks the count for a window
@@ -855,53 +839,26 @@ static inline int gs_parts(int n_remaining, int max_parts) {
     return np;
 }
 
-// Waves per goal workgroup of a batch launch with `items` whole goals and a window of n_remaining configurations: GQ_WAVES, or 6 / 8 for the
-// WIDE instantiations (three / two workgroups per CU).  EXPERIMENT knobs (read once): OMGX_GS_WIDE=0 never wide; OMGX_GS_WIDE8_MAX /
-// OMGX_GS_WIDE6_MAX = the largest launch (goal workgroups) that runs on eight / six waves.
-static int g_wide_on = -1;  // -1: not read yet
-static int64_t g_wide_max8 = GS_WIDE8_MAX_ITEMS, g_wide_max6 = GS_WIDE6_MAX_ITEMS, g_wide_long6 = GS_WIDE6_LONG_MAX_ITEMS;
-// Waves per goal workgroup of a batch launch of `items` whole goals with a window of n_remaining configurations (PS / MR / P: the launch's
-// LDS layout).  The rule (round 6, measured: DESIGN.md section 4.5):
-//   * a window whose four-wave layout needs more than 53 248 B of LDS — plans of 57 .. 64 waypoints (15-16 points per link; the launch's poses are the trajectory layer's: all n) — admits TWO workgroups per CU whatever their
-//     waves: eight waves each (16 per CU instead of 8; 50 / 100 scenes x 64 goals x 64 waypoints: 0.287 -> 0.240 / 0.500 -> 0.399 ms per step);
-//   * everything else on four: up to 56 waypoints the wide workgroups cost a workgroup per CU (stamps: 2.0 six-wave workgroups resident per CU
-//     against 2.85 four-wave ones at 50 waypoints: 52 / 56 waypoints +6 .. +10 %), and at 30 waypoints they pay only in launches of a few hundred goals
-//     under a layout rule of their own (2 - 8 scenes x 64 goals -4 .. -5 %, 13 x 128 +13 %): thresholds 0, kept as EXPERIMENT knobs —
-//     OMGX_GS_WIDE=0 never wide; OMGX_GS_WIDE8_MAX / OMGX_GS_WIDE6_MAX / OMGX_GS_WIDE6_LONG_MAX = the largest launch (goal workgroups) on
-//     eight / six waves (windows up to 32 waypoints) / six waves (longer windows), read once; omgx_debug_set_wide.
-static inline int gs_wide_waves(int64_t items, int n_remaining, int PS, int MR, int P) {
-    if (g_wide_on < 0) {
-        const char* e = getenv("OMGX_GS_WIDE");
-        const char* e8 = getenv("OMGX_GS_WIDE8_MAX");
-        const char* e6 = getenv("OMGX_GS_WIDE6_MAX");
-        const char* el = getenv("OMGX_GS_WIDE6_LONG_MAX");
-        if (el) g_wide_long6 = (int64_t)atoll(el);
-        if (e8) g_wide_max8 = (int64_t)atoll(e8);
-        if (e6) g_wide_max6 = (int64_t)atoll(e6);
-        g_wide_on = e ? (atoi(e) != 0) : 1;
-    }
-    if (!g_wide_on || GQ_WAVES != 4) return GQ_WAVES;
-    if (GqLayout(PS, MR, P, 4, false, GQ_WAVES).total > 53248 && GqLayout(PS, MR, P, 4, false, 8).total <= 64 * 1024) return 8;
-    if (n_remaining > 32) {  // (EXPERIMENT: OMGX_GS_WIDE_LONG_W = 6 | 8 waves for the long windows the knob admits)
-        static const int lw = [] { const char* e = getenv("OMGX_GS_WIDE_LONG_W"); return (e && atoi(e) == 8) ? 8 : 6; }();
-        return items <= g_wide_long6 ? lw : GQ_WAVES;
-    }
-    if (items <= g_wide_max8) return 8;
-    if (items <= g_wide_max6) return 6;
-    return GQ_WAVES;
+// Test / experiment hook (tests/test_gpu_round6.py; not part of the ABI): 0 = the rule below, 4 = never wide, 8 = eight waves wherever wide
+// workgroups are admissible (batch layout, whole goals, own kinematics, a layout that fits 64 KB) and the rule elsewhere.
+static std::atomic<int> g_force_goal_waves{0};
+extern "C" void omgx_debug_force_goal_waves(int waves) { g_force_goal_waves.store(waves == 4 || waves == 8 ? waves : 0, std::memory_order_relaxed); }
+// Waves per goal workgroup of a batch launch of whole goals (PS / MR / P: the launch's LDS layout).  The rule (round 6, measured: DESIGN.md
+// section 4.5):
+//   * a window whose four-wave layout needs more than 53 248 B of LDS — plans of 57 .. 64 waypoints (15-16 points per link; the launch's
+//     poses are the trajectory layer's: all n) — admits TWO workgroups per CU whatever their waves: eight waves each (16 per CU instead of
+//     8; 50 / 100 scenes x 64 goals x 64 waypoints: 0.287 -> 0.240 / 0.500 -> 0.399 ms per step);
+//   * everything else on four: up to 56 waypoints wide workgroups cost a workgroup per CU (52 / 56 waypoints +6 .. +10 %), and at 30
+//     waypoints they pay only in launches of a few hundred goals (2 - 8 scenes x 64 goals -4 .. -5 %, 13 x 128 +13 %).
+static inline int gs_wide_waves(int PS, int MR, int P) {
+    const int force = g_force_goal_waves.load(std::memory_order_relaxed);
+    if (force == 4 || GQ_WAVES != 4 || GqLayout(PS, MR, P, 4, false, 8).total > 64 * 1024) return GQ_WAVES;
+    return (force == 8 || GqLayout(PS, MR, P, 4, false, GQ_WAVES).total > 53248) ? 8 : GQ_WAVES;
 }
-// which instantiation the calling thread's process launched last (test hook: the rules above are the library's business, a test can still hold
-// them): waves per goal workgroup | 0x100 waypoint ranges | 0x200 split goals | 0x400 latency mode | 0x800 behind the kinematics pre-pass
-static int g_last_goalset_variant = 0;
+// which instantiation the calling thread launched last (test hook: the rules above are the library's business, a test can still hold
+// them): waves per goal workgroup | 0x200 split goals | 0x400 latency mode | 0x800 behind the kinematics pre-pass
+static thread_local int g_last_goalset_variant = 0;
 extern "C" int omgx_debug_last_goalset_variant(void) { return g_last_goalset_variant; }
-// test / experiment hook (tests/test_gpu_round6.py, tools/experiments/ab_wide.py; not part of the ABI): the rule's two thresholds; negative = keep
-extern "C" void omgx_debug_set_wide(int on, long long max8, long long max6, long long long6) {
-    (void)gs_wide_waves(0, 1, 2, 1, 1);  // the environment first, so that it does not overwrite what is set here
-    g_wide_on = on != 0;
-    if (max8 >= 0) g_wide_max8 = max8; else if (max8 < -1) g_wide_max8 = GS_WIDE8_MAX_ITEMS;  // (-1: keep, below: the built-in rule)
-    if (max6 >= 0) g_wide_max6 = max6; else if (max6 < -1) g_wide_max6 = GS_WIDE6_MAX_ITEMS;
-    if (long6 >= 0) g_wide_long6 = long6; else if (long6 < -1) g_wide_long6 = GS_WIDE6_LONG_MAX_ITEMS;
-}
 
 // One goal-set launch: bracketed by the timing events when this launch is recorded (timing_events), plain otherwise.
 template <class K>
@@ -923,37 +880,24 @@ static int launch_goalset(ChunkArgs& ca, int timing_kind, hipStream_t st, const 
     if (ca.spread && (ca.schedule || ca.work)) return OMGX_ERR_UNSUPPORTED;  // a dispatch schedule belongs to the batch layout: a scene per XCD
     ca.wp_pose_out = layer ? tl.wp_pose_out : nullptr;
     ca.layer_lg = tl.layer_lg;
-    // RANGES (round 6; omg_goalset_queue.h: RANGE, k_goalset_range): two parts of a LONG window are waypoint ranges, not dealt tiles — each
-    // holds only its own configurations' poses (50 waypoints: 29 KB of LDS instead of 50, five workgroups per CU instead of three) and
-    // no kinematics run twice.  The second range — the goal's end, where the objects are — is the shorter one and a multiple of four
-    // waypoints (its blocks then hold four rows each).  The trajectory layer's pieces are cut in two as well, or their poses would
-    // set the launch's LDS.  MEASURED AND LEFT OFF (DESIGN_HISTORY.md appendix A, round 6): a part pays a workgroup's whole latency L0 for half a
-    // goal's work — 100 x 64 x 50 waypoints 0.306 against 0.317 ms per step with whole goals, config 5's shape 0.185 against 0.164 with
-    // dealt tiles (the goal's end is the heavy range).  OMGX_GS_RANGE_MIN=<n> / omgx_debug_set_range(n): ranges for windows beyond n.
-    if (g_range_min < 0) { const char* e = getenv("OMGX_GS_RANGE_MIN"); g_range_min = e ? atoi(e) : GS_RANGE_MIN_WINDOW; }
-    const bool range = split && ca.NP == 2 && ca.CH > g_range_min && tl.kin_ws == nullptr && ca.traj_start != nullptr;
-    ca.range_h = range ? ca.CH - 4 * (ca.CH / 8) : 0;
     int layer_cb_req = tl.layer_cb;
-    if (range && layer && layer_cb_req == 0) layer_cb_req = (ca.wp_n + 1) / 2;
     {   // The trajectory layer's pieces cut to the goal WINDOW's size (round 6): a piece holds the poses of all its waypoints, so five pieces of
         // all n waypoints set the launch's LDS by the plan's LENGTH — in a 50-waypoint plan every goal-set launch asked for 47-50 KB, three
         // workgroups per CU, however short its window had become.  Cut to max(window + 1, 16) waypoints the launch's LDS follows the window and
         // the later launches hold four or five: plan of 100 x 64 x 50 waypoints 14.35 -> 12.64 ms, config 5's shape 10.91 -> 10.23, 50 x 64 x 64
-        // 12.18 -> 11.02, 100 x 64 x 41 11.58 -> 11.18 (tools/experiments/ab_layer_follow.sh).  Any split of the layer gives the same bits.
-        // Plans up to 32 waypoints hold five workgroups per CU anyway.  OMGX_GS_LAYER_FOLLOW=0 (experiments): the five whole pieces.
-        static const int follow = [] { const char* e = getenv("OMGX_GS_LAYER_FOLLOW"); return e ? atoi(e) : GS_LAYER_FOLLOW_MIN; }();
-        if (follow > 0 && layer && layer_cb_req == 0 && !ca.spread && ca.NG > 0 && !range && ca.wp_n > 32) {
-            const int want = ca.CH + 1 > follow ? ca.CH + 1 : follow;
+        // 12.18 -> 11.02, 100 x 64 x 41 11.58 -> 11.18.  Any split of the layer gives the same bits.
+        // Plans up to 32 waypoints hold five workgroups per CU anyway.
+        if (layer && layer_cb_req == 0 && !ca.spread && ca.NG > 0 && ca.wp_n > 32) {
+            const int want = ca.CH + 1 > GS_LAYER_FOLLOW_MIN ? ca.CH + 1 : GS_LAYER_FOLLOW_MIN;
             if (want < ca.wp_n) layer_cb_req = want;
         }
         // SMALL launches (up to 1 024 goal workgroups: everything is resident at once and the launch lasts as long as its longest workgroup —
         // late in a plan that is a layer piece of 2 links x all waypoints, 26 us, beside goals of 13): ten link groups x blocks of max(window
         // + 1, 16) waypoints.  Plan of 13 x 128 4.53 -> 4.18 ms, 16 x 64 4.25 -> 4.04, 25 x 64 4.65 -> 4.19, 8 x 64 4.06 -> 3.62; the pinned step of
-        // 16 x 64 0.0698 -> 0.0679, 13 x 128 unchanged (tools/experiments/ab_layer_small.sh).  OMGX_GS_LAYER_SMALL=0 (experiments): five whole pieces.
-        static const int small = [] { const char* e = getenv("OMGX_GS_LAYER_SMALL"); return e ? atoi(e) : GS_LAYER_FOLLOW_MIN; }();
-        if (small > 0 && layer && layer_cb_req == 0 && !ca.spread && ca.NG > 0 && !range && tl.layer_lg == 5 && (int64_t)ca.S * ca.NCH <= 1024) {
+        // 16 x 64 0.0698 -> 0.0679, 13 x 128 unchanged.
+        if (layer && layer_cb_req == 0 && !ca.spread && ca.NG > 0 && tl.layer_lg == 5 && (int64_t)ca.S * ca.NCH <= 1024) {
             ca.layer_lg = 10;
-            const int want = ca.CH + 1 > small ? ca.CH + 1 : small;
+            const int want = ca.CH + 1 > GS_LAYER_FOLLOW_MIN ? ca.CH + 1 : GS_LAYER_FOLLOW_MIN;
             if (want < ca.wp_n) layer_cb_req = want;
         }
     }
@@ -961,7 +905,6 @@ static int launch_goalset(ChunkArgs& ca, int timing_kind, hipStream_t st, const 
     ca.layer_nb = layer ? (ca.wp_n + ca.layer_cb - 1) / ca.layer_cb : 1;
     ca.layer_parts = ca.layer_lg * ca.layer_nb;
     ca.PS = ca.CH + 1; ca.MR = ca.CH; ca.LPW = 10;
-    if (range) { ca.PS = ca.range_h + 1; ca.MR = ca.range_h; }  // (range_h >= CH - range_h)
     if (layer) { if (ca.layer_cb > ca.PS) ca.PS = ca.layer_cb; if (ca.layer_cb > ca.MR) ca.MR = ca.layer_cb; }
     const int64_t per_scene = (int64_t)ca.NCH + (layer ? ca.layer_parts : 0);
     const int64_t grid = ca.spread ? (int64_t)ca.S * per_scene
@@ -970,9 +913,9 @@ static int launch_goalset(ChunkArgs& ca, int timing_kind, hipStream_t st, const 
     if (grid > 0x7fffffff) return OMGX_ERR_UNSUPPORTED;
     if (grid == 0) return OMGX_OK;
     const bool pre = tl.kin_ws != nullptr && ca.NG > 0 && ca.traj_start != nullptr;
-    // WIDE workgroups (round 6; omg_goalset_queue.h, template parameter W): a launch of few enough goal workgroups to be resident all at
-    // once lasts as long as its heaviest goal — more waves draw that goal's tiles.  Whole goals with their own kinematics only.
-    const int wide = (!ca.spread && !split && !pre && ca.NG > 0) ? gs_wide_waves((int64_t)ca.S * ca.NG, ca.CH, ca.PS, ca.MR, ca.P) : GQ_WAVES;
+    // WIDE workgroups (round 6; omg_goalset_queue.h, template parameter W): more waves draw a goal's tiles.  Whole goals with their own
+    // kinematics only.
+    const int wide = (!ca.spread && !split && !pre && ca.NG > 0) ? gs_wide_waves(ca.PS, ca.MR, ca.P) : GQ_WAVES;
     ca.tbl_n = gq_choose_tbl_n(ca.PS, ca.MR, ca.P, ca.spread, wide);
     const size_t lds = (size_t)GqLayout(ca.PS, ca.MR, ca.P, ca.tbl_n, ca.spread, wide).total;
     if (lds > 64 * 1024) {
@@ -1001,17 +944,15 @@ static int launch_goalset(ChunkArgs& ca, int timing_kind, hipStream_t st, const 
 #ifdef OMGX_GS_CLOCK  // measurement build only (tools/gs_phase_clock.py): fewer workgroups per CU by asking for more LDS than the layout needs
     if (const char* e = getenv("OMGX_GS_LDS_MIN")) { const uint32_t v = (uint32_t)atoi(e); if (v > l32 && v <= 64 * 1024) l32 = v; }
 #endif
-    // k_goalset_queue<2, STAMP, LAT, SPLIT, PRE, W> and k_goalset_range<2, STAMP>
+    // k_goalset_queue<2, STAMP, LAT, SPLIT, PRE, W>
     const auto go = [&](auto* kernel, int block) { gs_launch(kernel, g, (unsigned)block, l32, st, ev0, ev1, ca); };
-    if (range) { if (ca.work) go(k_goalset_range<2, true>, GQ_NT); else go(k_goalset_range<2, false>, GQ_NT); }
-    else if (wide == 6) { if (ca.work) go(k_goalset_queue<2, true, false, false, false, 6>, 64 * 6); else go(k_goalset_queue<2, false, false, false, false, 6>, 64 * 6); }
-    else if (wide == 8) { if (ca.work) go(k_goalset_queue<2, true, false, false, false, 8>, 64 * 8); else go(k_goalset_queue<2, false, false, false, false, 8>, 64 * 8); }
+    if (wide == 8) { if (ca.work) go(k_goalset_queue<2, true, false, false, false, 8>, 64 * 8); else go(k_goalset_queue<2, false, false, false, false, 8>, 64 * 8); }
     else if (ca.spread) { if (pre) go(k_goalset_queue<2, false, true, false, true>, 256); else go(k_goalset_queue<2, false, true, false, false>, 256); }
     else if (split && ca.work) { if (pre) go(k_goalset_queue<2, true, false, true, true>, GQ_NT); else go(k_goalset_queue<2, true, false, true, false>, GQ_NT); }
     else if (split) { if (pre) go(k_goalset_queue<2, false, false, true, true>, GQ_NT); else go(k_goalset_queue<2, false, false, true, false>, GQ_NT); }
     else if (ca.work) { if (pre) go(k_goalset_queue<2, true, false, false, true>, GQ_NT); else go(k_goalset_queue<2, true, false, false, false>, GQ_NT); }
     else { if (pre) go(k_goalset_queue<2, false, false, false, true>, GQ_NT); else go(k_goalset_queue<2, false, false, false, false>, GQ_NT); }
-    g_last_goalset_variant = (range ? 0x100 : 0) | (split ? 0x200 : 0) | (ca.spread ? 0x400 : 0) | (pre ? 0x800 : 0) | (range ? GQ_WAVES : wide);
+    g_last_goalset_variant = (split ? 0x200 : 0) | (ca.spread ? 0x400 : 0) | (pre ? 0x800 : 0) | wide;
     OMGX_CHECK_LAUNCH("k_goalset_queue");
     return OMGX_OK;
 }

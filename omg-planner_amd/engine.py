@@ -23,7 +23,6 @@ closes the job (``gather_costs``).
 from __future__ import annotations
 
 import operator
-import os
 
 import numpy as np
 import torch
@@ -113,8 +112,8 @@ class ChompEngine:
     # Fixed-goal iterations (the plan's smoothing phase: a layer-only launch + a step launch) of a batch below this many scenes run as ONE
     # pipeline part: their kernels are short chains on an almost empty chip, and three parts cost the host three times the launches — with the
     # layer in 40 pieces per scene (ops.IterationCalls._layer_only_tiling) a plan of 13 x 128 goes 4.72 -> 4.26 ms, 16 x 64 4.84 -> 4.24, 25 x 64
-    # 4.97 -> 4.64 (tools/experiments/ab_smooth_small.sh).  Larger batches keep their parts (100 scenes: 8.80-8.86 as one part against 8.72-8.74).
-    SMOOTH_SINGLE_PART_BELOW = int(os.environ.get("OMGX_SMOOTH_SINGLE_PART_BELOW", 32))
+    # 4.97 -> 4.64.  Larger batches keep their parts (100 scenes: 8.80-8.86 as one part against 8.72-8.74).
+    SMOOTH_SINGLE_PART_BELOW = 32
     WIDE_WINDOW_FROM = 57  # cfg.timesteps from which a plan's goal-set launches (their LDS follows the trajectory layer: all n waypoints) need more than 53 248 B per four-wave goal workgroup (15-16 points per link): eight waves
 
     @classmethod
@@ -207,10 +206,8 @@ class ChompEngine:
         (k_goalset_kin, one lane per (goal, configuration), through a workspace in HBM) instead of in every goal workgroup's
         prologue — the same bits from three launches per iteration instead of two."""
         self.cfg = cfg
-        if prepass is None:  # the class default, or OMGX_PREPASS=0/1 (A/B runs of one command line)
-            import os
-            env = os.environ.get("OMGX_PREPASS", "")
-            prepass = self.PREPASS_DEFAULT if env == "" else env not in ("0", "false", "no")
+        if prepass is None:
+            prepass = self.PREPASS_DEFAULT
         self.prepass = bool(prepass)
         self.latency = bool(latency_mode)
         self.goal_parts = 1 if self.latency else int(goal_parts)

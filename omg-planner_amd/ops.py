@@ -2,7 +2,6 @@
 libomg_hip.so.  Every function enqueues on torch's current stream and returns without syncing."""
 from __future__ import annotations
 
-import os
 import ctypes as C
 
 import numpy as np
@@ -894,9 +893,9 @@ class IterationCalls:
     # (goal_parts, layer_link_groups, layer_config_block, spread) of a layer-ONLY launch in the batch layout (the smoothing iterations of a
     # plan): any split gives the same bits (every element is computed on its own).  Five workgroups per scene (2 links x all waypoints)
     # take 38 us on a chip they fill to a third; TEN (one link each) shorten the launch: plan of 100 scenes 9.06 -> 8.73 ms, with early
-    # stop 7.88 -> 7.62 (round 6, tools/experiments/ab_layer_tiling.sh; config blocks on top: nothing; 13 x 128 and 16 x 64: within the noise
-    # either way).  OMGX_LAYER_ONLY_TILING="1,5,0,0" (experiments) overrides.
-    LAYER_ONLY_TILING = tuple(int(x) for x in os.environ["OMGX_LAYER_ONLY_TILING"].split(",")) if os.environ.get("OMGX_LAYER_ONLY_TILING") else None
+    # stop 7.88 -> 7.62 (round 6; config blocks on top: nothing; 13 x 128 and 16 x 64: within the noise either way).  An experiment
+    # overrides the rule by setting this attribute, e.g. (1, 5, 0, 0).
+    LAYER_ONLY_TILING = None
 
     def _layer_only_tiling(self):
         if self.LAYER_ONLY_TILING is not None:
@@ -905,7 +904,7 @@ class IterationCalls:
         if self.n > 32:
             # Long plans (50 waypoints, a dozen objects): a piece of 2 links x all waypoints is 70 us of work and a batch of 16 scenes has 80 of
             # them on 1 280 slots.  About 1 100 pieces in all, ten link groups x blocks of waypoints: plan of 16 x 64 x 50 x 13 objects 9.94 ->
-            # 8.85 ms, 8 x 64 x 50 7.92 -> 6.86, 32 x 64 x 50 13.41 -> 12.22, 100 x 64 x 50 13.23 -> 12.79 (tools/experiments/ab_layer_tiling_long.sh)
+            # 8.85 ms, 8 x 64 x 50 7.92 -> 6.86, 32 x 64 x 50 13.41 -> 12.22, 100 x 64 x 50 13.23 -> 12.79
             blocks = max(1, min(7, round(110.0 / max(S, 1))))
             return (1, 10, 0 if blocks == 1 else -(-self.n // blocks), 0)
         return (1, 10, 0, 0) if S >= 32 else (1, 10, 8, 0)  # small batches: 40 pieces per scene (13 x 128: plan 4.72 -> 4.48 by the pieces, 4.26 with the phase as one part)

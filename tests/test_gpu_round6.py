@@ -198,41 +198,55 @@ def test_persistent_launch_many_goals(dev, G):
             assert torch.equal(x, y), (k, float((x.double() - y.double()).abs().max()))
 
 
-def _set_wide(on, max8=-1, max6=-1, long6=-1):
+def _force_goal_waves(waves):
+    """The library's test hook: 0 = its own rule, 4 = never wide, 8 = eight waves wherever wide workgroups are admissible."""
     import ctypes as C
     from omg_planner_amd import _lib
-    f = _lib.lib().omgx_debug_set_wide
-    f.argtypes = [C.c_int, C.c_longlong, C.c_longlong, C.c_longlong]
-    f.restype = None
-    f(on, max8, max6, long6)
+    f = _lib.lib().omgx_debug_force_goal_waves
+    f.argtypes, f.restype = [C.c_int], None
+    f(waves)
 
 
-@pytest.mark.parametrize("waves,alg,S,G,n,kw", [
-    (8, "MD", 5, 24, 30, {}), (6, "MD", 5, 24, 30, {}), (8, "FTL", 3, 70, 30, {"standoff": True}), (6, "Exp", 9, 16, 17, {}),
-    (8, "MD", 4, 12, 30, {"goal_counts": [12, 5, 1, 9]}), (6, "MD", 2, 40, 32, {"objects": 9}), (8, "FTC", 3, 8, 5, {}),
-    (6, "MD", 3, 10, 50, {"objects": 12}), (6, "FTL", 2, 7, 64, {}), (6, "Exp", 2, 9, 41, {"standoff": True})])
-def test_wide_workgroups_change_no_bit(dev, waves, alg, S, G, n, kw):
-    """The WIDE instantiations of the batch kernel (six / eight waves per goal workgroup, chosen for launches small enough to be resident
-    at once; omg_kernels.hip gs_wide_waves): masks, tiles and the exact sum are those of four waves — every tensor the iterations
-    leave is bit for bit the same, through the dispatch-schedule measurement and the scheduled launches too."""
+def _last_goalset_variant():
+    import ctypes as C
+    from omg_planner_amd import _lib
+    probe = _lib.lib().omgx_debug_last_goalset_variant
+    probe.restype = C.c_int
+    return probe()
+
+
+@pytest.mark.parametrize("force,alg,S,G,n,kw", [
+    (8, "MD", 5, 24, 30, {}), (8, "MD", 5, 24, 30, {}), (8, "FTL", 3, 70, 30, {"standoff": True}), (8, "Exp", 9, 16, 17, {}),
+    (8, "MD", 4, 12, 30, {"goal_counts": [12, 5, 1, 9]}), (8, "MD", 2, 40, 32, {"objects": 9}), (8, "FTC", 3, 8, 5, {}),
+    (8, "MD", 3, 10, 50, {"objects": 12}), (8, "FTL", 2, 7, 64, {}), (8, "Exp", 2, 9, 41, {"standoff": True}),
+    (0, "MD", 2, 8, 57, {}), (0, "MD", 2, 8, 64, {})])
+def test_wide_workgroups_change_no_bit(dev, force, alg, S, G, n, kw):
+    """The WIDE instantiation of the batch kernel (eight waves per goal workgroup; omg_kernels.hip gs_wide_waves): masks, tiles and the
+    exact sum are those of four waves — every tensor the iterations leave is bit for bit the same, through the dispatch-schedule
+    measurement and the scheduled launches too.  Engine `a` never wide; engine `b` on eight waves, forced (8) or — the plans of 57 and 64
+    waypoints — by the library's own rule (0)."""
     try:
-        _set_wide(0)
+        _force_goal_waves(4)
         a, b = _pair(dev, S, G, n, alg, **kw)
         for e in (a, b):
             e.select_initial_goal()
             e.pose_hand_over(True)
         for t in range(8):
             a.iterate(t)
+            if t == 0:
+                assert _last_goalset_variant() == 4
         torch.cuda.synchronize()
-        _set_wide(1, 1 << 40 if waves == 8 else 0, 1 << 40 if waves == 6 else 0, 1 << 40)
+        _force_goal_waves(force)
         for t in range(8):
             b.iterate(t)
-        _same(a, b, f"{waves} waves")
+            if t == 0:
+                assert _last_goalset_variant() == 8
+        _same(a, b, f"eight waves (force {force})")
         # the stand-alone goal-set entry point (Cost.batch_obstacle_cost's numbers) as well
         ca, cb = a.goal_cost.clone(), b.goal_cost.clone()
         assert torch.equal(ca, cb)
     finally:
-        _set_wide(1, -2, -2, -2)  # back to the built-in rule
+        _force_goal_waves(0)  # back to the built-in rule
 
 
 @pytest.mark.parametrize("S,G,n,alg,proj,update_cus", [(1, 1, 12, "FTL", False, 1), (1, 5, 20, "Exp", False, 1), (1, 2, 41, "FTL", True, 2), (2, 2, 12, "MD", True, 2),
@@ -264,7 +278,7 @@ def test_persistent_launch_of_a_tiny_plan_ignores_dedicated_update_cus(dev, S, G
 
 def test_the_library_picks_the_goal_workgroups_width_by_the_window(dev, request):
     """omg_kernels.hip gs_wide_waves / launch_goalset: four waves per goal workgroup, EIGHT in plans of 57 .. 64 waypoints (the launch's LDS
-    follows the trajectory layer's n configurations: two workgroups per CU either way), split goals and latency mode never wide, waypoint ranges only behind their hook — read
+    follows the trajectory layer's n configurations: two workgroups per CU either way), split goals and latency mode never wide — read
     back through the library's test probe after real launches of the engine."""
     import ctypes as C
     import bench
@@ -284,13 +298,6 @@ def test_the_library_picks_the_goal_workgroups_width_by_the_window(dev, request)
     assert variant(2, 8, 64) == 8 and variant(2, 8, 60) == 8 and variant(2, 8, 57) == 8
     assert variant(2, 8, 64, goal_parts=2) == 0x200 | 4 and variant(2, 8, 50, goal_parts=2) == 0x200 | 4
     assert variant(1, 8, 64, latency_mode=True) & 0x400
-    f = _lib.lib().omgx_debug_set_range
-    f.argtypes, f.restype = [C.c_int], None
-    try:
-        f(40)
-        assert variant(2, 8, 50, goal_parts=2) == 0x300 | 4 and variant(2, 8, 30, goal_parts=2) == 0x200 | 4
-    finally:
-        f(-1)
 
 
 def test_an_engine_laid_out_for_plans_agrees_with_the_default_one(dev):

@@ -4,7 +4,7 @@ import csv, sys
 rows = [r for r in csv.DictReader(open(sys.argv[1])) if r["Kernel_Name"].startswith(("k_", "void k_"))]
 rows.sort(key=lambda r: int(r["Start_Timestamp"]))
 # the last plan in the trace: find the last 210+ goalset launches
-gs = [r for r in rows if "k_goalset_queue" in r["Kernel_Name"] or "k_goalset_range" in r["Kernel_Name"]]
+gs = [r for r in rows if "k_goalset_queue" in r["Kernel_Name"]]
 qs = {}
 for r in gs:
     qs.setdefault(r["Queue_Id"], []).append(r)
