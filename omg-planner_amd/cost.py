@@ -224,14 +224,7 @@ class Cost(object):
             self._pool_ref, self._pool_version = weakref.ref(t), t._version
             self._pool_host, self._infl_cache = t.detach().reshape(-1).cpu().numpy(), {}
         sc.tighten_far_boxes(table, self._pool_host, self._infl_cache)
-        ds = ops.DeviceScenes.__new__(ops.DeviceScenes)
-        ds.device = self.device
-        ds.num_scenes = 1
-        ds.objects = torch.from_numpy(table.view(np.uint8).copy()).to(self.device)
-        ds.scene_begin = torch.tensor([0, len(table)], dtype=torch.int32, device=self.device)
-        ds.pool = self.env.sdf_torch.reshape(-1)
-        if not (ds.pool.is_cuda and ds.pool.dtype == torch.float32 and ds.pool.is_contiguous()):
-            raise _lib.OmgHipError("env.sdf_torch must be a contiguous float32 device tensor")
+        ds = ops.DeviceScenes.over_pool(table, [0, len(table)], self.env.sdf_torch, "env.sdf_torch")
         import weakref
         self._scenes_cache = (key, weakref.ref(env.sdf_torch), ds, weakref.ref(lim_t))
         return ds

@@ -467,10 +467,7 @@ class ChompEngine:
         part._batch_scenes = self.S  # the scenes of the whole batch: what the chip holds while this part's launches run
         part._parts, part._forked, part.pipeline = None, False, 1
         part._hot = None
-        sc = object.__new__(ops.DeviceScenes)
-        sc.__dict__.update(self.scenes.__dict__)
-        sc.num_scenes, sc.scene_begin = hi - lo, self.scenes.scene_begin[lo:hi + 1]  # object offsets stay absolute
-        part.scenes = sc
+        part.scenes = self.scenes.scene_range(lo, hi)  # for launches only; object offsets stay absolute
         part.work = torch.zeros(part.S * self.G * (1 if self.latency else self._parts_max), dtype=torch.int32, device=self.device)
         part.schedule, part._gs_launches, part._measured, part._sched_np = None, 0, False, 1
         part._sched_buf, part._sched_flip, part._sched_age = None, 0, None

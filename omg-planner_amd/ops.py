@@ -3,11 +3,13 @@ libomg_hip.so.  Every function enqueues on torch's current stream and returns wi
 from __future__ import annotations
 
 import ctypes as C
+import time
+from collections import Counter
 
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, scenes as _sc
 from ._lib import ChompParams, LearnerParams, check
 
 _ws_cache: dict = {}
@@ -179,6 +181,52 @@ def sdf_loss_forward(pose_init, sdf_grids, sdf_limits, points, epsilons, padding
     return [pot, grad, col]
 
 
+class PoolSlots:
+    """Which part of the SDF pool each object's volume may use, as offsets and element counts.  Identical volumes are stored once
+    (scenes.pack_table(share_grids=True), scene_io); a slot several objects share is never written in place (copy-on-write)."""
+
+    def __init__(self, offsets, sizes, used: int, capacity: int):
+        self.offset = [int(o) for o in offsets]  # where object i's volume lies
+        self.cap = [int(n) for n in sizes]       # elements object i may use there
+        self.refs = Counter(self.offset)
+        self.free = []       # [(offset, capacity)] slots no object points at any more: reused before the reserve is touched
+        self.pending = {}    # object -> (offset, capacity) offered, not yet committed
+        self.used, self.capacity = int(used), int(capacity)  # the reserve is [used, capacity)
+
+    def offer(self, i: int, n: int) -> int:
+        """Offset for object i's NEXT volume of n elements: its own slot if n fits and nobody shares it, else the first free slot
+        that fits, else the reserve.  Nothing changes for i before commit(i); an offer never committed returns to the free list."""
+        old = self.pending.pop(i, None)
+        if old is not None and old[0] != self.offset[i]:
+            self.free.append(old)
+        off, cap = self.offset[i], self.cap[i]
+        if n > cap or self.refs[off] > 1:
+            for k, (_, fc) in enumerate(self.free):
+                if fc >= n:
+                    off, cap = self.free.pop(k)
+                    break
+            else:
+                if self.used + n > self.capacity:
+                    raise _lib.OmgHipError(f"the SDF pool has no room for {n} more voxels: build DeviceScenes with reserve_voxels")
+                off, cap = self.used, n
+                self.used += n
+        self.pending[i] = (off, cap)
+        return off
+
+    def commit(self, i: int) -> int:
+        """Object i moves into the slot it was offered; the slot it leaves behind is free once no object uses it."""
+        off, cap = self.pending.pop(i)
+        old = self.offset[i]
+        if off != old:
+            self.refs[old] -= 1
+            if self.refs[old] <= 0:
+                del self.refs[old]
+                self.free.append((old, self.cap[i]))
+            self.refs[off] += 1
+            self.offset[i], self.cap[i] = off, cap
+        return off
+
+
 class DeviceScenes:
     """Scene table resident in HBM: object records, scene_begin, SDF pool (see scenes.SceneBatch) — and the ways to change it
     while it stays there (include/omg_hip.h section 8): `set_object_pose` (a 48-byte write), `replace_grid` (a volume that is
@@ -186,110 +234,96 @@ class DeviceScenes:
     volume directly).  Every change is ordered on torch's current stream; launches enqueued behind it see the new scene, and a
     ChompEngine built on these scenes plans again without being rebuilt (it holds pointers, not copies).
     `reserve_voxels`: spare float32 elements at the end of the pool for volumes that outgrow their slot (the pool is never
-    reallocated: engines and prepared launches keep its address)."""
+    reallocated: engines and prepared launches keep its address).
+    DeviceScenes(batch) and from_scenes own their pool; over_pool borrows one (poses may change, volumes may not); scene_range is a
+    view of some scenes for launches (nothing may change)."""
 
-    def __init__(self, batch, device="cuda:0", reserve_voxels: int = 0):
-        from . import scenes as _sc
-        self.device = torch.device(device)
-        self.num_scenes = batch.num_scenes
-        self.host_objects = np.ascontiguousarray(batch.objects).copy()          # host mirror of the records (the region fields of a
-        self.host_scene_begin = np.ascontiguousarray(batch.scene_begin, np.int32)  # device-fitted object are stale until sync_host())
-        assert self.host_objects.dtype == _sc.OBJECT_DTYPE
-        self.objects = torch.from_numpy(self.host_objects.view(np.uint8).copy()).to(self.device)
-        self.scene_begin = torch.from_numpy(self.host_scene_begin).to(self.device)
+    def __init__(self, batch, device="cuda:0", reserve_voxels: int = 0, *, _fields=None):
+        if _fields is not None:  # from_scenes, over_pool, scene_range
+            return self._set(*_fields)
+        dev = torch.device(device)
         used = int(np.asarray(batch.pool).size)
-        pool = np.ascontiguousarray(batch.pool, np.float32)
-        if reserve_voxels > 0:
-            self.pool = torch.empty(used + int(reserve_voxels), dtype=torch.float32, device=self.device)
-            self.pool[:used].copy_(torch.from_numpy(pool))
+        pool = torch.empty(used + max(int(reserve_voxels), 0), dtype=torch.float32, device=dev)
+        pool[:used].copy_(torch.from_numpy(np.ascontiguousarray(batch.pool, np.float32).reshape(-1)))
+        self._set(np.ascontiguousarray(batch.objects).copy(), batch.scene_begin, pool, used, dev)
+
+    def _set(self, rec, scene_begin, pool, pool_used, device, shared=None):
+        """Every field of a DeviceScenes.  rec: the host mirror of the records (the region fields of a device-fitted object are
+        stale until sync_host()); pool_used None: the pool is not ours; shared: (objects, scene_begin, slots) of the table this one views."""
+        assert rec.dtype == _sc.OBJECT_DTYPE
+        self.device, self.pool, self.host_objects = torch.device(device), pool, rec
+        self.host_scene_begin = np.ascontiguousarray(scene_begin, np.int32)
+        self.num_scenes = len(self.host_scene_begin) - 1
+        self._view, self._scratch = shared is not None, None
+        if self._view:
+            self.objects, self.scene_begin, self._slots = shared
         else:
-            self.pool = torch.from_numpy(pool).to(self.device)
-        self.pool_used = used
-        sizes = self.host_objects["dim"].astype(np.int64).prod(axis=1)
-        self._slot_cap = {i: int(sizes[i]) for i in range(len(sizes))}  # elements object i may use at its grid_offset
-        # scenes.pack_table(share_grids=True) and scene_io store identical volumes once: several records then point at one offset.
-        # A slot that is shared is never written in place (copy-on-write: the object that changes gets space of its own).
-        from collections import Counter
-        self._refs = Counter(int(o) for o in self.host_objects["grid_offset"])
-        self._free = []       # [(offset, capacity)] slots no record points at any more: reused before the reserve is touched
-        self._pending = {}    # object -> (offset, capacity) handed out by grid_slot, not yet committed by replace_grid
-        self._scratch = None
+            self.objects = torch.from_numpy(rec.view(np.uint8).copy()).to(self.device)
+            self.scene_begin = torch.from_numpy(self.host_scene_begin).to(self.device)
+            self._slots = None if pool_used is None else PoolSlots(rec["grid_offset"], rec["dim"].astype(np.int64).prod(axis=1), pool_used, pool.numel())
+
+    @property
+    def pool_used(self) -> int:  # elements of the pool that hold volumes: what lies behind them is the reserve
+        return self.pool.numel() if self._slots is None else self._slots.used
+
+    def _changing(self, volumes: bool = False):  # called first by every method that changes the table
+        if self._view:
+            raise _lib.OmgHipError("a scene range is for launches: change the scenes through the table the engine was built on")
+        if volumes and self._slots is None:
+            raise _lib.OmgHipError("these scenes address a pool that belongs to somebody else: its volumes are not replaced through them")
 
     @classmethod
     def from_scenes(cls, scenes, cfg_kwargs=None, device="cuda:0", share_grids: bool = True, reserve_voxels: int = 0,
                     timing: "dict | None" = None) -> "DeviceScenes":
         """First build of a batch WITHOUT a host pass over the voxels (Env.combine_sdfs, omg/core.py:366-411; scenes.pack_table is
         the host-side specification): the records are written on the host from the scenes' poses / limits / thresholds (a few
-        hundred bytes per object), every distinct volume goes to the pool with one copy, and ALL influence regions are fitted on
-        the device in seven launches (omgx_fit_influence_regions) — volumes and thresholds that occur several times are fitted
-        once.  share_grids: a volume referenced by several objects (the same ndarray) is stored once.  The device records equal
-        scenes.pack_table(scenes, cfg_kwargs, ragged=True, share_grids=share_grids) field for field; the host mirror's region
-        fields are the loose ones until sync_host()."""
-        import time as _time
-        from . import scenes as _sc
-        t0 = _time.perf_counter()
-        cfg_kwargs = cfg_kwargs or {}
+        hundred bytes per object, scenes.ragged_records), every distinct volume goes to the pool with one copy, and ALL influence
+        regions are fitted on the device in seven launches (omgx_fit_influence_regions) — volumes and thresholds that occur several
+        times are fitted once.  share_grids: a volume referenced by several objects (the same ndarray) is stored once.  The device
+        records equal scenes.pack_table(scenes, cfg_kwargs, ragged=True, share_grids=share_grids) field for field; the host
+        mirror's region fields are the loose ones until sync_host()."""
+        t0 = time.perf_counter()
         dev = torch.device(device)
-        n_obj = sum(len(s.objects) for s in scenes)
-        rec = np.zeros(n_obj, _sc.OBJECT_DTYPE)
-        begins, chunks, seen, offset, k = [0], [], {}, 0, 0
-        for s in scenes:
-            poses, eps, pad, clr, dis = _sc.layer_params(s, **cfg_kwargs)
-            m = len(s.objects)
-            rec["pose_inv"][k: k + m] = poses[:, :3, :4].reshape(m, 12)
-            rec["epsilon"][k: k + m], rec["padding_scale"][k: k + m], rec["clearance"][k: k + m] = eps, pad, clr
-            rec["disabled"][k: k + m] = dis > 0
-            for i, ob in enumerate(s.objects):
-                mn, mxc = ob.sdf.min_coords, ob.sdf.max_coords
-                rec["lo"][k + i] = mn.astype(np.float32)
-                rec["hi"][k + i] = np.array([mn[a] + (mxc[a] - mn[a]) * 1.0 for a in range(3)], np.float32)  # scenes.pack_table (ragged)
-                rec["dim"][k + i] = ob.sdf.data.shape
-                rec["delta"][k + i] = ob.sdf.delta
-                key = id(ob.sdf.data)
-                if share_grids and key in seen:
-                    rec["grid_offset"][k + i] = seen[key]
-                else:
-                    rec["grid_offset"][k + i] = offset
-                    seen[key] = offset
-                    chunks.append((offset, ob.sdf.data))
-                    offset += int(ob.sdf.data.size)
-            k += m
-            begins.append(k)
-        _sc.finish_records(rec)  # derived constants + the loose region
-        t1 = _time.perf_counter()
-        self = cls.__new__(cls)
-        self.device = dev
-        self.num_scenes = len(scenes)
-        self.host_objects = rec
-        self.host_scene_begin = np.array(begins, np.int32)
+        rec, begins, chunks, used = _sc.ragged_records(scenes, cfg_kwargs, share_grids)
+        t1 = time.perf_counter()
         with torch.cuda.device(dev):
-            self.pool = torch.empty(offset + int(reserve_voxels), dtype=torch.float32, device=dev)
+            pool = torch.empty(used + int(reserve_voxels), dtype=torch.float32, device=dev)
             for off, data in chunks:
                 src = torch.from_numpy(np.ascontiguousarray(data, np.float32).reshape(-1))
-                self.pool[off: off + src.numel()].copy_(src, non_blocking=True)
-            self.objects = torch.from_numpy(rec.view(np.uint8).copy()).to(dev)
-            self.scene_begin = torch.from_numpy(self.host_scene_begin).to(dev)
-        self.pool_used = offset
-        sizes = rec["dim"].astype(np.int64).prod(axis=1)
-        self._slot_cap = {i: int(sizes[i]) for i in range(n_obj)}
-        from collections import Counter
-        self._refs = Counter(int(o) for o in rec["grid_offset"])
-        self._free, self._pending, self._scratch = [], {}, None
-        t2 = _time.perf_counter()
+                pool[off: off + src.numel()].copy_(src, non_blocking=True)
+            self = cls(None, _fields=(rec, begins, pool, used, dev))
+        t2 = time.perf_counter()
         self.fit_all()
         if timing is not None:
             torch.cuda.synchronize(dev)
-            t3 = _time.perf_counter()
+            t3 = time.perf_counter()
             timing.update(records_ms=(t1 - t0) * 1e3, upload_ms=(t2 - t1) * 1e3, fit_ms=(t3 - t2) * 1e3, total_ms=(t3 - t0) * 1e3)
         return self
 
+    @classmethod
+    def over_pool(cls, records, scene_begin, pool: torch.Tensor, what: str = "the pool", device="cuda") -> "DeviceScenes":
+        """Records (OBJECT_DTYPE, e.g. scenes.table_from_padded) around a pool that belongs to somebody else, addressed IN PLACE: a
+        contiguous float32 tensor of any shape on a `device` kind of device; records and scene_begin go where it lives.  Objects
+        can be moved and the mirror read back; the volumes are not ours to replace: grid_slot and replace_grid refuse."""
+        if not (pool.device.type == torch.device(device).type and pool.dtype == torch.float32 and pool.is_contiguous()):
+            raise _lib.OmgHipError(f"{what} must be a contiguous float32 device tensor")
+        return cls(None, _fields=(np.ascontiguousarray(records).copy(), scene_begin, pool.reshape(-1), None, pool.device))
+
+    def scene_range(self, lo: int, hi: int) -> "DeviceScenes":
+        """Scenes [lo, hi) as a table for launches (the engine's pipeline parts): the same record buffer, host mirror and pool, both
+        scene_begin cut to rows lo .. hi (object offsets stay absolute).  It cannot diverge from this table: every mutating method raises."""
+        if not 0 <= lo <= hi <= self.num_scenes:
+            raise IndexError(f"scenes [{lo}, {hi}) of {self.num_scenes}")
+        shared = (self.objects, self.scene_begin[lo: hi + 1], self._slots)
+        return DeviceScenes(None, _fields=(self.host_objects, self.host_scene_begin[lo: hi + 1], self.pool, None, self.device, shared))
+
     def fit_all(self) -> int:
-        """Fit the influence region of every record the kernels cull for, on the device, in seven launches
+        """Fit the influence region of every record the kernels cull for (scenes.culled), on the device, in seven launches
         (omgx_fit_influence_regions); records with the same volume CONTENT (omgx_volume_hashes: private copies of one model in many
         scenes count as one), dims, voxel size and thresholds are fitted once.  Returns the number of distinct fits."""
+        self._changing()
         rec = self.host_objects
         w = (rec["hi"].astype(np.float32) - rec["lo"].astype(np.float32)).astype(np.float32)
-        ok = (w > 0).all(axis=1) & (rec["dim"] > 1).all(axis=1) & (rec["epsilon"] < 1.0) & (rec["clearance"] <= 1.0)  # scenes.tighten_far_boxes
         l = _lib.lib()
         with torch.cuda.device(self.device):  # 128-bit content hashes of all volumes: one launch, one small download
             d_hash = torch.empty((len(rec), 2), dtype=torch.int64, device=self.device)
@@ -297,7 +331,7 @@ class DeviceScenes:
             hashes = d_hash.cpu().numpy()
         copy_src = np.full(len(rec), -1, np.int32)
         leaders, first = [], {}
-        for o in np.nonzero(ok)[0]:
+        for o in np.flatnonzero(_sc.culled(rec)):
             r = rec[o]
             key = (hashes[o].tobytes(), r["dim"].tobytes(), w[o].tobytes(), float(r["epsilon"]), float(r["clearance"]))
             lead = first.setdefault(key, int(o))
@@ -333,7 +367,7 @@ class DeviceScenes:
         """Move an object: pose_mat [4,4] (object -> world; numpy or a device tensor).  The record's pose rows become
         se3_inverse(pose_mat) in float32 (omg/util.py:129-135, what Cost.compute_obstacle_cost_layer rebuilds per call,
         omg/cost.py:303-316); its influence region lives in object coordinates and stays."""
-        from . import scenes as _sc
+        self._changing()
         idx = self._index(scene, obj)
         if isinstance(pose_mat, torch.Tensor):
             P = pose_mat.to(device=self.device, dtype=torch.float64)
@@ -354,7 +388,7 @@ class DeviceScenes:
         host mirror; record bytes and mirror end up as after set_object_pose(scene, obj, pose) with every pose given as a numpy
         array.  (set_object_pose inverts a TENSOR pose on the device with torch, whose rounding of R^T t is its own; here a
         tensor takes the numpy path, so the equality is with set_object_pose's numpy path whatever the input type.)"""
-        from . import scenes as _sc
+        self._changing()
         pairs = np.asarray(indices, np.int64).reshape(-1, 2)
         if isinstance(poses, torch.Tensor):
             poses = poses.detach().cpu().numpy()
@@ -374,43 +408,13 @@ class DeviceScenes:
 
     def grid_slot(self, scene: int, obj: int, shape) -> torch.Tensor:
         """A float32 [X,Y,Z] view into the pool where the object's NEXT volume can be written in place (e.g. by
-        point_cloud_sdf(out=...)): the object's own slot if the shape fits and no other object shares it, else a slot nobody
-        uses any more, else fresh space from the reserve.  Nothing about the object changes until replace_grid is given the view:
-        a slot handed out and never used goes back to the free list with the next grid_slot call for the same object.
+        point_cloud_sdf(out=...)), chosen by PoolSlots.offer.  Nothing about the object changes until replace_grid is given the view.
         Sizing the reserve: one extra volume per object whose cloud extents grow from frame to frame (a slot that is outgrown
         is reused by the next volume that fits it), plus one per object that shares its volume and will be changed."""
-        idx = self._index(scene, obj)
+        self._changing(volumes=True)
         n = int(np.prod(shape))
-        old = self._pending.pop(idx, None)
-        if old is not None and old[0] != int(self.host_objects[idx]["grid_offset"]):
-            self._free.append(old)  # handed out earlier, never committed
-        off, cap = int(self.host_objects[idx]["grid_offset"]), self._slot_cap[idx]
-        if n > cap or self._refs[off] > 1:
-            for k, (fo, fc) in enumerate(self._free):
-                if fc >= n:
-                    off, cap = self._free.pop(k)
-                    break
-            else:
-                if self.pool_used + n > self.pool.numel():
-                    raise _lib.OmgHipError(f"the SDF pool has no room for {n} more voxels: build DeviceScenes with reserve_voxels")
-                off, cap = self.pool_used, n
-                self.pool_used += n
-        self._pending[idx] = (off, cap)
+        off = self._slots.offer(self._index(scene, obj), n)
         return self.pool[off: off + n].view(tuple(int(d) for d in shape))
-
-    def _commit_slot(self, idx: int, n: int):
-        """replace_grid: the object moves into the slot grid_slot handed out; a slot it leaves behind is free once no record uses it."""
-        off, cap = self._pending.pop(idx)
-        old = int(self.host_objects[idx]["grid_offset"])
-        if off != old:
-            self._refs[old] -= 1
-            if self._refs[old] <= 0:
-                del self._refs[old]
-                self._free.append((old, self._slot_cap[idx]))
-            self._refs[off] += 1
-            self._slot_cap[idx] = cap
-            self.host_objects[idx]["grid_offset"] = off
-        return off
 
     def replace_grid(self, scene: int, obj: int, grid: torch.Tensor, origin, delta: float, fit: str = "device") -> None:
         """Give an object a new volume that is already on the device: grid [X,Y,Z] float32 (a view from grid_slot: used in place;
@@ -418,6 +422,7 @@ class DeviceScenes:
         limits follow like scenes.pack_table writes them; the influence region is fitted ON THE DEVICE (fit="device":
         omgx_fit_influence_region, the algorithm of scenes.influence_rbox) or left loose (fit="loose": the grid with 1.5 voxels
         of slack — same results, more exact lookups)."""
+        self._changing(volumes=True)
         if fit not in ("device", "loose"):
             raise ValueError("fit must be 'device' or 'loose'")
         _need(grid, torch.float32, "grid")
@@ -426,23 +431,18 @@ class DeviceScenes:
         idx = self._index(scene, obj)
         shape = tuple(int(d) for d in grid.shape)
         n = int(np.prod(shape))
-        pend = self._pending.get(idx)
+        pend = self._slots.pending.get(idx)
         if pend is not None and n <= pend[1] and grid.data_ptr() == self.pool.data_ptr() + 4 * pend[0]:
             slot = grid  # the view grid_slot handed out, filled in place
         else:
             slot = self.grid_slot(scene, obj, shape)
             slot.copy_(grid)
-        self._commit_slot(idx, n)
         rec = self.host_objects[idx]
-        mn = np.asarray(origin, np.float64)
-        mxc = mn + float(delta) * np.array(shape)
-        lo = mn.astype(np.float32)
-        hi = np.array([mn[a] + (mxc[a] - mn[a]) * 1.0 for a in range(3)], np.float32)  # scenes.pack_table (ragged)
+        rec["grid_offset"] = self._slots.commit(idx)
+        lo, hi = _sc.grid_limits(origin, shape, delta)
         dims = np.array(shape, np.int32)
         rec["lo"], rec["hi"], rec["dim"], rec["delta"] = lo, hi, dims, np.float32(delta)
-        one = self.host_objects[idx: idx + 1]
-        from . import scenes as _sc
-        _sc.finish_records(one)  # host mirror: derived constants + the loose region
+        _sc.finish_records(self.host_objects[idx: idx + 1])  # host mirror: derived constants + the loose region
         l = _lib.lib()
         vp = C.c_void_p
         with torch.cuda.device(self.device):
@@ -458,13 +458,12 @@ class DeviceScenes:
 
     def sync_host(self) -> np.ndarray:
         """Bring the host mirror of the records up to date with the device (one small copy; tests, oracle comparisons)."""
-        self.host_objects = self.objects.cpu().numpy().view(self.host_objects.dtype).copy()
+        self.host_objects[:] = self.objects.cpu().numpy().view(self.host_objects.dtype)  # in place: scene ranges share the mirror
         return self.host_objects
 
     def host_batch(self):
         """The scenes as they are on the device now, as a host SceneBatch (records + pool copied back): for oracle checks."""
-        from . import scenes as _sc
-        return _sc.SceneBatch(self.sync_host(), self.host_scene_begin.copy(), self.pool[: self.pool_used].cpu().numpy())
+        return _sc.SceneBatch(self.sync_host().copy(), self.host_scene_begin.copy(), self.pool[: self.pool_used].cpu().numpy())
 
 
 def robot_blob(model, device="cuda:0") -> torch.Tensor:
@@ -1014,7 +1013,6 @@ class MeshPool:
     volume fields of a record are set_volume's; first_workgroup is the caller's."""
 
     def __init__(self, meshes, drop_zero_area: bool):
-        from . import scenes as _sc
         if len(meshes) < 1:
             raise _lib.OmgHipError("a batch of meshes needs at least one mesh")
         self.rec = (_lib.Mesh * len(meshes))()
@@ -1036,7 +1034,6 @@ class MeshPool:
     def set_volume(self, m: int, origin, delta, sample, dims, out_offset, padding=4):
         """The grid of mesh m's volume into its record: origin [3] and nodes per axis (both None: scenes.mesh_grid_layout with
         `padding`), node spacing, "centre" or "node", the element offset of the volume in its buffer -> (origin, dims)."""
-        from . import scenes as _sc
         if sample not in _sc.MESH_SAMPLE_OFFSET:
             raise _lib.OmgHipError(f"mesh {m}: sample must be 'centre' or 'node', got {sample!r}")
         r = self.rec[m]
@@ -1055,7 +1052,6 @@ class MeshPool:
 
 def _mesh_grid(verts, delta, padding, origin, dims, m: int = 0):
     """(origin [3] float64, dims as ints) of mesh m's grid: as given, or scenes.mesh_grid_layout's around `verts`."""
-    from . import scenes as _sc
     if not (float(delta) > 0 and np.isfinite(float(delta))):
         raise _lib.OmgHipError(f"mesh {m}: delta must be positive and finite, got {delta}")
     if (origin is None) != (dims is None):

@@ -195,20 +195,26 @@ def influence_rbox(grid: np.ndarray, epsilon: float, clearance: float, vox: np.n
     return best[1], best[2], best[3]
 
 
+def culled(rec: np.ndarray) -> np.ndarray:
+    """bool [n]: the records the kernels cull for, the ones whose influence region is worth fitting — a positive extent, more than
+    one voxel along every axis, and thresholds an out-of-range lookup (which returns 1.0) cannot reach: epsilon < 1, clearance <= 1."""
+    w = (rec["hi"].astype(np.float32) - rec["lo"].astype(np.float32)).astype(np.float32)
+    return (w > 0).all(axis=-1) & (rec["dim"] > 1).all(axis=-1) & (rec["epsilon"] < 1.0) & (rec["clearance"] <= 1.0)
+
+
 def tighten_far_boxes(rec: np.ndarray, pool: np.ndarray, cache: dict | None = None) -> np.ndarray:
     """Replace the default influence region of every record (the whole grid) by the fitted rounded box (influence_rbox) of
     the lookups that can matter, grown by 1 % of a voxel + 1e-6 m for the float32 rounding of the kernels' coordinates.
-    Only meaningful where the kernels cull at all (epsilon < 1 and clearance <= 1: an out-of-range lookup returns 1.0).
+    Only meaningful where the kernels cull at all (`culled`).
     A record nothing can reach gets R^2 = -1 (every point is rejected).
     `cache` (optional dict) keeps the fits between calls (key: the volume's CONTENT, voxel sizes, epsilon, clearance — scenes
     with private copies of one model share the fit)."""
     import hashlib
     cache = {} if cache is None else cache
-    for r in rec:
+    for o in np.flatnonzero(culled(rec)):
+        r = rec[o]
         d = r["dim"].astype(np.int64)
         w = (r["hi"].astype(np.float32) - r["lo"].astype(np.float32)).astype(np.float32)
-        if not ((w > 0).all() and (d > 1).all() and r["epsilon"] < 1.0 and r["clearance"] <= 1.0):
-            continue
         g = pool[int(r["grid_offset"]): int(r["grid_offset"]) + int(d.prod())]
         vox = (w / d.astype(np.float32)).astype(np.float64)
         key = (hashlib.blake2b(np.ascontiguousarray(g).tobytes(), digest_size=12).digest(), tuple(d), tuple(vox), float(r["epsilon"]), float(r["clearance"]))
@@ -552,6 +558,42 @@ class SceneBatch:
         return SceneBatch(rec, (self.scene_begin[first:last + 1] - lo_o).astype(np.int32), self.pool[p0:p1])
 
 
+def grid_limits(origin, shape, delta):
+    """(lo, hi) float32 [3] a record keeps of a grid of `shape` voxels of size `delta` with its min corner at `origin`: hi is
+    combine_sdfs' stretched max coordinate with max_shape == size (omg/core.py:366-411), float64 arithmetic rounded to float32 ONCE."""
+    mn = np.asarray(origin, np.float64)
+    mxc = mn + float(delta) * np.array(shape)
+    return mn.astype(np.float32), np.array([mn[a] + (mxc[a] - mn[a]) * 1.0 for a in range(3)], np.float32)
+
+
+def ragged_records(scenes, cfg_kwargs=None, share_grids: bool = True):
+    """The records of `scenes` in the ragged engine layout, without touching a voxel -> (rec after finish_records, scene_begin
+    int32 [S+1], chunks = [(offset, ndarray)] of the distinct volumes in pool order, the elements they take).  share_grids: a
+    volume several objects reference (the same ndarray) once.  pack_table concatenates the chunks, DeviceScenes.from_scenes uploads them."""
+    cfg_kwargs = cfg_kwargs or {}
+    rec = np.zeros(sum(len(s.objects) for s in scenes), OBJECT_DTYPE)
+    begins, chunks, seen, offset, k = [0], [], {}, 0, 0
+    for s in scenes:
+        poses, eps, pad, clr, dis = layer_params(s, **cfg_kwargs)
+        m = len(s.objects)
+        rec["pose_inv"][k: k + m] = poses[:, :3, :4].reshape(m, 12)
+        rec["epsilon"][k: k + m], rec["padding_scale"][k: k + m], rec["clearance"][k: k + m] = eps, pad, clr
+        rec["disabled"][k: k + m] = dis > 0
+        for i, ob in enumerate(s.objects):
+            rec["lo"][k + i], rec["hi"][k + i] = grid_limits(ob.sdf.min_coords, ob.sdf.data.shape, ob.sdf.delta)
+            rec["dim"][k + i] = ob.sdf.data.shape
+            rec["delta"][k + i] = ob.sdf.delta
+            key = id(ob.sdf.data)
+            if not (share_grids and key in seen):
+                seen[key] = offset
+                chunks.append((offset, ob.sdf.data))
+                offset += int(ob.sdf.data.size)
+            rec["grid_offset"][k + i] = seen[key]
+        k += m
+        begins.append(k)
+    return finish_records(rec), np.array(begins, np.int32), chunks, offset
+
+
 def pack_table(scenes, cfg_kwargs=None, ragged: bool = True, share_grids: bool = True, tight: bool = True) -> SceneBatch:
     """Pack scenes into the engine layout.
 
@@ -563,45 +605,25 @@ def pack_table(scenes, cfg_kwargs=None, ragged: bool = True, share_grids: bool =
     tight=True shrinks each record's far box to the voxels that can contribute (tighten_far_boxes): same results,
     fewer exact lookups.
     """
-    cfg_kwargs = cfg_kwargs or {}
-    recs, begins, chunks, offset = [], [0], [], 0
-    seen = {}
-    for sc in scenes:
-        poses, eps, pad, clr, dis = layer_params(sc, **cfg_kwargs)
-        if ragged:
-            for i, ob in enumerate(sc.objects):
-                r = np.zeros((), OBJECT_DTYPE)
-                r["pose_inv"] = poses[i][:3, :4].ravel()
-                r["lo"] = ob.sdf.min_coords.astype(np.float32)
-                # same float32 arithmetic as combine_sdfs with max_shape == size
-                mn, mxc = ob.sdf.min_coords, ob.sdf.max_coords
-                r["hi"] = np.array([mn[a] + (mxc[a] - mn[a]) * 1.0 for a in range(3)], np.float32)
-                r["dim"] = ob.sdf.data.shape
-                r["delta"] = ob.sdf.delta
-                r["epsilon"], r["padding_scale"], r["clearance"] = eps[i], pad[i], clr[i]
-                r["disabled"] = 1 if dis[i] > 0 else 0
-                key = id(ob.sdf.data)
-                if share_grids and key in seen:
-                    r["grid_offset"] = seen[key]
-                else:
-                    r["grid_offset"] = offset
-                    seen[key] = offset
-                    chunks.append(np.ascontiguousarray(ob.sdf.data, np.float32).ravel())
-                    offset += chunks[-1].size
-                recs.append(r)
-        else:
+    if ragged:
+        rec, begins, chunks, _ = ragged_records(scenes, cfg_kwargs, share_grids)
+        chunks = [np.ascontiguousarray(data, np.float32).ravel() for _, data in chunks]
+    else:
+        recs, begins, chunks, offset = [], [0], [], 0
+        for sc in scenes:
+            poses, eps, pad, clr, dis = layer_params(sc, **(cfg_kwargs or {}))
             sdf, lim = pack_padded(sc.objects)
             t = table_from_padded(poses, lim, eps, pad, clr, dis)
             t["grid_offset"] += offset
             chunks.append(sdf.ravel())
             offset += sdf.size
             recs.extend(list(t))
-        begins.append(len(recs))
-    rec = finish_records(np.array(recs, OBJECT_DTYPE))
+            begins.append(len(recs))
+        rec, begins = finish_records(np.array(recs, OBJECT_DTYPE)), np.array(begins, np.int32)
     pool = np.concatenate(chunks) if chunks else np.zeros(0, np.float32)
     if tight:
         tighten_far_boxes(rec, pool)
-    return SceneBatch(rec, np.array(begins, np.int32), pool)
+    return SceneBatch(rec, begins, pool)
 
 
 # ------------------------------------------------------------------------------------------------

@@ -271,3 +271,41 @@ def test_first_build_on_the_device_is_the_host_pack_table(dev, S, share):
     c.select_initial_goal()
     r = engine_vs_oracle(c, want, [0, S // 2, S - 1], steps=6, pin_window=False)
     assert r["goal_idx_equal"] and r["max_traj_err"] <= 1e-9 and r["max_cost_rel_err"] <= 1e-5, r
+
+
+def test_scene_changes_through_the_parent_table_reach_every_pipeline_part(dev):
+    """A pipelined engine launches through contiguous scene ranges of the table it was built on.  Plan with two parts; then, through
+    the PARENT table, move an object of scene 3 and give an object of scene 2 — both lie in the second part — a volume that
+    outgrows its slot; plan again with the same engine: every output equals, bit for bit, that of a fresh single-stream engine
+    built on what the device holds now."""
+    import bench
+    from omg_planner_amd import ops, scenes as sc
+    from omg_planner_amd.engine import ChompEngine
+    S, G = 4, 8
+    cfg, model, batch, start, goals = bench.build_workload(S, G, 30, 32, 0, False)  # private volumes
+    vol = sc.sphere_sdf(0.22, (34, 32, 32), 0.6 / 32)  # larger than the 32^3 slot it replaces: the reserve holds just this one
+    ds = ops.DeviceScenes(batch, dev, reserve_voxels=int(vol.data.size))
+    eng = ChompEngine(model, ds, copy.deepcopy(cfg), start, goals, device=dev, ol_alg="MD")
+    eng.pipeline = 2
+    fresh = eng.snapshot()
+    eng.plan(early_stop=False)
+    torch.cuda.synchronize()
+    assert eng._parts is not None and [(p._lo, p.S) for p in eng._parts] == [(0, 2), (2, 2)]
+    before = eng.traj.cpu().numpy().copy()
+    eng.restore(fresh)
+    ds.set_object_pose(3, 1, sc._yaw_pose(0.45, 0.12, 0.16, 0.7))
+    ds.replace_grid(2, 1, torch.from_numpy(vol.data).to(dev), vol.origin, vol.delta, fit="device")
+    assert int(ds.host_objects[ds.host_scene_begin[2] + 1]["grid_offset"]) == batch.pool.size  # it left its slot for the reserve
+    eng.plan(early_stop=False)
+    torch.cuda.synchronize()
+    keys = ("traj", "info", "goal_idx", "goal_cost", "pot", "col")
+    after = {k: getattr(eng, k).cpu().numpy().copy() for k in keys}
+    moved = np.abs(after["traj"] - before).reshape(S, -1).max(axis=1)
+    print("largest change of a waypoint per scene:", moved)
+    assert moved[0] == 0 and moved[1] == 0 and moved[2] > 1e-5 and moved[3] > 1e-5  # both changes matter, and only where they were made
+    eng2 = ChompEngine(model, ds.host_batch(), copy.deepcopy(cfg), start, goals, device=dev, ol_alg="MD")
+    eng2.pipeline = 1
+    eng2.plan(early_stop=False)
+    torch.cuda.synchronize()
+    for k in keys:
+        assert np.array_equal(after[k], getattr(eng2, k).cpu().numpy(), equal_nan=True), k
