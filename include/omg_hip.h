@@ -904,6 +904,60 @@ int omgx_register_clouds(const omgx_object* objects, const omgx_object* h_object
                          double* poses_out, double* stats_out, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * (16) omgx_surface_count, omgx_surface_gather: triangle meshes from distance volumes
+ * Stands in for what the reference keeps on disk: a mesh file beside every volume file (omg/core.py:86-127 loads the SDF,
+ * ycb_render the mesh), and for an object it has no mesh of, grasps from an outside source (cfg.external_grasps,
+ * omg/planner.py:176-186).  Here the level set {v = level} of M volumes of the SDF pool (a ragged batch) becomes M closed,
+ * outward-oriented triangle meshes in the vertex / face pools the mesh kernels read, in a fixed order, by naive surface nets.
+ * omg-planner_amd/scenes.py (surface_nets) is the specification; the vertices are float64 with + - * / only, without
+ * contraction, and have the specification's bits.  New entry points only: omgx_abi_version() stays 14.
+ *
+ * A volume is an omgx_mesh record: origin, delta, sample_offset, dims, out_offset = the element offset of sample (0,0,0) in
+ * `pool` (x-major: sample (i,j,k) at pool[out_offset + (i * dims[1] + j) * dims[2] + k] sits at
+ * origin + ((i,j,k) + sample_offset) * delta), first_workgroup = the prefix table of omgx_mesh_sdf with
+ * OMGX_SURFACE_NODES_PER_WORKGROUP samples per workgroup; vert_begin / vert_count, face_begin / face_count: the mesh's rows of
+ * the output pools.
+ *   inside(i,j,k)   v < level, compared as float32: NaN is outside
+ *   cell (i,j,k)    0 <= i < dims[0] - 1 and so on; corners (i+dx, j+dy, k+dz); active iff neither all inside nor all outside
+ *   vertex          one per active cell.  Its 12 edges in the order axis x, y, z and, within an axis, the offsets (u, w) on the two
+ *                   other axes taken cyclically (x -> (y,z), y -> (z,x), z -> (x,y)) through 00, 01, 10, 11; an edge from corner a
+ *                   to b = a + e_axis crosses iff inside(a) != inside(b), at t = (L - va) / (vb - va), L = (double)level, the
+ *                   samples widened to double; t outside [0,1] (samples that are not finite): t = 0.5.  The crossing point has t on
+ *                   the axis and u, w on the two others; local = (their sum, in that order, per component, from +0.0) / count;
+ *                   vertex = origin + (((i,j,k) + sample_offset) + local) * delta
+ *   vertex order    by the cell's x-major index, ascending
+ *   faces           every sample edge a -> a + e_axis with inside(a) != inside(b) has four cells around it, (o1, o2) the cyclic
+ *                   other axes: c0 = a - e_o1 - e_o2, c1 = a - e_o2, c2 = a, c3 = a - e_o1.  One of them outside the grid: the
+ *                   edge gives nothing and counts as one open edge.  Otherwise two triangles split along c0-c2, the normal from
+ *                   inside to outside: (c0,c1,c2), (c0,c2,c3) if inside(a), else (c0,c2,c1), (c0,c3,c2); indices local to the mesh
+ *   face order      by 3 * linear(a) + axis, ascending, the two triangles of an edge adjacent
+ * A volume with a dims < 2 has no cells: an empty mesh, every crossing edge open.  All inside or all outside: an empty mesh.
+ * A mesh is closed iff it has no open edge.
+ *
+ * omgx_surface_count: one thread per sample; per workgroup the numbers of vertices, closed crossing edges and open edges, and the
+ *   rank of every active cell inside its workgroup, into `workspace` (omgx_surface_workspace_bytes bytes); a second launch, one
+ *   workgroup per volume, turns the totals into exclusive offsets in place and writes counts [M][4] int32 (device) =
+ *   (vertices, faces, open edges, 0).  The vert / face fields of the records are ignored.
+ * omgx_surface_gather: the same records with the ranges the host assigned from `counts`, `workspace` as omgx_surface_count left
+ *   it, the same pool and level.  verts [vert_cap][3] double, faces [face_cap][3] int32.  Rows at or beyond
+ *   vert_begin + vert_count, face_begin + face_count or the caps are not written; rows outside every range are neither read nor
+ *   written.  Deterministic, no atomics.
+ * `meshes` are the records on the device, h_meshes the same on the host; ALL checks are made on the host copies before any HIP call.
+ * OMGX_ERR_INVALID: a null pointer (verts with vert_cap == 0 and faces with face_cap == 0 may be NULL), M < 1, a dims < 1,
+ * delta <= 0 or not finite, a sample_offset other than 0.0 / 0.5, an origin that is not finite, a volume outside
+ * [0, pool_elems), a first_workgroup that is not the prefix sum, a level that is NaN, a negative begin, count or cap, ranges of
+ * two meshes that overlap.  OMGX_ERR_UNSUPPORTED: more than 2^31 - 1 samples in one volume or workgroups in all.
+ * omgx_surface_workspace_bytes: 16 + 256 bytes per workgroup, or the error of the records.
+ * ------------------------------------------------------------------------------------------- */
+#define OMGX_SURFACE_NODES_PER_WORKGROUP 256
+int64_t omgx_surface_workspace_bytes(const omgx_mesh* h_meshes, int32_t num_meshes);
+int omgx_surface_count(const float* pool, int64_t pool_elems, const omgx_mesh* meshes, const omgx_mesh* h_meshes,
+                       int32_t num_meshes, float level, void* workspace, int32_t* counts, void* stream);
+int omgx_surface_gather(const float* pool, int64_t pool_elems, const omgx_mesh* meshes, const omgx_mesh* h_meshes,
+                        int32_t num_meshes, float level, const void* workspace, double* verts, int64_t vert_cap,
+                        int32_t* faces, int64_t face_cap, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Diagnostics
  * ------------------------------------------------------------------------------------------- */
 const char* omgx_last_error(void); /* thread-local text of the last OMGX_ERR_LAUNCH               */

@@ -208,3 +208,50 @@ def observe_scenes(scenes, meshes, cam_from_world, intrinsics, H: int, W: int, c
     batch = ops.CameraBatch(pool, instances, inst_begin, cameras, device=device)
     t, inst, face = ops.render_depth(batch, H, W, cull=cull)
     return Observation(batch, t, inst, face)
+
+
+def table_object_poses(table) -> np.ndarray:
+    """world_from_obj [n,4,4] float64 of every record of an ops.DeviceScenes, from the host mirror: the inverse, in float64, of the
+    float32 rows [R t] the record keeps (pose_inv)."""
+    inv = np.asarray(table.host_objects["pose_inv"], np.float64).reshape(-1, 3, 4)
+    out = np.tile(np.eye(4), (len(inv), 1, 1))
+    for k, m in enumerate(inv):
+        out[k, :3, :3] = m[:, :3].T
+        out[k, :3, 3] = -(m[:, :3].T @ m[:, 3])
+    return out
+
+
+def observe_table(table, cam_from_world, intrinsics, H: int, W: int, level: float = 0.0, targets=None, skip=(), cull: bool = True) -> Observation:
+    """observe_scenes for an ops.DeviceScenes that has no meshes: the level set of every object's volume is extracted on the device
+    (DeviceScenes.object_surfaces, read in place, shared volumes once), downloaded once, and drawn at the object's pose
+    (table_object_poses) through the host-side builders of observe_scenes (instance_records, ops.CameraBatch).  targets [S]: the
+    object of each scene that gets label 0 (default 0), every other object 1; skip: (scene, object) pairs that are not drawn (a
+    table slab); an object whose surface is empty at `level` is not drawn either.  It does not call the planner."""
+    from . import ops
+    S = table.num_scenes
+    cfw = np.broadcast_to(np.asarray(cam_from_world, np.float64), (S, 4, 4))
+    intr = np.broadcast_to(np.asarray(intrinsics, np.float64), (S, 4))
+    verts, faces, vrows, frows, _ = table.object_surfaces(level=level)
+    hv, hf = verts.cpu().numpy(), faces.cpu().numpy()
+    poses, skip = table_object_poses(table), {(int(s), int(o)) for s, o in skip}
+    pool, where, recs, begin = [], {}, [], [0]
+    for s in range(S):
+        lo, hi = int(table.host_scene_begin[s]), int(table.host_scene_begin[s + 1])
+        target = 0 if targets is None else int(targets[s])
+        idx, ps, labels = [], [], []
+        for k in range(lo, hi):
+            if (s, k - lo) in skip or frows[k, 1] == 0:
+                continue
+            key = (int(vrows[k, 0]), int(frows[k, 0]))
+            if key not in where:
+                where[key] = len(pool)
+                pool.append((hv[vrows[k, 0]: vrows[k, 0] + vrows[k, 1]], hf[frows[k, 0]: frows[k, 0] + frows[k, 1]]))
+            idx.append(where[key]), ps.append(poses[k]), labels.append(0 if k - lo == target else 1)
+        recs.append(instance_records(pool, idx, ps, labels, cfw[s]))
+        begin.append(begin[-1] + len(idx))
+    if not pool:
+        raise ValueError("no object of any scene has a surface at this level")
+    cameras = np.stack([camera_rows(intr[s], cfw[s]) for s in range(S)])
+    batch = ops.CameraBatch(pool, np.concatenate(recs), np.array(begin, np.int64), cameras, device=table.device)
+    t, inst, face = ops.render_depth(batch, H, W, cull=cull)
+    return Observation(batch, t, inst, face)

@@ -456,6 +456,37 @@ class DeviceScenes:
                                                   lo.ctypes.data_as(vp), hi.ctypes.data_as(vp), float(rec["epsilon"]), float(rec["clearance"]),
                                                   _ptr(self._scratch), _stream()), "omgx_fit_influence_region")
 
+    def surface_records(self, indices):
+        """The volumes of the objects `indices` (rows of the record table) as omgx_mesh records for omgx_surface_count /
+        omgx_surface_gather: origin = the record's lo, its delta and dim, voxel centres, out_offset = its grid_offset in the pool,
+        first_workgroup the prefix table.  From the host mirror: nothing is downloaded."""
+        rec = self.host_objects
+        idx = [int(i) for i in indices]
+        if any(not 0 <= i < len(rec) for i in idx):
+            raise IndexError(f"object rows must lie in [0, {len(rec)})")
+        return surface_records([(rec["lo"][i].astype(np.float64), float(rec["delta"][i]), "centre", rec["dim"][i], int(rec["grid_offset"][i])) for i in idx])
+
+    def object_surfaces(self, pairs=None, level: float = 0.0):
+        """The level set of the volumes of the (scene, object) `pairs` (default: every object) as triangle meshes, read IN PLACE
+        from the pool (ops.surface_meshes: nothing is uploaded but the records) -> (verts [V,3] float64 and faces [F,3] int32 on the
+        device, vert_rows [n,2] and face_rows [n,2] = (begin, count) per pair, open_edges [n]; host int64).  Objects that share a
+        volume (share_grids) are extracted once and name the same rows.  Coordinates are in the object's own frame, like its volume."""
+        if pairs is None:
+            idx = list(range(len(self.host_objects)))
+        else:
+            idx = [self._index(int(s), int(o)) for s, o in np.asarray(pairs, np.int64).reshape(-1, 2)]
+        rec, first, which = self.host_objects, {}, []
+        for i in idx:
+            key = (int(rec["grid_offset"][i]), rec["dim"][i].tobytes(), rec["lo"][i].tobytes(), rec["delta"][i].tobytes())
+            which.append(first.setdefault(key, len(first)))
+        if not idx:
+            z = np.zeros((0, 2), np.int64)
+            return (torch.empty((0, 3), dtype=torch.float64, device=self.device), torch.empty((0, 3), dtype=torch.int32, device=self.device), z, z.copy(),
+                    np.zeros(0, np.int64))
+        leaders = [idx[which.index(u)] for u in range(len(first))]
+        verts, faces, vrows, frows, open_edges = surface_meshes(self.pool, self.surface_records(leaders), level)
+        return verts, faces, vrows[which], frows[which], open_edges[which]
+
     def sync_host(self) -> np.ndarray:
         """Bring the host mirror of the records up to date with the device (one small copy; tests, oracle comparisons)."""
         self.host_objects[:] = self.objects.cpu().numpy().view(self.host_objects.dtype)  # in place: scene ranges share the mirror
@@ -1139,6 +1170,94 @@ def mesh_sdf(verts, faces, delta, padding=4, sample="centre", origin=None, dims=
         import logging
         logging.getLogger(__name__).debug("mesh_sdf: dropped %d faces of zero area", dropped[0])
     return grids[0], org[0], deltas[0]
+
+
+def surface_records(volumes):
+    """omgx_mesh records (a ctypes array) of the volumes [(origin [3], delta, "centre" or "node", dims [3], element offset in the
+    pool)] for omgx_surface_count / omgx_surface_gather, first_workgroup filled in; the vert / face fields are left zero.  An array
+    of records passes through a copy (its first_workgroup is rewritten)."""
+    if isinstance(volumes, C.Array) and getattr(volumes, "_type_", None) is _lib.Mesh:
+        rec = (_lib.Mesh * len(volumes))()
+        C.memmove(rec, volumes, C.sizeof(rec))
+    else:
+        volumes = list(volumes)
+        rec = (_lib.Mesh * len(volumes))()
+        for m, (origin, delta, sample, dims, offset) in enumerate(volumes):
+            if sample not in _sc.MESH_SAMPLE_OFFSET:
+                raise _lib.OmgHipError(f"volume {m}: sample must be 'centre' or 'node', got {sample!r}")
+            origin, dims = np.asarray(origin, np.float64).reshape(-1), [int(d) for d in np.asarray(dims).reshape(-1)]
+            if len(origin) != 3 or len(dims) != 3 or min(dims) < 1 or int(offset) < 0:
+                raise _lib.OmgHipError(f"volume {m}: origin [3], three dims >= 1 and an offset >= 0, got {origin}, {dims} and {offset}")
+            if not (float(delta) > 0 and np.isfinite(float(delta)) and np.isfinite(origin).all()):
+                raise _lib.OmgHipError(f"volume {m}: delta must be positive and finite and the origin finite, got {delta} and {origin}")
+            r = rec[m]
+            r.origin[:], r.delta, r.sample_offset, r.dims[:], r.out_offset = list(origin), float(delta), _sc.MESH_SAMPLE_OFFSET[sample], dims, int(offset)
+    if len(rec) < 1:
+        raise _lib.OmgHipError("a batch of volumes needs at least one volume")
+    wg = 0
+    for r in rec:
+        r.first_workgroup = wg
+        wg += -(-(int(r.dims[0]) * int(r.dims[1]) * int(r.dims[2])) // _lib.SURFACE_NODES_PER_WORKGROUP)
+    return rec
+
+
+def surface_meshes(pool: torch.Tensor, records_or_layouts, level: float = 0.0, out=None):
+    """The level sets {v = level} of M volumes of `pool` as closed, outward-oriented triangle meshes, on the device
+    (omgx_surface_count, omgx_surface_gather; scenes.surface_nets is the specification: the same float64 vertices bit for bit, the
+    same faces in the same order).  pool: a contiguous float32 device tensor (the SDF pool, or any volume) read IN PLACE;
+    records_or_layouts: what surface_records takes.  Count, ONE download of the counts, an exact allocation, gather.
+    -> (verts [V_total,3] float64, faces [F_total,3] int32 with indices local to their mesh: device; vert_rows [M,2] and
+    face_rows [M,2] = (begin, count) of mesh m's rows, open_edges [M]: host int64).  A mesh with open_edges > 0 left its grid and
+    is not closed there.  out: (verts [cap,3], faces [cap,3]) of the caller's, written IN PLACE instead; rows beyond a cap are
+    not written (the tables still tell what the mesh has).  The meshes lie back to back from row 0, in order."""
+    _need(pool, torch.float32, "pool")
+    level = float(level)
+    if np.isnan(np.float32(level)):
+        raise _lib.OmgHipError("level is NaN")
+    rec = surface_records(records_or_layouts)
+    M, dev, l, vp = len(rec), pool.device, _lib.lib(), C.c_void_p
+    elems = int(pool.numel())
+    for m, r in enumerate(rec):
+        n = int(r.dims[0]) * int(r.dims[1]) * int(r.dims[2])
+        if r.out_offset < 0 or r.out_offset + n > elems:
+            raise _lib.OmgHipError(f"volume {m} (offset {r.out_offset}, {n} elements) leaves the pool of {elems}")
+    if out is not None:
+        for t, name, dt in ((out[0], "out[0]", torch.float64), (out[1], "out[1]", torch.int32)):
+            _need(t, dt, name)
+            if t.device != dev or t.dim() != 2 or t.shape[1] != 3:
+                raise _lib.OmgHipError(f"{name} must be [cap,3] on {dev}, got {tuple(t.shape)} on {t.device}")
+    nbytes = int(l.omgx_surface_workspace_bytes(C.cast(rec, vp), M))
+    check(min(nbytes, 0), "omgx_surface_workspace_bytes")
+    with torch.cuda.device(dev):
+        ws = torch.empty(max(nbytes // 4, 1), dtype=torch.int32, device=dev)
+        counts = torch.empty((M, 4), dtype=torch.int32, device=dev)
+        d_rec = torch.from_numpy(np.frombuffer(rec, np.uint8).copy()).to(dev)
+        check(l.omgx_surface_count(_ptr(pool), elems, _ptr(d_rec), C.cast(rec, vp), M, level, _ptr(ws), _ptr(counts), _stream()), "omgx_surface_count")
+        h = counts.cpu().numpy().astype(np.int64)
+        if h[:, :2].sum(0).max() > 0x7fffffff:
+            raise _lib.OmgHipError("the meshes have more rows than int32 ranges address")
+        vrows, frows = (np.stack([np.concatenate([[0], np.cumsum(h[:, col])[:-1]]), h[:, col]], -1) for col in (0, 1))
+        for m, r in enumerate(rec):
+            r.vert_begin, r.vert_count, r.face_begin, r.face_count = int(vrows[m, 0]), int(vrows[m, 1]), int(frows[m, 0]), int(frows[m, 1])
+        if out is None:
+            out = (torch.empty((int(h[:, 0].sum()), 3), dtype=torch.float64, device=dev), torch.empty((int(h[:, 1].sum()), 3), dtype=torch.int32, device=dev))
+        verts, faces = out
+        d_rec2 = torch.from_numpy(np.frombuffer(rec, np.uint8).copy()).to(dev)
+        check(l.omgx_surface_gather(_ptr(pool), elems, _ptr(d_rec2), C.cast(rec, vp), M, level, _ptr(ws), _ptr(verts) if verts.shape[0] else None,
+                                    int(verts.shape[0]), _ptr(faces) if faces.shape[0] else None, int(faces.shape[0]), _stream()), "omgx_surface_gather")
+        for t in (ws, d_rec, d_rec2):
+            t.record_stream(torch.cuda.current_stream(dev))
+    return verts, faces, vrows, frows, h[:, 2].copy()
+
+
+def surface_mesh(grid: torch.Tensor, origin, delta, sample: str = "centre", level: float = 0.0):
+    """The level set of ONE volume, a contiguous float32 [X,Y,Z] device tensor whose sample (i,j,k) sits at
+    origin + ((i,j,k) + offset) * delta -> (verts [V,3] float64, faces [F,3] int32 on the device, open_edges).
+    scenes.surface_nets with the same arguments is the specification."""
+    if not isinstance(grid, torch.Tensor) or grid.dim() != 3:
+        raise _lib.OmgHipError("grid must be a tensor [X,Y,Z]")
+    verts, faces, _, _, open_edges = surface_meshes(grid, [(origin, delta, sample, tuple(grid.shape), 0)], level)
+    return verts, faces, int(open_edges[0])
 
 
 class RayBatch:

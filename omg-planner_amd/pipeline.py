@@ -101,3 +101,31 @@ def plan_meshes(model, scenes, meshes, starts, cfg, n_rays: int = 512, n_angles:
     sets = _gr.sample_grasp_sets(meshes, grids, n_rays, n_angles, np.random.RandomState(0) if grasp_rng is None else grasp_rng,
                                  max_grasps=max_grasps, device=device, **grasp_kwargs)
     return plan_grasps(model, scenes, sets, starts, cfg, ol_alg=ol_alg, rng=rng, obj_coord=True, device=device, layout_scenes=layout_scenes), sets
+
+
+def plan_volumes(model, scenes, starts, cfg, level: float = 0.0, n_rays: int = 512, n_angles: int = 8, ol_alg=None, rng=np.random,
+                 grasp_rng=None, max_grasps=None, device="cuda:0", layout_scenes: "int | None" = None, **grasp_kwargs):
+    """plan_meshes without meshes: the targets exist only as distance volumes.  The scene table is built
+    (ops.DeviceScenes.from_scenes), the level set {v = level} of every target's volume is extracted from the table's own pool on
+    the device (DeviceScenes.object_surfaces) and downloaded once, grasps.sample_grasp_sets samples grasps on those meshes with
+    the same pool as the gripper check, then plan_grasps unchanged (it builds its own table).  level: 0 for a signed volume; a
+    small radius for a target that is the unsigned distance to an observed cloud (ops.point_cloud_sdf).  A target whose surface
+    is empty or leaves its grid (open edges: the mesh is not closed there) is refused, by scene.  The other arguments are
+    plan_meshes'.  -> (GraspPlans, grasp poses: S arrays [G_s,4,4] in the targets' frames, meshes: S (verts, faces) on the host)."""
+    from . import grasps as _gr
+    dev = torch.device(device)
+    if any(ob.attached for sc_ in scenes for ob in sc_.objects):
+        raise ValueError("plan_volumes plans grasps only: a scene with an attached object needs per-scene robot points")
+    table = ops.DeviceScenes.from_scenes(scenes, cfg.layer_kwargs(), device=dev)
+    targets = [int(sc_.target_idx) for sc_ in scenes]
+    verts, faces, vrows, frows, open_edges = table.object_surfaces([(s, t) for s, t in enumerate(targets)], level)
+    bad = [f"scene {s}: the target's surface at level {level} " + ("is empty" if frows[s, 1] == 0 else f"leaves its grid ({int(open_edges[s])} open edges)")
+           for s in range(len(scenes)) if frows[s, 1] == 0 or open_edges[s] > 0]
+    if bad:
+        raise ValueError("; ".join(bad))
+    hv, hf = verts.cpu().numpy(), faces.cpu().numpy()
+    meshes = [(hv[vrows[s, 0]: vrows[s, 0] + vrows[s, 1]], hf[frows[s, 0]: frows[s, 0] + frows[s, 1]]) for s in range(len(scenes))]
+    sets = _gr.sample_grasp_sets(meshes, table, n_rays, n_angles, np.random.RandomState(0) if grasp_rng is None else grasp_rng,
+                                 max_grasps=max_grasps, targets=targets, device=dev, **grasp_kwargs)
+    plans = plan_grasps(model, scenes, sets, starts, cfg, ol_alg=ol_alg, rng=rng, obj_coord=True, device=device, layout_scenes=layout_scenes)
+    return plans, sets, meshes

@@ -125,6 +125,18 @@ def load_obj(path: str):
     return np.array(verts, np.float64).reshape(-1, 3), np.array(faces, np.int32).reshape(-1, 3)
 
 
+def save_obj(path: str, verts, faces) -> None:
+    """Write (verts [V,3] float, faces [F,3] int, 0-based) as a Wavefront OBJ file that load_obj reads back to the same float64
+    coordinates (repr round-trips a double) and the same faces: the counterpart of load_obj, e.g. for a surface extracted from a
+    volume (scenes.surface_nets, ops.surface_meshes).  An empty mesh gives a file without lines."""
+    verts, faces = np.asarray(verts, np.float64).reshape(-1, 3), np.asarray(faces).reshape(-1, 3)
+    if len(faces) and (faces.min() < 0 or faces.max() >= len(verts)):
+        raise ValueError(f"face indices must lie in [0, {len(verts)})")
+    with open(path, "w") as fh:
+        fh.writelines(f"v {float(x)!r} {float(y)!r} {float(z)!r}\n" for x, y, z in verts)
+        fh.writelines(f"f {int(a) + 1} {int(b) + 1} {int(c) + 1}\n" for a, b, c in faces)
+
+
 def read_sdf_text(path: str) -> SdfGrid:
     """A text .sdf volume (what SignedDensityField.from_sdf reads, omg/sdf_tools.py:169-185; real_world/convert_sdf.py:17-26):
     three header lines `nx ny nz`, `x0 y0 z0`, `delta`, then one value per line with x running fastest and z slowest ->

@@ -466,6 +466,117 @@ def mesh_sdf(verts, faces, delta: float, padding: int = 4, sample: str = "centre
 
 
 # ------------------------------------------------------------------------------------------------
+# triangle meshes from distance volumes (naive surface nets): the specification of omgx_surface_count / omgx_surface_gather
+# (csrc/omg_surface_body.h follows it operation by operation) and the CPU path.  The reference has no counterpart: its data set keeps
+# a mesh file beside every volume file (omg/core.py:86-127 loads the volume, ycb_render the mesh), and an object it has no mesh of
+# gets its grasps from an outside detector (omg/planner.py:176-186).
+# ------------------------------------------------------------------------------------------------
+def _surface_edges():
+    """The 12 edges of a cell in the order the vertex sums them: axis x, y, z; the offsets (u, w) on the two other axes, taken
+    cyclically (x -> (y, z), y -> (z, x), z -> (x, y)), through 00, 01, 10, 11 -> [(axis, o1, o2, u, w)]."""
+    return [(ax, (ax + 1) % 3, (ax + 2) % 3, u, w) for ax in range(3) for u in (0, 1) for w in (0, 1)]
+
+
+def surface_nets(grid, origin=None, delta=None, sample: str = "centre", level: float = 0.0):
+    """The level set {v = level} of a distance volume as a triangle mesh -> (verts [V,3] float64, faces [F,3] int32, open_edges).
+    grid: an SdfGrid (origin and delta default to its own) or an array [X,Y,Z]; sample (i,j,k) sits at
+    origin + ((i,j,k) + offset) * delta, offset 0.5 for "centre" and 0.0 for "node", as in mesh_sdf.
+
+    * inside(i,j,k) = v[i,j,k] < float32(level), a float32 compare: NaN is outside.
+    * Cell (i,j,k), 0 <= i < X-1 and so on, has the corners (i+dx, j+dy, k+dz); it is active iff they are neither all inside nor
+      all outside.  An active cell has ONE vertex: over its 12 edges in _surface_edges' order, an edge from corner a to
+      b = a + e_axis crosses iff inside(a) != inside(b), at t = (L - va) / (vb - va) with L = float64(float32(level)) and the
+      samples widened to float64 (t outside [0,1], i.e. from samples that are not finite: t = 0.5); the crossing point has t on the
+      axis and the edge's offsets (u, w) on the two others; local = (sum of the crossing points, in that order, component by
+      component, from +0.0) / count, and vertex = origin + (((i,j,k) + offset) + local) * delta.  + - * / only, each rounded once.
+    * Vertices are numbered by their cell's x-major index, ascending.
+    * Every sample edge a -> a + e_axis with inside(a) != inside(b) has four cells around it, with (o1, o2) the cyclic other axes:
+      c0 = a - e_o1 - e_o2, c1 = a - e_o2, c2 = a, c3 = a - e_o1.  If one of them is outside the grid the edge gives nothing and
+      counts as an open edge; otherwise two triangles split along c0-c2, turned so that the normal points from inside to outside:
+      (c0,c1,c2), (c0,c2,c3) if inside(a), else (c0,c2,c1), (c0,c3,c2).  Faces are ordered by 3 * linear(a) + axis, ascending.
+    * A volume with a dim below 2 has no cells: an empty mesh (V = F = 0) whose crossing edges are all open.  All inside or all
+      outside: an empty mesh without open edges.
+
+    The surface is closed iff open_edges == 0.  Plain numpy float64, vectorised over the cells."""
+    if isinstance(grid, SdfGrid):
+        origin = grid.min_coords if origin is None else origin
+        delta = grid.delta if delta is None else delta
+        grid = grid.data
+    if origin is None or delta is None:
+        raise ValueError("an array needs origin and delta")
+    if sample not in MESH_SAMPLE_OFFSET:
+        raise ValueError(f"sample must be 'centre' or 'node', got {sample!r}")
+    delta, off = float(delta), MESH_SAMPLE_OFFSET[sample]
+    if not (delta > 0 and np.isfinite(delta)):
+        raise ValueError("delta must be positive and finite")
+    origin = np.asarray(origin, np.float64).reshape(3)
+    v32 = np.ascontiguousarray(grid, np.float32)
+    if v32.ndim != 3 or min(v32.shape) < 1:
+        raise ValueError(f"a volume is [X,Y,Z] with every dim >= 1, got {v32.shape}")
+    L32 = np.float32(level)
+    if np.isnan(L32):
+        raise ValueError("level is NaN")
+    empty = (np.zeros((0, 3), np.float64), np.zeros((0, 3), np.int32), 0)
+    n = v32.shape
+    inside = v32 < L32
+    v, L = v32.astype(np.float64), float(L32)
+    c = tuple(d - 1 for d in n)  # cells per axis
+
+    def corner(a, d):  # the corner (dx, dy, dz) = d of every cell
+        return a[d[0]: d[0] + c[0], d[1]: d[1] + c[1], d[2]: d[2] + c[2]]
+    n_in = sum(corner(inside, (dx, dy, dz)).astype(np.int32) for dx in (0, 1) for dy in (0, 1) for dz in (0, 1))
+    active = (n_in > 0) & (n_in < 8)
+    sums, count = [np.zeros(c), np.zeros(c), np.zeros(c)], np.zeros(c)
+    with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
+        for ax, o1, o2, u, w in _surface_edges():
+            da, db = [0, 0, 0], [0, 0, 0]
+            da[o1] = db[o1] = u
+            da[o2] = db[o2] = w
+            db[ax] = 1
+            cross = corner(inside, da) != corner(inside, db)
+            va, vb = corner(v, da), corner(v, db)
+            t = (L - va) / (vb - va)
+            t = np.where((t >= 0.0) & (t <= 1.0), t, 0.5)
+            p = [None, None, None]
+            p[ax], p[o1], p[o2] = t, float(u), float(w)
+            for k in range(3):
+                sums[k] = sums[k] + np.where(cross, p[k], 0.0)
+            count = count + np.where(cross, 1.0, 0.0)
+        ijk = np.nonzero(active)  # x-major, ascending
+        verts = np.stack([origin[k] + ((ijk[k].astype(np.float64) + off) + sums[k][ijk] / count[ijk]) * delta for k in range(3)], -1)
+    index = np.full(c, -1, np.int64)
+    index[ijk] = np.arange(len(ijk[0]))
+    keys, tris, open_edges = [], [], 0
+    lin = np.arange(int(np.prod(n)), dtype=np.int64).reshape(n)
+    for ax in range(3):
+        o1, o2 = (ax + 1) % 3, (ax + 2) % 3
+        sl_a, sl_b = [slice(None)] * 3, [slice(None)] * 3
+        sl_a[ax], sl_b[ax] = slice(0, n[ax] - 1), slice(1, n[ax])
+        ia = inside[tuple(sl_a)]
+        a = np.stack(np.nonzero(ia != inside[tuple(sl_b)]), -1)  # the samples a of the crossing edges of this axis
+        if not len(a):
+            continue
+        closed = (a[:, o1] >= 1) & (a[:, o1] <= n[o1] - 2) & (a[:, o2] >= 1) & (a[:, o2] <= n[o2] - 2)
+        open_edges += int((~closed).sum())
+        a = a[closed]
+        e1, e2 = np.zeros(3, np.int64), np.zeros(3, np.int64)
+        e1[o1], e2[o2] = 1, 1
+        cell = lambda q: index[q[:, 0], q[:, 1], q[:, 2]]
+        c0, c1, c2, c3 = cell(a - e1 - e2), cell(a - e2), cell(a), cell(a - e1)
+        a_in = inside[a[:, 0], a[:, 1], a[:, 2]]
+        first = np.where(a_in[:, None], np.stack([c0, c1, c2], -1), np.stack([c0, c2, c1], -1))
+        second = np.where(a_in[:, None], np.stack([c0, c2, c3], -1), np.stack([c0, c3, c2], -1))
+        keys.append(3 * lin[a[:, 0], a[:, 1], a[:, 2]] + ax)
+        tris.append(np.stack([first, second], 1))
+    if not keys:
+        return (verts, empty[1], open_edges) if len(verts) else (empty[0], empty[1], open_edges)
+    order = np.argsort(np.concatenate(keys), kind="stable")
+    faces = np.concatenate(tris)[order].reshape(-1, 3)
+    assert faces.min(initial=0) >= 0  # the four cells of a crossing edge each have a crossing edge: they are active
+    return verts, np.ascontiguousarray(faces, np.int32), open_edges
+
+
+# ------------------------------------------------------------------------------------------------
 # per-object SDF-layer parameters (Cost.compute_obstacle_cost_layer, omg/cost.py:303-328)
 # ------------------------------------------------------------------------------------------------
 def layer_params(scene: Scene, epsilon=0.2, target_epsilon=0.1, clearance=0.01, target_clearance=0.0,
