@@ -182,6 +182,41 @@ __device__ __forceinline__ void gq_st_out(float* p, float v) {
     else *p = v;
 }
 
+// A wave-uniform value as a scalar register of its OWN (an empty move the compiler cannot see through).  The kernel's arguments arrive
+// as 4- and 8-dword tuples of neighbouring fields, and the register allocator keeps a tuple whole: one that stays live for ONE field
+// is spilled to VGPR lanes and restored whole — a lane move per dword wherever the field is read.  A copy
+// costs one scalar move and ends the tuple's life.
+__device__ __forceinline__ int gq_own(int v) { int r; asm volatile("s_mov_b32 %0, %1" : "=s"(r) : "s"(v)); return r; }
+__device__ __forceinline__ float gq_own(float v) { float r; asm volatile("s_mov_b32 %0, %1" : "=s"(r) : "s"(v)); return r; }
+// (a pointer argument of the kernel: global memory, said out loud — behind the move the compiler no longer knows and would fall back to flat loads)
+template <class T> __device__ __forceinline__ T* gq_own(T* v) {
+    T* r;
+    asm volatile("s_mov_b64 %0, %1" : "=s"(r) : "s"(v));
+    return (T*)(OMG_GLOBAL_AS T*)(uintptr_t)r;
+}
+
+// The trajectory-layer piece `layer_part` of scene s.  Everything it needs it reads from the arguments ITSELF: nothing computed for it is
+// alive in the goal item's prologue (the two items share one function; what both read the compiler computes ahead of the branch and
+// keeps — in spill lanes — for whichever runs).
+template <bool LAT, bool PERSIST, int W>
+__device__ __forceinline__ void gq_layer_item(const ChunkArgs& a, double* const lds_pose, const int s, const int layer_part) {
+    const int o_begin = as_const(a.scene_begin)[s], o_end = as_const(a.scene_begin)[s + 1];
+    const int P = a.P;
+    // LAT: the scene's object records and the links' radii into the scalar cache, asynchronously (consumed after the (sin, cos) stage)
+    const bool warming = LAT && o_end > o_begin;
+    const RobotViewS rv(a.robot, P);
+    const GqLayout L(a.PS, a.MR, P, a.tbl_n, LAT, W);
+    char* const lds_bytes = reinterpret_cast<char*>(lds_pose);
+    uint32_t* const rowmask = reinterpret_cast<uint32_t*>(lds_bytes + L.mask_off);
+    const int lgi = a.layer_nb > 1 ? layer_part / a.layer_nb : layer_part, cbi = layer_part - lgi * a.layer_nb;
+    const int lpg = 10 / a.layer_lg, c_begin = cbi * a.layer_cb;
+    const int c_end = c_begin + a.layer_cb < a.wp_n ? c_begin + a.layer_cb : a.wp_n;
+    waypoint_layer_block<LAT, PERSIST>(a, s, lgi * lpg, (lgi + 1) * lpg, c_begin, c_end, lds_pose, rowmask, o_begin, o_end, rv,
+                              reinterpret_cast<double*>(lds_bytes + L.fkc_off), warming,
+                              reinterpret_cast<float*>(lds_bytes + L.objc_off), reinterpret_cast<double*>(lds_bytes + L.btab_off));
+    GS_WG_STAMP(4);
+}
+
 // One work item of k_goalset_queue — a goal (or one part of it) or one piece of a scene's trajectory layer — by a whole workgroup.
 // ROLE (omg_persist.h compiles the two kinds of item as functions of their own): 0 = either, 1 = a trajectory-layer piece, 2 = a goal.
 // W (round 6): waves per workgroup.  4 everywhere but in the WIDE instantiations of the batch kernel (whole goals, own kinematics: eight
@@ -189,47 +224,45 @@ __device__ __forceinline__ void gq_st_out(float* p, float v) {
 // by however many waves there are.  Same masks, same tiles, same exact sum: same bits.
 template <int LB, bool STAMP, bool LAT, bool SPLIT, bool PRE, bool PERSIST = false, int ROLE = 0, int W = GQ_WAVES>
 __device__ __forceinline__ void gq_item(const ChunkArgs& a, double* const lds_pose, const int s, const bool is_layer, const int layer_part, const int chunk, const int NP) {
-    const int o_begin = as_const(a.scene_begin)[s], o_end = as_const(a.scene_begin)[s + 1];
-    const int P = a.P;
-    // LAT: the scene's object records and the links' radii into the scalar cache, asynchronously (consumed after the (sin, cos) stage)
-    const bool warming = LAT && o_end > o_begin;
+    static_assert(W == GQ_WAVES || (!LAT && !SPLIT && !PRE && !PERSIST && W == 8), "wide workgroups: the batch kernel with whole goals and its own kinematics");
+    if (ROLE == 1 || (ROLE == 0 && is_layer)) {
+        gq_layer_item<LAT, PERSIST, W>(a, lds_pose, s, layer_part);
+        return;
+    }
     // A goal's TILES may be dealt over a.NP workgroups (latency mode): chunk = goal * NP + part, part takes the tiles t with
     // t % NP == part — (waypoint block + link pair) % NP for NP = 2, 4: the heavy tiles (last waypoints, hand links) are spread
     // evenly — and runs the kinematics of all configurations itself (the chain's latency does not depend on their number).
     const int goal = NP > 1 ? chunk / NP : chunk;
     const int part = NP > 1 ? chunk - goal * NP : 0;
-    const int CH = a.CH;
+    const int tid = (int)threadIdx.x;
+    if (a.goal_count && goal >= as_const(a.goal_count)[s]) {  // padding of a ragged goal set
+        if (STAMP && tid == 0) a.work[(int64_t)s * a.NCH + chunk] = 0u;
+        return;
+    }
+    // The goal item's wave-uniform inputs as registers of their own (gq_own), taken HERE: the prologue's stages read single fields of
+    // the argument tuples, and each read of a tuple that had been spilled brought the whole tuple back — 127 restores on the chain
+    // wave's way to the main loop (profiles/r07a_prologue_path.md).
+    // (latency mode keeps its pointer arguments as they come: two workgroups per CU at the most, registers are free)
+    auto own = [](auto v) { if constexpr (LAT && std::is_pointer<decltype(v)>::value) return v; else return gq_own(v); };
+    const int CH = own(a.CH), P = own(a.P), pstride = own(a.PS), MR = own(a.MR), tbl_n = own(a.tbl_n);
+    const omgx_object* const objects = own(a.objects);
+    const int o_begin = as_const(a.scene_begin)[s], o_end = as_const(a.scene_begin)[s + 1];
+    // LAT: the scene's object records and the links' radii into the scalar cache, asynchronously (consumed after the (sin, cos) stage)
+    const bool warming = LAT && o_end > o_begin;
     // The blocks of 4 waypoints are aligned with the END of the window: when CH is no multiple of 4 the short block is the first one
     // (far from the goal, mostly culled as a whole) instead of the last one — the heaviest tiles, which then ran at half their lanes.
     const int blk_shift = (4 - (CH & 3)) & 3;
     const int p = threadIdx.x & 15, lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));  // provably wave-uniform: tile indices and their address arithmetic stay on the scalar unit
-    const int tid = (int)threadIdx.x;
-    const RobotViewS rv(a.robot, P);
-    const int pstride = a.PS, MR = a.MR;
-    static_assert(W == GQ_WAVES || (!LAT && !SPLIT && !PRE && !PERSIST && W == 8), "wide workgroups: the batch kernel with whole goals and its own kinematics");
+    const RobotViewS rv(own(a.robot), P);
     constexpr int NT = 64 * W;  // threads of the workgroup
-    const GqLayout L(pstride, MR, P, a.tbl_n, LAT, W);
+    const GqLayout L(pstride, MR, P, tbl_n, LAT, W);
     char* const lds_bytes = reinterpret_cast<char*>(lds_pose);
     uint32_t* const rowmask = reinterpret_cast<uint32_t*>(lds_bytes + L.mask_off);
     uint32_t* const tilebits = reinterpret_cast<uint32_t*>(lds_bytes + L.tile_off);  // goal workgroups: which tiles have anything in reach
-    if (ROLE == 1 || (ROLE == 0 && is_layer)) {
-        const int lgi = a.layer_nb > 1 ? layer_part / a.layer_nb : layer_part, cbi = layer_part - lgi * a.layer_nb;
-        const int lpg = 10 / a.layer_lg, c_begin = cbi * a.layer_cb;
-        const int c_end = c_begin + a.layer_cb < a.wp_n ? c_begin + a.layer_cb : a.wp_n;
-        waypoint_layer_block<LAT, PERSIST>(a, s, lgi * lpg, (lgi + 1) * lpg, c_begin, c_end, lds_pose, rowmask, o_begin, o_end, rv,
-                                  reinterpret_cast<double*>(lds_bytes + L.fkc_off), warming,
-                                  reinterpret_cast<float*>(lds_bytes + L.objc_off), reinterpret_cast<double*>(lds_bytes + L.btab_off));
-        GS_WG_STAMP(4);
-        return;
-    }
-    if (a.goal_count && goal >= as_const(a.goal_count)[s]) {  // padding of a ragged goal set
-        if (STAMP && tid == 0) a.work[(int64_t)s * a.NCH + chunk] = 0u;
-        return;
-    }
     const unsigned long long work_t0 = STAMP ? wall_clock64() : 0ull;
     GS_FREQ_BEGIN();
-    uint32_t* const tbl = reinterpret_cast<uint32_t*>(lds_bytes + L.tbl_off);      // [a.tbl_n][16]
+    uint32_t* const tbl = reinterpret_cast<uint32_t*>(lds_bytes + L.tbl_off);      // [tbl_n][16]
     double* const pts = reinterpret_cast<double*>(lds_bytes + L.pts_off);          // [10][P][3]
     float* const stage = reinterpret_cast<float*>(lds_bytes + L.stage_off) + wave * 256;  // wave-private [64][4]
 
@@ -243,7 +276,7 @@ __device__ __forceinline__ void gq_item(const ChunkArgs& a, double* const lds_po
         const float rad = (float)bl[3] + 1.0e-4f;
         uint32_t m = 0;
         for (int o = o_begin; o < o_end; ++o) {
-            ObjTablePtr ob = as_const(a.objects) + o;
+            ObjTablePtr ob = as_const(objects) + o;
             // the record in ONE trip through the scalar cache (gq_load_far: written field by field the compiler waits for `disabled`,
             // then for epsilon / clearance, then for the rest — two to three dependent trips per object and pass on the prologue's tail)
             const GqFar f = gq_load_far(ob);
@@ -313,10 +346,10 @@ __device__ __forceinline__ void gq_item(const ChunkArgs& a, double* const lds_po
         const double* pw = a.pre_poses + gi * gk_pose_doubles(CH);
         const uint32_t* mw = a.pre_masks + gi * (int64_t)(10 * CH);
         const double pv0 = tid < 30 * P ? rv.g[246 + tid] : 0.0, pv1 = tid + GQ_NT < 30 * P ? rv.g[246 + tid + GQ_NT] : 0.0;
-        const bool tbl_lane = tid >= 128 && tid - 128 < a.tbl_n && o_begin + tid - 128 < o_end;
+        const bool tbl_lane = tid >= 128 && tid - 128 < tbl_n && o_begin + tid - 128 < o_end;
         GqTblRec trec{};
-        if (tbl_lane) trec = gq_tbl_load(a.objects + o_begin + (tid - 128));
-        if (warming) gq_warm_scalar_cache(a.objects, o_begin, o_end, a.robot + OMGX_ROBOT_POINTS + 30 * P + 316 + 30 * P);
+        if (tbl_lane) trec = gq_tbl_load(objects + o_begin + (tid - 128));
+        if (warming) gq_warm_scalar_cache(objects, o_begin, o_end, rv.raw + OMGX_ROBOT_POINTS + 30 * P + 316 + 30 * P);
         const int nm = 10 * CH, ne = 90 * ncfg;
         uint32_t mv[3];
 #pragma unroll
@@ -351,6 +384,7 @@ __device__ __forceinline__ void gq_item(const ChunkArgs& a, double* const lds_po
         const double* q0 = a.traj_start + a.ts_stride * (int64_t)s;
         const double* qg = a.goals + ((int64_t)s * a.NG + goal) * 9;
         const int ncfg = CH + 1;
+        const double inv_ncfg = a.inv_ncfg;
         double* sc = reinterpret_cast<double*>(lds_bytes + L.stage_off);  // [ncfg][7][2]: the queues' region, first used in the main loop
         int* const progress = reinterpret_cast<int*>(lds_bytes + L.stage_off + pstride * 14 * 8);  // [4] links a chain wave has published
         if (tid < 4) progress[tid] = (tid < chain_waves || (cull_beside_chain && tid == 3)) ? 0 : 99;  // [3]: the culling's pair counter when two waves are free
@@ -358,13 +392,13 @@ __device__ __forceinline__ void gq_item(const ChunkArgs& a, double* const lds_po
         const double pv0 = tid < 30 * P ? rv.g[246 + tid] : 0.0, pv1 = (tid < 256 && tid + 256 < 30 * P) ? rv.g[246 + tid + 256] : 0.0;  // (30 P <= 480)
         double* const fkc = reinterpret_cast<double*>(lds_bytes + L.fkc_off);  // LAT: the chain's constants, one coalesced load
         const double fkv = (LAT && tid < 246) ? rv.g[tid] : 0.0;
-        const bool tbl_lane = tid >= 128 && tid - 128 < a.tbl_n && o_begin + tid - 128 < o_end;  // lanes of wave 2: idle during the chain stage
+        const bool tbl_lane = tid >= 128 && tid - 128 < tbl_n && o_begin + tid - 128 < o_end;  // lanes of wave 2: idle during the chain stage
         GqTblRec trec{};
-        if (LAT && tbl_lane) trec = gq_tbl_load(a.objects + o_begin + (tid - 128));  // LAT: requested here, stored after the barrier
-        if (warming) gq_warm_scalar_cache(a.objects, o_begin, o_end, a.robot + OMGX_ROBOT_POINTS + 30 * P + 316 + 30 * P);
+        if (LAT && tbl_lane) trec = gq_tbl_load(objects + o_begin + (tid - 128));  // LAT: requested here, stored after the barrier
+        if (warming) gq_warm_scalar_cache(objects, o_begin, o_end, rv.raw + OMGX_ROBOT_POINTS + 30 * P + 316 + 30 * P);
         auto joint = [&](int cfg, int d) {
             const double q0d = gq_ld_traj<PERSIST>(q0 + d);
-            return cfg == 0 ? q0d : q0d + ((double)cfg * (1.0 / (double)(CH + 1))) * (qg[d] - q0d);
+            return cfg == 0 ? q0d : q0d + ((double)cfg * inv_ncfg) * (qg[d] - q0d);  // inv_ncfg = 1.0 / (double)(CH + 1), divided on the host
         };
         for (int t = tid; t < ncfg * 7; t += NT) {
             const int cfg = t / 7, i = t - cfg * 7;
@@ -385,9 +419,9 @@ __device__ __forceinline__ void gq_item(const ChunkArgs& a, double* const lds_po
         GS_WG_STAMP(1);
         if (tid < 30 * P) pts[tid] = pv0;
         if (tid < 256 && tid + 256 < 30 * P) pts[tid + 256] = pv1;
-        // ---- exact-path records of the scene's first a.tbl_n objects -> LDS, by lanes of wave 2 (idle during the chain stage)
+        // ---- exact-path records of the scene's first tbl_n objects -> LDS, by lanes of wave 2 (idle during the chain stage)
         if (tbl_lane) {
-            if (!LAT) trec = gq_tbl_load(a.objects + o_begin + (tid - 128));
+            if (!LAT) trec = gq_tbl_load(objects + o_begin + (tid - 128));
             gq_tbl_store(tbl + (tid - 128) * 16, trec);
         }
         auto run_chain = [&](const auto& view) {
@@ -406,7 +440,7 @@ __device__ __forceinline__ void gq_item(const ChunkArgs& a, double* const lds_po
         if constexpr (LAT) {
             // the joints' matrices first, one lane per (configuration, joint) like the (sin, cos) stage (whose table they read), then
             // the chain over the tabulated matrices: its 7 dependent steps shrink from 30 + 30 to 12 + 12 reads / multiply-adds each
-            const RobotView rvl(a.robot, P, fkc);
+            const RobotView rvl(rv.raw, P, fkc);
             double* const btab = reinterpret_cast<double*>(lds_bytes + L.btab_off);
             for (int t = tid; t < ncfg * 7; t += 256) fk_joint_matrix(rvl, t - (t / 7) * 7, sc[2 * t], sc[2 * t + 1], btab + 9 * t);
             __syncthreads();
@@ -515,7 +549,7 @@ __device__ __forceinline__ void gq_item(const ChunkArgs& a, double* const lds_po
     asm volatile("s_mov_b32 %0, %10\n\ts_mov_b32 %1, %11\n\ts_mov_b32 %2, %12\n\ts_mov_b32 %3, %13\n\ts_mov_b32 %4, %14\n\ts_mov_b32 %5, %15\n\t"
                  "s_mov_b32 %6, %16\n\ts_mov_b32 %7, %17\n\ts_mov_b64 %8, %18\n\ts_mov_b64 %9, %19"
                  : "=&s"(h_CH), "=&s"(h_P), "=&s"(h_ps), "=&s"(h_ob), "=&s"(h_oe), "=&s"(h_tbl), "=&s"(h_soft), "=&s"(h_idt), "=&s"(h_objects), "=&s"(h_pool)
-                 : "s"(CH), "s"(P), "s"(pstride), "s"(o_begin), "s"(o_end), "s"(a.tbl_n), "s"(a.soften), "s"(a.inv_dt), "s"(a.objects), "s"(a.pool));
+                 : "s"(CH), "s"(P), "s"(pstride), "s"(o_begin), "s"(o_end), "s"(tbl_n), "s"(a.soften), "s"(a.inv_dt), "s"(objects), "s"(a.pool));
     // ---- the wave's queue.  Pending entries (object-space offset, weight) sit in the wave's LDS ring `stage`, slot i = entry i,
     // their object index | soft << 16 in q_meta of lane i; lanes / slots [0, pending).  f_*: the batch whose gathers are in flight.
     uint32_t q_meta = 0u;
@@ -723,7 +757,11 @@ __device__ __forceinline__ void gq_item(const ChunkArgs& a, double* const lds_po
             if (q >= n_list) return -1;
             // (a draw requested one tile ahead, to hide the atomic's trip behind the previous tile, was measured: every wave then holds
             // two of the dozen tiles from the start and the balance is the static deal's again — first / last wave out 10.8 / 15.1 us)
-            if (ncand > LIST_MAX) return cand(q);
+            // (the count behind an empty asm: compared here, per draw — hoisted, the comparison's lane mask is a register pair that lives
+            // through the main loop in spill lanes and comes back with two lane moves per draw)
+            int nc = ncand;
+            asm volatile("" : "+s"(nc));
+            if (nc > LIST_MAX) return cand(q);
             if constexpr (TILEBITS) { if (q >= 64) return __builtin_amdgcn_readlane(my_tile2, q - 64); }
             return __builtin_amdgcn_readlane(my_tile, q);
         } else return lat_tile(q_static++);

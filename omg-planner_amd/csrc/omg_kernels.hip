@@ -212,6 +212,10 @@ struct ChunkArgs {
     // [S * NG][10][9][CH + 1] and row masks [S * NG][10][CH] in the caller's workspace, or null: every goal workgroup runs its own
     double* pre_poses;
     uint32_t* pre_masks;
+    // 1.0 / (double)(CH + 1), the interpolation step of a goal's configurations (k_goalset_queue; set where CH is): the same for every
+    // goal of a launch, and as a division in the kernel it was 14 float64 instructions at each of the three places the chain wave
+    // interpolates a joint
+    double inv_ncfg;
 };
 
 // Thread layout: 256 threads = 16 rows x 16 lanes.  Lane = collision point p of a link (P <= 16), row =
@@ -905,6 +909,7 @@ static int launch_goalset(ChunkArgs& ca, int timing_kind, hipStream_t st, const 
     ca.layer_nb = layer ? (ca.wp_n + ca.layer_cb - 1) / ca.layer_cb : 1;
     ca.layer_parts = ca.layer_lg * ca.layer_nb;
     ca.PS = ca.CH + 1; ca.MR = ca.CH; ca.LPW = 10;
+    ca.inv_ncfg = 1.0 / (double)(ca.CH + 1);
     if (layer) { if (ca.layer_cb > ca.PS) ca.PS = ca.layer_cb; if (ca.layer_cb > ca.MR) ca.MR = ca.layer_cb; }
     const int64_t per_scene = (int64_t)ca.NCH + (layer ? ca.layer_parts : 0);
     const int64_t grid = ca.spread ? (int64_t)ca.S * per_scene

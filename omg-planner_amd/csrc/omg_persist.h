@@ -139,7 +139,7 @@ __device__ __forceinline__ void persist_item_impl(const unsigned long long pa_ad
     const int n = ca.wp_n;
     // (readfirstlane: provably wave-uniform for the scalar copies the item's main loop makes of them)
     const int CH = __builtin_amdgcn_readfirstlane(n - start_idx);
-    ca.CH = CH; ca.C = G * CH;
+    ca.CH = CH; ca.C = G * CH; ca.inv_ncfg = 1.0 / (double)(CH + 1);
     ca.PS = __builtin_amdgcn_readfirstlane(CH + 1 > n ? CH + 1 : n); ca.MR = __builtin_amdgcn_readfirstlane(CH > n ? CH : n);
     {   // exact-path records staged: whatever fits the launch's LDS beside this window's poses (any number gives the same bits)
         const int base = GqLayout(ca.PS, ca.MR, ca.P, 0).total;
