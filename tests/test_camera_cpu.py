@@ -5,18 +5,13 @@ of the wrappers, and the kernels' register budget."""
 from __future__ import annotations
 
 import ctypes as C
-import re
-import subprocess
-from pathlib import Path
 
 import numpy as np
 import pytest
 
 from tests import camera_cases as CC
+from tests import kernel_build as KB
 from tests import mesh_cases as MC
-
-ROOT = Path(__file__).resolve().parents[1]
-HIPCC = "/opt/rocm/bin/hipcc"
 
 
 @pytest.fixture(scope="module")
@@ -289,25 +284,13 @@ extern "C" int host_cloud(const rec* inst, int n_inst, const double* camera, int
 """
 
 
-def _host_compiler():
-    import shutil
-    for cxx in ("/opt/rocm/llvm/bin/clang++", shutil.which("clang++"), shutil.which("c++"), shutil.which("g++")):
-        if cxx and Path(cxx).exists():
-            return cxx
-    return None
-
-
-@pytest.mark.skipif(_host_compiler() is None, reason="no C++ compiler")
+@KB.requires_host_cxx
 def test_kernel_bodies_compiled_for_the_host_equal_the_specification(cam, tmp_path):
     """csrc/omg_camera_body.h is what the kernels do per pixel and per (pixel, instance) pair; compiled for the host without
     contraction, and with the per-mesh loop seeded by the running best as in k_render_depth, it gives the specification's t as
     int64 bits, its instance and its face on every pixel of the known-answer scenes, two device scenes and three random ones,
     with and without the cull, and the world-frame clouds as bits."""
-    (tmp_path / "h.cpp").write_text(_HOST_HARNESS)
-    so = tmp_path / "h.so"
-    subprocess.run([_host_compiler(), "-O2", "-ffp-contract=off", "-shared", "-fPIC", "-Wno-unknown-pragmas", f"-I{ROOT / 'omg-planner_amd' / 'csrc'}",
-                    str(tmp_path / "h.cpp"), "-o", str(so)], check=True)
-    lib = C.CDLL(str(so))
+    lib = KB.host_harness(_HOST_HARNESS, tmp_path)
     vp, dbl, i = C.c_void_p, C.c_double, C.c_int
     lib.host_render.argtypes = [vp] * 6 + [i, vp, i, i, i, dbl, dbl, vp, vp, vp]
     lib.host_cloud.argtypes = [vp, i, vp, i, i, vp, vp, i, vp]
@@ -539,21 +522,12 @@ def test_wrapper_checks_without_gpu(cam):
 # ---------------------------------------------------------------------------------------------------------------------
 # registers
 # ---------------------------------------------------------------------------------------------------------------------
-@pytest.mark.skipif(not Path(HIPCC).exists(), reason="hipcc not installed")
+@KB.requires_hipcc
 def test_camera_kernels_do_not_spill(tmp_path):
     """The compiler's resource remarks for csrc/omg_camera.hip: no kernel uses scratch, and k_render_depth keeps a pixel's state
     and a face's nine coordinates in few enough registers for at least four waves per SIMD."""
-    flags = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", f"-I{ROOT / 'include'}",
-             f"-I{ROOT / 'omg-planner_amd' / 'csrc'}", "--cuda-device-only", "-c", "-Rpass-analysis=kernel-resource-usage"]
-    r = subprocess.run([HIPCC, *flags, str(ROOT / "omg-planner_amd" / "csrc" / "omg_camera.hip"), "-o", str(tmp_path / "c.o")], check=True,
-                       stdout=subprocess.DEVNULL, stderr=subprocess.PIPE, text=True)
-    blocks = re.split(r"remark: Function Name: ", r.stderr)[1:]
-    seen = {}
-    for b in blocks:
-        name = re.match(r"\S+", b).group(0)
-        seen[name] = {k: int(re.search(rf"remark:\s+{re.escape(k)}: (\d+)", b).group(1))
-                      for k in ("VGPRs", "ScratchSize [bytes/lane]", "Occupancy [waves/SIMD]", "VGPRs Spill", "SGPRs Spill")}
-    kernels = {k: next(v for n, v in seen.items() if k in n) for k in ("k_render_depth", "k_pixel_count", "k_pixel_scan", "k_pixel_gather")}
+    seen = KB.kernel_resources("omg_camera.hip", tmp_path)
+    kernels = {k: KB.one(seen, k) for k in ("k_render_depth", "k_pixel_count", "k_pixel_scan", "k_pixel_gather")}
     for k, v in kernels.items():
         assert v["ScratchSize [bytes/lane]"] == 0 and v["VGPRs Spill"] == 0 and v["SGPRs Spill"] == 0, (k, v)
     assert kernels["k_render_depth"]["Occupancy [waves/SIMD]"] >= 4 and kernels["k_render_depth"]["VGPRs"] <= 128, kernels

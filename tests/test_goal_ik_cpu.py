@@ -4,9 +4,6 @@ prepared targets, omgx_goal_ik's argument checks, and the IK kernel's register b
 from __future__ import annotations
 
 import ctypes as C
-import re
-import shutil
-import subprocess
 from pathlib import Path
 
 import numpy as np
@@ -15,11 +12,11 @@ import pytest
 import ik_restatement as ikr
 from omg_planner_amd import robot as rb
 from omg_planner_amd import scenes as sc
+from tests import kernel_build as KB
 
 ROOT = Path(__file__).resolve().parents[1]
 GOLDEN = ROOT / "tests" / "golden"
 FIXTURES = sorted(GOLDEN.glob("ik_*.npz"))
-HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
 
 
 def load(path):
@@ -224,21 +221,13 @@ def test_goal_ik_argument_checks_without_gpu():
     assert call(S=2, N=0, begin=(0, 0, 0)) == _lib.OMGX_OK  # nothing to solve: nothing launched
 
 
-@pytest.mark.skipif(not Path(HIPCC).exists(), reason="hipcc not installed")
+@KB.requires_hipcc
 def test_ik_kernel_does_not_spill(tmp_path):
     """k_goal_ik keeps a chain's whole state (the Jacobian's rows, the rotated residual, q, the target) in registers: the
     compiled kernel has no scratch (256 VGPRs + AGPRs, one wave per SIMD)."""
-    out = tmp_path / "omg_ik.s"
-    flags = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", f"-I{ROOT / 'include'}",
-             f"-I{ROOT / 'omg-planner_amd' / 'csrc'}", "--cuda-device-only", "-S"]
-    subprocess.run([HIPCC, *flags, str(ROOT / "omg-planner_amd" / "csrc" / "omg_ik.hip"), "-o", str(out)], check=True,
-                   stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
-    text = out.read_text()
-    name = re.search(r"^(\S*k_goal_ik\S*):", text, re.M).group(1)
-    start = text.index(name + ":")
-    block = text[start: text.index("; Occupancy:", start) + 40]
-    assert int(re.search(r"; ScratchSize: (\d+)", block).group(1)) == 0
-    assert int(re.search(r"; Occupancy: (\d+)", block).group(1)) >= 1
+    v = KB.one(KB.kernel_resources("omg_ik.hip", tmp_path), "k_goal_ik")
+    assert v["ScratchSize [bytes/lane]"] == 0
+    assert v["Occupancy [waves/SIMD]"] >= 1
 
 
 # ---- the directed cases of tests/ik_cases.py: each is what it claims, away from every threshold, and stable --------------------

@@ -5,20 +5,17 @@ of the reference's planners, ops.select_goals' argument checks and the selection
 from __future__ import annotations
 
 import ctypes as C
-import re
-import shutil
-import subprocess
 from pathlib import Path
 
 import numpy as np
 import pytest
 
 from omg_planner_amd import goalset
+from tests import kernel_build as KB
 
 ROOT = Path(__file__).resolve().parents[1]
 GOLDEN = ROOT / "tests" / "golden"
 FIXTURES = sorted(GOLDEN.glob("setup_*.npz"))
-HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
 
 
 def dist2(a, b):
@@ -229,17 +226,9 @@ def test_select_goals_abi_checks_without_gpu():
     assert lib.omgx_select_goals_workspace_bytes(0, 855) == 0 and lib.omgx_select_goals_workspace_bytes(3, 0) == 0
 
 
-@pytest.mark.skipif(not Path(HIPCC).exists(), reason="hipcc not installed")
+@KB.requires_hipcc
 def test_select_kernel_does_not_spill(tmp_path):
     """k_select_goals keeps a candidate's nine doubles and the block masks in registers: no scratch."""
-    out = tmp_path / "omg_goal_select.s"
-    flags = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", f"-I{ROOT / 'include'}",
-             f"-I{ROOT / 'omg-planner_amd' / 'csrc'}", "--cuda-device-only", "-S"]
-    subprocess.run([HIPCC, *flags, str(ROOT / "omg-planner_amd" / "csrc" / "omg_goal_select.hip"), "-o", str(out)], check=True,
-                   stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
-    text = out.read_text()
-    name = re.search(r"^(\S*k_select_goals\S*):", text, re.M).group(1)
-    start = text.index(name + ":")
-    block = text[start: text.index("; Occupancy:", start) + 40]
-    assert int(re.search(r"; ScratchSize: (\d+)", block).group(1)) == 0
-    assert int(re.search(r"; Occupancy: (\d+)", block).group(1)) >= 1
+    v = KB.one(KB.kernel_resources("omg_goal_select.hip", tmp_path), "k_select_goals")
+    assert v["ScratchSize [bytes/lane]"] == 0
+    assert v["Occupancy [waves/SIMD]"] >= 1

@@ -4,18 +4,14 @@ the host against the specification bit for bit, every argument error of the C AB
 from __future__ import annotations
 
 import ctypes as C
-import re
-import subprocess
-from pathlib import Path
 
 import numpy as np
 import pytest
 
 from tests import grasp_cases as GC
+from tests import kernel_build as KB
 from tests import mesh_cases as MC
 
-ROOT = Path(__file__).resolve().parents[1]
-HIPCC = "/opt/rocm/bin/hipcc"
 CONE = np.deg2rad(15.0)
 
 
@@ -275,24 +271,12 @@ extern "C" void host_poses(const double* p1, const double* n1, const double* d, 
 """
 
 
-def _host_compiler():
-    import shutil
-    for cxx in ("/opt/rocm/llvm/bin/clang++", shutil.which("clang++"), shutil.which("c++"), shutil.which("g++")):
-        if cxx and Path(cxx).exists():
-            return cxx
-    return None
-
-
-@pytest.mark.skipif(_host_compiler() is None, reason="no C++ compiler")
+@KB.requires_host_cxx
 def test_kernel_bodies_compiled_for_the_host_equal_the_specification(G, tmp_path):
     """csrc/omg_grasp_body.h is what the kernels do per (ray, face) pair, per (ray, angle) pair and per probe point; compiled for
     the host without contraction it gives the specification's t as uint64 bits and its face on 2 000 (ray, face set) cases, and
     the poses as bits with the same flags."""
-    (tmp_path / "h.cpp").write_text(_HOST_HARNESS)
-    so = tmp_path / "h.so"
-    subprocess.run([_host_compiler(), "-O2", "-ffp-contract=off", "-shared", "-fPIC", "-Wno-unknown-pragmas", f"-I{ROOT / 'omg-planner_amd' / 'csrc'}",
-                    str(tmp_path / "h.cpp"), "-o", str(so)], check=True)
-    lib = C.CDLL(str(so))
+    lib = KB.host_harness(_HOST_HARNESS, tmp_path)
     vp, dbl = C.c_void_p, C.c_double
     lib.host_raycast.argtypes = [vp, vp, C.c_int, vp, vp, C.c_int, dbl, dbl, vp, vp]
     lib.host_poses.argtypes = [vp, vp, vp, vp, vp, C.c_int, vp, vp, C.c_int, vp, C.c_int, vp, dbl, dbl, vp, vp, dbl, dbl, dbl, dbl, dbl, vp, vp]
@@ -503,22 +487,13 @@ def test_wrapper_checks_without_gpu(G):
 # ---------------------------------------------------------------------------------------------------------------------
 # 8: registers
 # ---------------------------------------------------------------------------------------------------------------------
-@pytest.mark.skipif(not Path(HIPCC).exists(), reason="hipcc not installed")
+@KB.requires_hipcc
 def test_grasp_kernels_do_not_spill(tmp_path):
     """The compiler's resource remarks for csrc/omg_grasp.hip: no kernel uses scratch, and k_mesh_raycast keeps a ray's state and a
     face's nine coordinates in few enough registers for at least four waves per SIMD (65 VGPRs, seven)."""
-    flags = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", f"-I{ROOT / 'include'}",
-             f"-I{ROOT / 'omg-planner_amd' / 'csrc'}", "--cuda-device-only", "-c", "-Rpass-analysis=kernel-resource-usage"]
-    r = subprocess.run([HIPCC, *flags, str(ROOT / "omg-planner_amd" / "csrc" / "omg_grasp.hip"), "-o", str(tmp_path / "g.o")], check=True,
-                       stdout=subprocess.DEVNULL, stderr=subprocess.PIPE, text=True)
-    blocks = re.split(r"remark: Function Name: ", r.stderr)[1:]
-    seen = {}
-    for b in blocks:
-        name = re.match(r"\S+", b).group(0)
-        seen[name] = {k: int(re.search(rf"remark:\s+{re.escape(k)}: (\d+)", b).group(1))
-                      for k in ("VGPRs", "ScratchSize [bytes/lane]", "Occupancy [waves/SIMD]", "VGPRs Spill", "SGPRs Spill")}
-    kernels = {k: next(v for n, v in seen.items() if k in n) for k in ("k_mesh_raycast_reduce", "k_grasp_poses")}
-    kernels["k_mesh_raycast"] = next(v for n, v in seen.items() if "k_mesh_raycast" in n and "reduce" not in n)
+    seen = KB.kernel_resources("omg_grasp.hip", tmp_path)
+    kernels = {k: KB.one(seen, k) for k in ("k_mesh_raycast_reduce", "k_grasp_poses")}
+    kernels["k_mesh_raycast"] = KB.one({n: v for n, v in seen.items() if "reduce" not in n}, "k_mesh_raycast")
     for k, v in kernels.items():
         assert v["ScratchSize [bytes/lane]"] == 0 and v["VGPRs Spill"] == 0 and v["SGPRs Spill"] == 0, (k, v)
     assert kernels["k_mesh_raycast"]["Occupancy [waves/SIMD]"] >= 4 and kernels["k_mesh_raycast"]["VGPRs"] <= 128, kernels

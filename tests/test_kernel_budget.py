@@ -1,36 +1,25 @@
 """Register / LDS budget of the dominant kernel.  k_goalset_queue<2> runs at 5 workgroups per CU with <= 96 VGPRs and at most
 31 744 B of LDS per workgroup (tools/lds_occupancy_probe.hip: the CU admits 5 workgroups up to that size, 4 at 32 768 B
 although the occupancy API still answers 5), and it must not spill: scratch traffic in its main loop once cost 25 % of the
-kernel's speed.  This compiles the file to assembly (no GPU needed) and checks the figures the
-measured numbers were obtained with."""
+kernel's speed.  This compiles the file as the library's object is compiled (tests/kernel_build.py, no GPU needed)
+and checks the figures the measured numbers were obtained with."""
 import re
-import shutil
-import subprocess
 from pathlib import Path
 
-import pytest
+from tests import kernel_build as KB
 
 ROOT = Path(__file__).resolve().parents[1]
-HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
 
 
-@pytest.mark.skipif(not Path(HIPCC).exists(), reason="hipcc not installed")
+@KB.requires_hipcc
 def test_goalset_kernel_register_and_spill_budget(tmp_path):
-    out = tmp_path / "omg_kernels.s"
-    flags = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", f"-I{ROOT / 'include'}",
-             f"-I{ROOT / 'omg-planner_amd' / 'csrc'}", "--cuda-device-only", "-S"]
-    subprocess.run([HIPCC, *flags, str(ROOT / "omg-planner_amd" / "csrc" / "omg_kernels.hip"), "-o", str(out)], check=True,
-                   stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
-    text = out.read_text()
+    res = KB.kernel_resources("omg_kernels.hip", tmp_path)
     variants = [(st, lat, sp, pre, 4) for pre in (0, 1) for (st, lat, sp) in ((0, 0, 0), (1, 0, 0), (0, 0, 1), (1, 0, 1), (0, 1, 0))]
     variants += [(st, 0, 0, 0, w) for w in (8,) for st in (0, 1)]  # round 6: the WIDE instantiation (eight waves: 2 workgroups per CU)
     for st, lat, sp, pre, w in variants:  # batch, measuring, batch with split goals (x2), latency mode — each with its own kinematics and behind the pre-pass
         name = f"_Z15k_goalset_queueILi2ELb{st}ELb{lat}ELb{sp}ELb{pre}ELi{w}EEv9ChunkArgs"  # <LB, STAMP, LAT, SPLIT, PRE, W>
-        start = text.index(name + ":")
-        block = text[start: text.index("; Occupancy:", start) + 40]
-        vgprs = int(re.search(r"; NumVgprs: (\d+)", block).group(1))
-        scratch = int(re.search(r"; ScratchSize: (\d+)", block).group(1))
-        occupancy = int(re.search(r"; Occupancy: (\d+)", block).group(1))
+        v = KB.one(res, name)
+        vgprs, scratch, occupancy = v["VGPRs"], v["ScratchSize [bytes/lane]"], v["Occupancy [waves/SIMD]"]
         if not lat:  # the latency-mode variant (LAT = true) runs one or two workgroups per CU
             assert vgprs <= 96 and occupancy >= 5, (name, vgprs, occupancy)
         assert scratch == 0, f"{name} spills {scratch} bytes per lane: the goal path must stay in registers"
@@ -65,21 +54,13 @@ def test_goalset_kernel_lds_fits_five_workgroups_per_cu():
     assert "__shared__ float" not in src  # no static LDS on top of the dynamic allocation
 
 
-@pytest.mark.skipif(not Path(HIPCC).exists(), reason="hipcc not installed")
+@KB.requires_hipcc
 def test_update_kernels_have_no_static_lds(tmp_path):
     """k_update_optimize_split / k_update_optimize / k_chomp_optimize ask for up to all of a CU's LDS as DYNAMIC memory
     (hipFuncSetAttribute(..., 160 KB)): any static allocation on top — a `__shared__` variable, or a library helper that brings one,
     like __syncthreads_or — makes that call fail on the device.  Checked here on the compiled metadata, without a GPU."""
-    out = tmp_path / "omg_chomp.s"
-    flags = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", f"-I{ROOT / 'include'}",
-             f"-I{ROOT / 'omg-planner_amd' / 'csrc'}", "--cuda-device-only", "-S"]
-    subprocess.run([HIPCC, *flags, str(ROOT / "omg-planner_amd" / "csrc" / "omg_chomp.hip"), "-o", str(out)], check=True,
-                   stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
-    text = out.read_text()
-    seen = 0
-    for m in re.finditer(r"\.group_segment_fixed_size: (\d+)[\s\S]*?\.name:\s+(\S+)", text):
-        size, name = int(m.group(1)), m.group(2)
-        if "k_update_optimize" in name or "k_chomp_optimize" in name:
-            seen += 1
-            assert size == 0, f"{name} has {size} B of static LDS"
-    assert seen >= 4, seen  # split, fused and plain kernels in both item-count variants
+    res = KB.kernel_resources("omg_chomp.hip", tmp_path)
+    seen = {**KB.matching(res, "k_update_optimize"), **KB.matching(res, "k_chomp_optimize")}
+    for name, v in seen.items():
+        assert v["LDS Size [bytes/block]"] == 0, f"{name} has {v['LDS Size [bytes/block]']} B of static LDS"
+    assert len(seen) >= 4, sorted(seen)  # split, fused and plain kernels in both item-count variants

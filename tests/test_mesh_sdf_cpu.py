@@ -5,18 +5,13 @@ and the compiled kernel's registers.  The device side is tests/test_gpu_mesh_sdf
 from __future__ import annotations
 
 import ctypes as C
-import re
-import subprocess
 from fractions import Fraction
-from pathlib import Path
 
 import numpy as np
 import pytest
 
+from tests import kernel_build as KB
 from tests import mesh_cases as MC
-
-ROOT = Path(__file__).resolve().parents[1]
-HIPCC = "/opt/rocm/bin/hipcc"
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -386,24 +381,12 @@ extern "C" void host_mesh(const double* verts, const int32_t* faces, int nf, con
 """
 
 
-def _host_compiler():
-    import shutil
-    for cxx in ("/opt/rocm/llvm/bin/clang++", shutil.which("clang++"), shutil.which("c++"), shutil.which("g++")):
-        if cxx and Path(cxx).exists():
-            return cxx
-    return None
-
-
-@pytest.mark.skipif(_host_compiler() is None, reason="no C++ compiler")
+@KB.requires_host_cxx
 def test_kernel_pair_body_compiled_for_the_host_equals_the_specification(tmp_path):
     """csrc/omg_mesh_sdf_body.h is what k_mesh_sdf does per (node, face) pair; compiled for the host without contraction it gives
     the specification's float64 distance bit for bit, and the same inside decision, on closed and open meshes."""
     from omg_planner_amd import scenes as sc
-    (tmp_path / "h.cpp").write_text(_HOST_HARNESS)
-    so = tmp_path / "h.so"
-    subprocess.run([_host_compiler(), "-O2", "-ffp-contract=off", "-shared", "-fPIC", "-Wno-unknown-pragmas", f"-I{ROOT / 'omg-planner_amd' / 'csrc'}",
-                    str(tmp_path / "h.cpp"), "-o", str(so)], check=True)
-    lib = C.CDLL(str(so))
+    lib = KB.host_harness(_HOST_HARNESS, tmp_path)
     lib.host_mesh.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
     ico = MC.icosphere(2, 0.06, (0.003, -0.002, 0.001))
     for v, f, delta, sample in ((*MC.box_mesh(MC.BOX_HALF, MC.pose((1.1, 0.4, -0.7), (-0.4, 1.5, 0.25))), 0.011, "node"),
@@ -421,19 +404,11 @@ def test_kernel_pair_body_compiled_for_the_host_equals_the_specification(tmp_pat
         assert np.abs(hw - w).max() < 1e-12
 
 
-@pytest.mark.skipif(not Path(HIPCC).exists(), reason="hipcc not installed")
+@KB.requires_hipcc
 def test_mesh_sdf_kernel_does_not_spill(tmp_path):
     """k_mesh_sdf keeps a node's whole state and a face's nine coordinates in registers: no scratch (128
     VGPRs, four waves per SIMD)."""
-    out = tmp_path / "omg_mesh_sdf.s"
-    flags = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", f"-I{ROOT / 'include'}",
-             f"-I{ROOT / 'omg-planner_amd' / 'csrc'}", "--cuda-device-only", "-S"]
-    subprocess.run([HIPCC, *flags, str(ROOT / "omg-planner_amd" / "csrc" / "omg_mesh_sdf.hip"), "-o", str(out)], check=True,
-                   stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
-    text = out.read_text()
-    name = re.search(r"^(\S*k_mesh_sdf\S*):", text, re.M).group(1)
-    start = text.index(name + ":")
-    block = text[start: text.index("; Occupancy:", start) + 40]
-    assert int(re.search(r"; ScratchSize: (\d+)", block).group(1)) == 0
-    assert int(re.search(r"; NumVgprs: (\d+)", block).group(1)) <= 128
-    assert int(re.search(r"; Occupancy: (\d+)", block).group(1)) >= 4
+    v = KB.one(KB.kernel_resources("omg_mesh_sdf.hip", tmp_path), "k_mesh_sdf")
+    assert v["ScratchSize [bytes/lane]"] == 0
+    assert v["VGPRs"] <= 128
+    assert v["Occupancy [waves/SIMD]"] >= 4

@@ -4,17 +4,13 @@ argument errors come back through the C ABI and the wrapper, and the kernel uses
 from __future__ import annotations
 
 import ctypes as C
-import re
-import subprocess
 from pathlib import Path
 
 import numpy as np
 import pytest
 
+from tests import kernel_build as KB
 from tests import register_cases as RC
-
-ROOT = Path(__file__).resolve().parents[1]
-HIPCC = "/opt/rocm/bin/hipcc"
 
 
 @pytest.fixture(scope="module")
@@ -267,28 +263,13 @@ extern "C" void host_register(const rec* objects, const float* pool, const int32
 """
 
 
-def _host_compiler():
-    import shutil
-    for cxx in ("/opt/rocm/llvm/bin/clang++", shutil.which("clang++"), shutil.which("c++"), shutil.which("g++")):
-        if cxx and Path(cxx).exists():
-            return cxx
-    return None
-
-
 @pytest.fixture(scope="module")
 def host_lib(tmp_path_factory):
-    if _host_compiler() is None:
+    if KB.host_compiler() is None:
         pytest.skip("no C++ compiler")
-    tmp = tmp_path_factory.mktemp("register_host")
-    (tmp / "h.cpp").write_text(_HOST_HARNESS)
-    so = tmp / "h.so"
-    subprocess.run([_host_compiler(), "-O2", "-std=c++17", "-ffp-contract=off", "-shared", "-fPIC", "-Wno-unknown-pragmas",
-                    f"-I{ROOT / 'omg-planner_amd' / 'csrc'}", str(tmp / "h.cpp"), "-o", str(so)], check=True)
-    lib = C.CDLL(str(so))
     vp, dbl, i = C.c_void_p, C.c_double, C.c_int
-    lib.host_register.argtypes = [vp] * 6 + [i, i, dbl, dbl, dbl, i, vp, vp]
-    lib.host_register.restype = None
-    return lib
+    return KB.host_harness(_HOST_HARNESS, tmp_path_factory.mktemp("register_host"),
+                           {"host_register": (None, [vp] * 6 + [i, i, dbl, dbl, dbl, i, vp, vp])})
 
 
 def host_register(lib, c):
@@ -493,18 +474,11 @@ def test_set_object_poses_equals_set_object_pose_on_the_host(reg):
 # ---------------------------------------------------------------------------------------------------------------------
 # registers
 # ---------------------------------------------------------------------------------------------------------------------
-@pytest.mark.skipif(not Path(HIPCC).exists(), reason="hipcc not installed")
+@KB.requires_hipcc
 def test_register_kernel_does_not_spill(tmp_path):
     """The compiler's resource remarks for csrc/omg_register.hip: k_register_clouds keeps a lane's 28 partials, two sets of totals
     and two poses in registers, without scratch; its LDS is the two slots of four wave totals."""
-    flags = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", f"-I{ROOT / 'include'}",
-             f"-I{ROOT / 'omg-planner_amd' / 'csrc'}", "--cuda-device-only", "-c", "-Rpass-analysis=kernel-resource-usage"]
-    r = subprocess.run([HIPCC, *flags, str(ROOT / "omg-planner_amd" / "csrc" / "omg_register.hip"), "-o", str(tmp_path / "r.o")], check=True,
-                       stdout=subprocess.DEVNULL, stderr=subprocess.PIPE, text=True)
-    blocks = [b for b in re.split(r"remark: Function Name: ", r.stderr)[1:] if "k_register_clouds" in b]
-    assert len(blocks) == 1
-    v = {k: int(re.search(rf"remark:\s+{re.escape(k)}: (\d+)", blocks[0]).group(1))
-         for k in ("VGPRs", "AGPRs", "ScratchSize [bytes/lane]", "Occupancy [waves/SIMD]", "VGPRs Spill", "SGPRs Spill", "LDS Size [bytes/block]")}
+    v = KB.one(KB.kernel_resources("omg_register.hip", tmp_path), "k_register_clouds")
     print(v)
     assert v["ScratchSize [bytes/lane]"] == 0 and v["VGPRs Spill"] == 0 and v["SGPRs Spill"] == 0, v
     assert v["Occupancy [waves/SIMD]"] >= 1 and v["LDS Size [bytes/block]"] == 2 * 4 * (28 * 8 + 4), v

@@ -5,17 +5,12 @@ every argument error of the C ABI and of the wrappers; the kernels use no scratc
 from __future__ import annotations
 
 import ctypes as C
-import re
-import subprocess
-from pathlib import Path
 
 import numpy as np
 import pytest
 
+from tests import kernel_build as KB
 from tests import surface_cases as SC
-
-ROOT = Path(__file__).resolve().parents[1]
-HIPCC = "/opt/rocm/bin/hipcc"
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -175,26 +170,12 @@ extern "C" void host_surface(const float* vol, const int32_t* n, const double* o
 """
 
 
-def _host_compiler():
-    import shutil
-    for cxx in ("/opt/rocm/llvm/bin/clang++", shutil.which("clang++"), shutil.which("c++"), shutil.which("g++")):
-        if cxx and Path(cxx).exists():
-            return cxx
-    return None
-
-
-@pytest.mark.skipif(_host_compiler() is None, reason="no C++ compiler")
+@KB.requires_host_cxx
 def test_kernel_body_compiled_for_the_host_equals_the_specification(tmp_path):
     """csrc/omg_surface_body.h is what a thread of the kernels does for its sample; compiled for the host without contraction and
     walked sample by sample it gives the specification's vertices as int64 bits, its faces and its open edges on every case."""
-    (tmp_path / "h.cpp").write_text(_HOST_HARNESS)
-    so = tmp_path / "h.so"
-    subprocess.run([_host_compiler(), "-O2", "-ffp-contract=off", "-shared", "-fPIC", "-Wno-unknown-pragmas", f"-I{ROOT / 'omg-planner_amd' / 'csrc'}",
-                    str(tmp_path / "h.cpp"), "-o", str(so)], check=True)
-    lib = C.CDLL(str(so))
     vp = C.c_void_p
-    lib.host_surface.argtypes = [vp, vp, vp, C.c_double, C.c_double, C.c_float, vp, vp, vp, vp]
-    lib.host_surface.restype = None
+    lib = KB.host_harness(_HOST_HARNESS, tmp_path, {"host_surface": (None, [vp, vp, vp, C.c_double, C.c_double, C.c_float, vp, vp, vp, vp])})
     samples = 0
     for name in SC.ALL:
         c = SC.case(name)
@@ -334,18 +315,11 @@ def test_wrapper_checks_without_gpu():
 # ---------------------------------------------------------------------------------------------------------------------
 # registers
 # ---------------------------------------------------------------------------------------------------------------------
-@pytest.mark.skipif(not Path(HIPCC).exists(), reason="hipcc not installed")
+@KB.requires_hipcc
 def test_surface_kernels_do_not_spill(tmp_path):
     """The compiler's resource remarks for csrc/omg_surface.hip: no kernel uses scratch (the eight corners and the twelve edges
     of a cell stay in registers)."""
-    flags = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", f"-I{ROOT / 'include'}",
-             f"-I{ROOT / 'omg-planner_amd' / 'csrc'}", "--cuda-device-only", "-c", "-Rpass-analysis=kernel-resource-usage"]
-    r = subprocess.run([HIPCC, *flags, str(ROOT / "omg-planner_amd" / "csrc" / "omg_surface.hip"), "-o", str(tmp_path / "s.o")], check=True,
-                       stdout=subprocess.DEVNULL, stderr=subprocess.PIPE, text=True)
-    seen = {}
-    for b in re.split(r"remark: Function Name: ", r.stderr)[1:]:
-        seen[re.match(r"\S+", b).group(0)] = {k: int(re.search(rf"remark:\s+{re.escape(k)}: (\d+)", b).group(1))
-                                             for k in ("VGPRs", "ScratchSize [bytes/lane]", "VGPRs Spill", "SGPRs Spill")}
-    kernels = {k: next(v for n, v in seen.items() if k in n) for k in ("k_surface_count", "k_surface_scan", "k_surface_gather")}
+    seen = KB.kernel_resources("omg_surface.hip", tmp_path)
+    kernels = {k: KB.one(seen, k) for k in ("k_surface_count", "k_surface_scan", "k_surface_gather")}
     for k, v in kernels.items():
         assert v["ScratchSize [bytes/lane]"] == 0 and v["VGPRs Spill"] == 0 and v["SGPRs Spill"] == 0 and v["VGPRs"] <= 128, (k, v)

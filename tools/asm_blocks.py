@@ -4,7 +4,7 @@ of them move values between the scalar file and spill lanes, and how often each 
 No GPU needed.  Compile the listing (the Makefile's flags, device side only; line tables add the source lines to the table and do
 not change the code):
 
-    hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off --cuda-device-only -S -gline-tables-only \
+    hipcc $(make -s -C omg-planner_amd/csrc flags) --cuda-device-only -S -gline-tables-only \
           -Rpass-analysis=kernel-resource-usage omg-planner_amd/csrc/omg_kernels.hip -o omg_kernels.s 2> remarks.txt
     python tools/asm_blocks.py omg_kernels.s                       # k_goalset_queue<2,false,false,false,false,4>
     python tools/asm_blocks.py omg_kernels.s --path BB19_95,BB19_97x7 --json out.json
