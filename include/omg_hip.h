@@ -958,6 +958,64 @@ int omgx_surface_gather(const float* pool, int64_t pool_elems, const omgx_mesh* 
                         int32_t* faces, int64_t face_cap, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * (17) omgx_carve_views, omgx_distance_transform: depth views to signed obstacle volumes
+ * The reference's obstacle volume from observation (PointEnv.compute_sdf_from_points, omg/core.py:426-457; here
+ * omgx_point_cloud_sdf) is unsigned, takes space no camera has seen for free and tests every node against every point.  Here
+ * V depth images classify the nodes of M volumes (a ragged batch) as FREE 0, SURFACE 1 or UNKNOWN 2, and an exact Euclidean
+ * distance transform of that classification becomes a signed float32 volume in the SDF pool, at a cost that does not depend on
+ * the number of pixels.  omg-planner_amd/fusion.py (carve_views, distance_transform) is the specification; all arithmetic is
+ * float64 without contraction, dot products as ((a*x + b*y) + c*z) + d, with + - * /, floor and sqrt only, and states and
+ * volumes have the specification's bits.  New entry points only: omgx_abi_version() stays 14.
+ *
+ * A volume is an omgx_mesh record as in (16): origin, delta, sample_offset, dims, out_offset = the element offset of node
+ * (0,0,0) in `pool` (read by omgx_distance_transform only), first_workgroup = the prefix table with
+ * OMGX_FUSION_NODES_PER_WORKGROUP nodes per workgroup; the vert / face fields are ignored.  Node (i,j,k) has the linear index
+ * L = (i * dims[1] + j) * dims[2] + k and its state at state[state_begin[m] + L].
+ * A view is one row of 16 doubles: fx, fy, cx, cy and the rows of cam_from_grid [3,4]; the camera convention is that of (14):
+ * optical axis +z, rows downwards, depth along the axis.  View v reads image v of depth [V][H][W] double (omgx_render_depth's
+ * t_out: +inf is background).  Volume m uses the views view_range[m][0] .. + view_range[m][1]; ranges of two volumes may overlap.
+ *
+ * omgx_carve_views: one thread per node.  p = origin + ((i,j,k) + sample_offset) * delta per component, q = cam_from_grid p,
+ *   z = q[2].  A view gives no information if !(z > near), or the pixel c = floor((fx*(q0/z) + cx) + 0.5),
+ *   r = floor((fy*(q1/z) + cy) + 0.5) is outside the image, or !(d > 0) with d = depth[v][r][c] (NaN and depths <= 0 say
+ *   nothing; r and c are clamped into the image before the load).  Otherwise it says free if z < d - band, surface if
+ *   d - band <= z <= d + band, nothing behind the surface.  state = 1 if any view says surface, else 0 if any view says free,
+ *   else 2.  merge != 0: the flags start from what `state` holds (1: surface, 0: free, anything else: nothing), so that carving
+ *   the views A and then merging the views B equals carving A and B together.
+ * omgx_distance_transform: a node is occupied if its state is 1, or is neither 0 nor 1 and unknown_occupied != 0; every other
+ *   node is free.  d2(p, X) = min(radius^2, min over the nodes q of X in the same volume of |p - q|^2) in index units, an exact
+ *   integer.  value = occupied ? -((sqrt((double)d2(p, free)) - 0.5) * delta) : (sqrt((double)d2(p, occupied)) - 0.5) * delta,
+ *   rounded to float32 once, at pool[out_offset + L]: the zero level lies on the faces between occupied and free voxels and
+ *   distances saturate at (radius - 0.5) * delta.  Three launches, one per axis (z, y, x), each a windowed minimum over
+ *   +-radius of both channels (to occupied, to free) saturated at radius^2 in 16 bits; the y and x passes stage
+ *   [axis][64 consecutive elements] in LDS, an axis longer than OMGX_FUSION_CHUNK in chunks with a halo of radius.  `workspace`:
+ *   omgx_distance_transform_workspace_bytes bytes (two 4-byte intermediates per node of every workgroup).  No atomics; the
+ *   stream is the only barrier.
+ * `volumes`, `views`, `view_range`, `state_begin` are on the device, h_* the same on the host; ALL checks are made on the host
+ * copies before any HIP call.  OMGX_ERR_INVALID: a null pointer (everything per volume may be NULL with M == 0, views and
+ * depth with V == 0), a negative count, H or W < 1 with V > 0, a dims < 1, delta <= 0 or not finite, an origin, band, near or
+ * view field that is not finite, fx or fy zero, a sample_offset other than 0.0 / 0.5, a negative out_offset, a view range
+ * outside [0, V], a state range outside [0, state_elems) or a volume outside [0, pool_elems), state ranges (or volumes in the
+ * pool) of two records that overlap, a first_workgroup that is not the prefix sum, radius < 1.  OMGX_ERR_UNSUPPORTED: radius >
+ * OMGX_FUSION_MAX_RADIUS, more than 2^31 - 1 nodes in one volume or workgroups in all, V * H * W > 2^31 - 1.  M == 0 returns
+ * OMGX_OK and launches nothing.
+ * ------------------------------------------------------------------------------------------- */
+#define OMGX_FUSION_NODES_PER_WORKGROUP 256
+#define OMGX_FUSION_MAX_RADIUS 255 /* radius^2 fits 16 bits                                        */
+#define OMGX_FUSION_CHUNK 64       /* outputs along the axis per workgroup of the y and x passes   */
+#define OMGX_FUSION_FREE 0
+#define OMGX_FUSION_SURFACE 1
+#define OMGX_FUSION_UNKNOWN 2
+int omgx_carve_views(const omgx_mesh* volumes, const omgx_mesh* h_volumes, int32_t num_volumes, const double* views,
+                     const double* h_views, int32_t num_views, const int32_t* view_range, const int32_t* h_view_range,
+                     const int64_t* state_begin, const int64_t* h_state_begin, const double* depth, int32_t H, int32_t W,
+                     double band, double near, int32_t merge, uint8_t* state, int64_t state_elems, void* stream);
+int64_t omgx_distance_transform_workspace_bytes(const omgx_mesh* h_volumes, int32_t num_volumes, int32_t radius);
+int omgx_distance_transform(const uint8_t* state, int64_t state_elems, const int64_t* state_begin, const int64_t* h_state_begin,
+                            const omgx_mesh* volumes, const omgx_mesh* h_volumes, int32_t num_volumes, int32_t radius,
+                            int32_t unknown_occupied, void* workspace, float* pool, int64_t pool_elems, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Diagnostics
  * ------------------------------------------------------------------------------------------- */
 const char* omgx_last_error(void); /* thread-local text of the last OMGX_ERR_LAUNCH               */

@@ -197,6 +197,37 @@ class Observation:
         points, begin = ops.pixel_clouds(self.batch, self.t, self.inst, cls)
         return [points[int(begin[s]): int(begin[s + 1])] for s in range(len(begin) - 1)]
 
+    def view_rows(self, table, pairs) -> np.ndarray:
+        """fusion.view_rows [n,16] of the (scene, obj) `pairs` of an ops.DeviceScenes: the camera of the pair's scene, and
+        cam_from_grid = inv(world_from_cam) @ world_from_obj with the object's pose from the table's host mirror."""
+        from . import fusion
+        cams, poses = self.batch.h_cameras, table_object_poses(table)
+        views = np.zeros((len(pairs), 16))
+        for m, (s, o) in enumerate(np.asarray(pairs, np.int64).reshape(-1, 2)):
+            cam_from_world = np.linalg.inv(np.vstack([cams["world_from_cam"][s].reshape(3, 4), [0.0, 0.0, 0.0, 1.0]]))
+            views[m] = fusion.view_rows([cams[k][s] for k in ("fx", "fy", "cx", "cy")], cam_from_world @ poses[table._index(int(s), int(o))])
+        return views
+
+    def fuse_obstacles(self, table, pairs, layouts, band: float, near: float, reach: float, unknown_occupied: bool = True,
+                       target_free: bool = True) -> int:
+        """The obstacle volumes of the (scene, obj) `pairs` of an ops.DeviceScenes from this observation's depth images
+        (ops.DeviceScenes.fuse_obstacles, which documents layouts, band, near and reach): pair m is seen by the camera of its own
+        scene, through the view row fusion.view_rows(intrinsics, cam_from_world @ world_from_obj) with the object's pose from the
+        table's host mirror.  target_free: the pixels of label 0 (the target) count as background, so that the volume holds the
+        non-target points only, as omg/core.py:849-851 splits them.  Returns the radius used."""
+        import torch
+        pairs = np.asarray(pairs, np.int64).reshape(-1, 2)
+        views = self.view_rows(table, pairs)
+        free_mask = None
+        if target_free:
+            labels, begin = self.batch.h_instances["label"], self.batch.h_inst_begin
+            lut = [torch.from_numpy(np.concatenate([labels[int(begin[s]): int(begin[s + 1])] == 0, [False]])).to(self.inst.device)
+                   for s in range(len(begin) - 1)]  # (the last entry: inst == -1, the background)
+            free_mask = torch.stack([lut[int(s)][self.inst[int(s)].long()] for s in pairs[:, 0]])
+        depth = self.t[torch.from_numpy(pairs[:, 0].copy()).to(self.t.device)].contiguous()
+        return table.fuse_obstacles(pairs, depth, views, np.stack([np.arange(len(pairs)), np.ones(len(pairs), np.int64)], -1), layouts, band,
+                                    near, reach, unknown_occupied, free_mask)
+
 
 def observe_scenes(scenes, meshes, cam_from_world, intrinsics, H: int, W: int, cull: bool = True, device="cuda:0") -> Observation:
     """Depth and instance images of S scenes.Scene on the device, one launch (scene_records, ops.CameraBatch, ops.render_depth).

@@ -1,8 +1,12 @@
-// omg_mesh_common.h — what the mesh translation units (omg_mesh_sdf.hip, omg_grasp.hip) share: the face tile that k_mesh_sdf and
-// k_mesh_raycast stage in LDS, and the checks on one host omgx_mesh record (include/omg_hip.h sections 12 and 13).
+// omg_mesh_common.h — what the translation units that take omgx_mesh records share: the face tile that k_mesh_sdf and
+// k_mesh_raycast stage in LDS (omg_mesh_sdf.hip, omg_grasp.hip), the checks on one host omgx_mesh record (include/omg_hip.h
+// sections 12 and 13) and on a batch of volumes (omg_surface.hip, omg_fusion.hip: sections 16 and 17).
 #pragma once
+#include <algorithm>
 #include <cmath>
 #include <cstdint>
+#include <utility>
+#include <vector>
 
 #include "omg_host.h"
 
@@ -43,4 +47,38 @@ static inline int mesh_check_volume(const omgx_mesh& h) {
     for (int a = 0; a < 3; ++a)
         if (!std::isfinite(h.origin[a])) return OMGX_ERR_INVALID;
     return mesh_node_count(h) > (int64_t)1 << 31 ? OMGX_ERR_UNSUPPORTED : OMGX_OK;
+}
+
+// The host copies of a batch of volume records -> OMGX_OK, OMGX_ERR_INVALID or OMGX_ERR_UNSUPPORTED (an invalid field of any
+// record first); first_workgroup must be the prefix table at `per_workgroup` nodes per workgroup; *workgroups: all of them.
+// pool_elems < 0: the volumes' place in the pool is not checked.
+static inline int mesh_check_volumes(const omgx_mesh* h_meshes, int32_t num_meshes, int64_t pool_elems, int per_workgroup,
+                                     int64_t* workgroups) {
+    if (!h_meshes || num_meshes < 1) return OMGX_ERR_INVALID;
+    bool too_big = false;
+    int64_t wg = 0;
+    for (int32_t m = 0; m < num_meshes; ++m) {
+        const omgx_mesh& h = h_meshes[m];
+        const int volume = mesh_check_volume(h);
+        if (volume == OMGX_ERR_INVALID || h.first_workgroup != wg) return OMGX_ERR_INVALID;
+        const int64_t samples = mesh_node_count(h);
+        if (samples > 0x7fffffffll) too_big = true;
+        else if (pool_elems >= 0 && (samples > pool_elems || h.out_offset > pool_elems - samples)) return OMGX_ERR_INVALID;
+        wg += (samples + per_workgroup - 1) / per_workgroup;
+        if (wg > 0x7fffffffll) too_big = true;
+    }
+    *workgroups = wg;
+    return too_big ? OMGX_ERR_UNSUPPORTED : OMGX_OK;
+}
+
+// Do two of the ranges [begin, begin + count) overlap?  (begins >= 0; empty ranges overlap nothing)
+static inline bool mesh_ranges_overlap(std::vector<std::pair<int64_t, int64_t>>& r) {
+    std::sort(r.begin(), r.end());
+    int64_t end = 0;
+    for (const auto& x : r) {
+        if (x.second == 0) continue;
+        if (x.first < end) return true;
+        end = x.first + x.second;
+    }
+    return false;
 }

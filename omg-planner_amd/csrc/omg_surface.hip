@@ -9,7 +9,6 @@
 //   k_surface_gather  the flags again; a vertex goes to row offset + rank, a closed crossing edge reads the ranks of its four cells
 //                     (and their workgroups' offsets) and writes its two triangles at twice its own scanned rank
 // The arithmetic is omg_surface_body.h: float64, contraction off, the bits of scenes.surface_nets.  Plain loads and stores only.
-#include <algorithm>
 #include <utility>
 #include <vector>
 
@@ -187,43 +186,11 @@ __global__ __launch_bounds__(SURF_BLOCK) void k_surface_gather(const float* __re
     }
 }
 
-// The host copies of the records -> OMGX_OK, OMGX_ERR_INVALID or OMGX_ERR_UNSUPPORTED (an invalid field of any record first);
-// *workgroups: all of them.  pool_elems < 0: the volumes' place in the pool is not checked.
-int check_volumes(const omgx_mesh* h_meshes, int32_t num_meshes, int64_t pool_elems, int64_t* workgroups) {
-    if (!h_meshes || num_meshes < 1) return OMGX_ERR_INVALID;
-    bool too_big = false;
-    int64_t wg = 0;
-    for (int32_t m = 0; m < num_meshes; ++m) {
-        const omgx_mesh& h = h_meshes[m];
-        const int volume = mesh_check_volume(h);
-        if (volume == OMGX_ERR_INVALID || h.first_workgroup != wg) return OMGX_ERR_INVALID;
-        const int64_t samples = mesh_node_count(h);
-        if (samples > 0x7fffffffll) too_big = true;
-        else if (pool_elems >= 0 && (samples > pool_elems || h.out_offset > pool_elems - samples)) return OMGX_ERR_INVALID;
-        wg += (samples + SURF_BLOCK - 1) / SURF_BLOCK;
-        if (wg > 0x7fffffffll) too_big = true;
-    }
-    *workgroups = wg;
-    return too_big ? OMGX_ERR_UNSUPPORTED : OMGX_OK;
-}
-
-// Do two of the row ranges [begin, begin + count) overlap?  (empty ranges overlap nothing)
-bool ranges_overlap(std::vector<std::pair<int64_t, int64_t>>& r) {
-    std::sort(r.begin(), r.end());
-    int64_t end = 0;
-    for (const auto& x : r) {
-        if (x.second == 0) continue;
-        if (x.first < end) return true;
-        end = x.first + x.second;
-    }
-    return false;
-}
-
 }  // namespace
 
 extern "C" int64_t omgx_surface_workspace_bytes(const omgx_mesh* h_meshes, int32_t num_meshes) {
     int64_t wg = 0;
-    const int status = check_volumes(h_meshes, num_meshes, -1, &wg);
+    const int status = mesh_check_volumes(h_meshes, num_meshes, -1, SURF_BLOCK, &wg);
     if (status != OMGX_OK) return status;
     return wg * (int64_t)(SURF_TOTALS * sizeof(int32_t)) + wg * SURF_BLOCK;
 }
@@ -232,7 +199,7 @@ extern "C" int omgx_surface_count(const float* pool, int64_t pool_elems, const o
                                   int32_t num_meshes, float level, void* workspace, int32_t* counts, void* stream) {
     if (!pool || !meshes || !h_meshes || !workspace || !counts || pool_elems < 0 || std::isnan(level)) return OMGX_ERR_INVALID;
     int64_t wg = 0;
-    const int status = check_volumes(h_meshes, num_meshes, pool_elems, &wg);
+    const int status = mesh_check_volumes(h_meshes, num_meshes, pool_elems, SURF_BLOCK, &wg);
     if (status != OMGX_OK) return status;
     int32_t* totals = (int32_t*)workspace;
     hipLaunchKernelGGL(k_surface_count, dim3((unsigned)wg), dim3(SURF_BLOCK), 0, (hipStream_t)stream, pool, meshes, (int)num_meshes, level, totals,
@@ -249,7 +216,7 @@ extern "C" int omgx_surface_gather(const float* pool, int64_t pool_elems, const 
     if (!pool || !meshes || !h_meshes || !workspace || pool_elems < 0 || std::isnan(level) || vert_cap < 0 || face_cap < 0) return OMGX_ERR_INVALID;
     if ((vert_cap > 0 && !verts) || (face_cap > 0 && !faces)) return OMGX_ERR_INVALID;
     int64_t wg = 0;
-    const int status = check_volumes(h_meshes, num_meshes, pool_elems, &wg);
+    const int status = mesh_check_volumes(h_meshes, num_meshes, pool_elems, SURF_BLOCK, &wg);
     if (status == OMGX_ERR_INVALID) return status;
     std::vector<std::pair<int64_t, int64_t>> vr, fr;
     for (int32_t m = 0; m < num_meshes; ++m) {
@@ -257,7 +224,7 @@ extern "C" int omgx_surface_gather(const float* pool, int64_t pool_elems, const 
         if (h.vert_begin < 0 || h.vert_count < 0 || h.face_begin < 0 || h.face_count < 0) return OMGX_ERR_INVALID;
         vr.emplace_back(h.vert_begin, h.vert_count), fr.emplace_back(h.face_begin, h.face_count);
     }
-    if (ranges_overlap(vr) || ranges_overlap(fr)) return OMGX_ERR_INVALID;
+    if (mesh_ranges_overlap(vr) || mesh_ranges_overlap(fr)) return OMGX_ERR_INVALID;
     if (status != OMGX_OK) return status;
     if (vert_cap == 0 && face_cap == 0) return OMGX_OK;
     const int32_t* totals = (const int32_t*)workspace;

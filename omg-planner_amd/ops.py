@@ -487,6 +487,45 @@ class DeviceScenes:
         verts, faces, vrows, frows, open_edges = surface_meshes(self.pool, self.surface_records(leaders), level)
         return verts, faces, vrows[which], frows[which], open_edges[which]
 
+    def fuse_obstacles(self, pairs, depth: torch.Tensor, views, view_range, layouts, band: float, near: float, reach: float,
+                       unknown_occupied: bool = True, free_mask: "torch.Tensor | None" = None) -> int:
+        """The observed obstacle volumes of the (scene, obj) `pairs` from depth views, written straight into the pool: ONE carve
+        launch and three transform launches for all pairs (carve_views, distance_transform), then grid_slot's slot becomes the
+        object's volume through replace_grid(fit="device"), object by object.  layouts: one (origin [3], delta, dims [3]) per pair,
+        voxel centres, in the object's own frame; views [V,16] (fusion.view_rows with cam_from_grid = cam_from_world times the
+        object's pose) and view_range [n,2] as carve_views takes them; depth [V,H,W] float64 on the device.  reach: the distance up
+        to which the cost reads the volume (epsilon + clearance): radius = ceil(reach / delta + 0.5) + 1 of the finest layout, so
+        the saturation lies beyond it.  free_mask: a bool tensor [V,H,W]; its pixels are set to +inf first (the target's pixels:
+        the reference's "non-target points only").  Returns the radius."""
+        from . import fusion as _fu
+        self._changing(volumes=True)
+        pairs = np.asarray(pairs, np.int64).reshape(-1, 2)
+        layouts = list(layouts)
+        if len(layouts) != len(pairs) or not len(pairs):
+            raise _lib.OmgHipError(f"{len(pairs)} pairs need as many layouts, and at least one")
+        if len({self._index(int(s), int(o)) for s, o in pairs}) != len(pairs):
+            raise _lib.OmgHipError("a (scene, obj) pair is named twice")
+        if not (np.isfinite(float(reach)) and float(reach) >= 0):
+            raise _lib.OmgHipError("reach must be finite and not negative")
+        # everything that can be refused is refused here, before grid_slot offers a slot: the radius, the layouts, the views
+        _carve_arguments([(origin, delta, "centre", dims) for origin, delta, dims in layouts], views, view_range, depth, band, near, None)
+        radius = _fusion_radius(max(_fu.obstacle_radius(reach, float(delta)) for _, delta, _ in layouts))
+        _need(depth, torch.float64, "depth")
+        if free_mask is not None:
+            if (not isinstance(free_mask, torch.Tensor) or free_mask.dtype != torch.bool or free_mask.shape != depth.shape
+                    or free_mask.device != depth.device):
+                raise _lib.OmgHipError("free_mask must be a bool tensor of depth's shape, on its device")
+            depth = torch.where(free_mask, torch.full_like(depth, float("inf")), depth).contiguous()
+        slots, volumes = [], []
+        for (s, o), (origin, delta, dims) in zip(pairs, layouts):
+            slot = self.grid_slot(int(s), int(o), tuple(int(d) for d in dims))
+            slots.append(slot)
+            volumes.append((origin, delta, "centre", dims, (slot.data_ptr() - self.pool.data_ptr()) // 4))
+        fuse_views(volumes, views, view_range, depth, band, near, radius, unknown_occupied, out=self.pool)
+        for (s, o), (origin, delta, _), slot in zip(pairs, layouts, slots):
+            self.replace_grid(int(s), int(o), slot, origin, float(delta), fit="device")
+        return radius
+
     def sync_host(self) -> np.ndarray:
         """Bring the host mirror of the records up to date with the device (one small copy; tests, oracle comparisons)."""
         self.host_objects[:] = self.objects.cpu().numpy().view(self.host_objects.dtype)  # in place: scene ranges share the mirror
@@ -1258,6 +1297,131 @@ def surface_mesh(grid: torch.Tensor, origin, delta, sample: str = "centre", leve
         raise _lib.OmgHipError("grid must be a tensor [X,Y,Z]")
     verts, faces, _, _, open_edges = surface_meshes(grid, [(origin, delta, sample, tuple(grid.shape), 0)], level)
     return verts, faces, int(open_edges[0])
+
+
+def _fusion_volumes(volumes, state_begin):
+    """(records, node counts, state_begin int64 [M]) of a fusion launch; volumes: what surface_records takes (the prefix table is
+    the same: 256 nodes per workgroup), or [] for an empty launch; a layout without its fifth field, the element offset in the
+    pool, lies behind the layout before it (the first at 0)."""
+    assert _lib.FUSION_NODES_PER_WORKGROUP == _lib.SURFACE_NODES_PER_WORKGROUP
+    rec = volumes if isinstance(volumes, C.Array) else [tuple(v) for v in volumes]
+    if not isinstance(rec, C.Array):
+        at = 0
+        for m, v in enumerate(rec):
+            if len(v) == 4:
+                rec[m] = v + (at,)
+            if len(rec[m]) != 5:
+                raise _lib.OmgHipError(f"volume {m}: (origin, delta, sample, dims[, offset]), got {len(v)} fields")
+            at = int(rec[m][4]) + int(np.prod([int(d) for d in np.asarray(v[3]).reshape(-1)]))
+    rec = surface_records(rec) if len(rec) else (_lib.Mesh * 0)()
+    nodes = np.array([int(r.dims[0]) * int(r.dims[1]) * int(r.dims[2]) for r in rec], np.int64)
+    begin = np.cumsum(nodes) - nodes if state_begin is None else np.ascontiguousarray(state_begin, np.int64).reshape(-1)
+    if len(begin) != len(rec):
+        raise _lib.OmgHipError(f"state_begin must have one offset per volume ({len(rec)}), got {len(begin)}")
+    return rec, nodes, begin
+
+
+def _upload(a: np.ndarray, dev) -> torch.Tensor:
+    return torch.from_numpy(np.frombuffer(bytes(a), np.uint8).copy() if isinstance(a, C.Array) else np.ascontiguousarray(a)).to(dev)
+
+
+def _fusion_radius(radius) -> int:
+    radius = int(radius)
+    if not 1 <= radius <= _lib.FUSION_MAX_RADIUS:
+        raise _lib.OmgHipError(f"radius must lie in [1, {_lib.FUSION_MAX_RADIUS}], got {radius}")
+    return radius
+
+
+def _carve_arguments(volumes, views, view_range, depth, band, near, state_begin):
+    """The host side of a carve launch, checked before anything touches the device -> (records, node counts, state_begin
+    int64 [M], views float64 [V,16], view_range int32 [M,2]).  depth is only asked for its shape."""
+    if not isinstance(depth, torch.Tensor) or depth.dim() != 3:
+        raise _lib.OmgHipError("depth must be a tensor [V,H,W]")
+    V = int(depth.shape[0])
+    h_views = np.ascontiguousarray(views, np.float64).reshape(-1, 16)
+    if len(h_views) != V:
+        raise _lib.OmgHipError(f"{len(h_views)} views but {V} images")
+    if not np.isfinite(h_views).all() or (h_views[:, :2] == 0).any():
+        raise _lib.OmgHipError("a view is not finite or has a focal length of zero")
+    if not (np.isfinite(float(band)) and np.isfinite(float(near))):
+        raise _lib.OmgHipError("band and near must be finite")
+    rec, nodes, begin = _fusion_volumes(volumes, state_begin)
+    M = len(rec)
+    h_range = np.asarray(view_range, np.int64).reshape(-1, 2)
+    if len(h_range) != M or (h_range < 0).any() or (h_range.sum(1) > V).any():
+        raise _lib.OmgHipError(f"view_range must be [{M},2] inside [0, {V}]")
+    return rec, nodes, begin, h_views, np.ascontiguousarray(h_range, np.int32)
+
+
+def carve_views(volumes, views, view_range, depth: torch.Tensor, band: float, near: float, state: "torch.Tensor | None" = None,
+                state_begin=None, merge: bool = False):
+    """The states (0 free, 1 surface, 2 unknown) of the nodes of M volumes from V depth views in ONE launch (omgx_carve_views;
+    fusion.carve_views is the specification: the same bytes) -> (state uint8 on the device, state_begin [M] int64 numpy): volume
+    m's node L at state[state_begin[m] + L].  volumes: what surface_records takes (the pool offset is not used here); views
+    [V,16] float64 on the host (fusion.view_rows); view_range [M,2] host integers (first view, count; ranges may overlap);
+    depth [V,H,W]: a contiguous float64 device tensor (render_depth's t), +inf as background.  state / state_begin: None -> a new
+    buffer that reaches to the end of the last volume, filled with 2 (unknown) where no volume lies, as the specification's; or
+    the caller's, written IN PLACE (elements outside every range are not touched).
+    merge: the flags start from what `state` holds, so that carving the views A and merging the views B equals carving both.
+    The host arguments are checked first, then the tensors: a refused call has touched nothing."""
+    from . import fusion as _fu
+    rec, nodes, begin, h_views, h_range = _carve_arguments(volumes, views, view_range, depth, band, near, state_begin)
+    if state is None and merge:
+        raise _lib.OmgHipError("merge needs the state of an earlier call")
+    _need(depth, torch.float64, "depth")
+    dev, vp = depth.device, C.c_void_p
+    (V, H, W), M = (int(d) for d in depth.shape), len(rec)
+    if state is None:
+        state = torch.full((max(int((begin + nodes).max()) if M else 0, 1),), _fu.UNKNOWN, dtype=torch.uint8, device=dev)
+    _need(state, torch.uint8, "state")
+    if state.device != dev:
+        raise _lib.OmgHipError(f"state must be on {dev}, got {state.device}")
+    with torch.cuda.device(dev):
+        d_rec, d_views, d_range, d_begin = _upload(rec, dev), _upload(h_views, dev), _upload(h_range, dev), _upload(begin, dev)
+        check(_lib.lib().omgx_carve_views(_ptr(d_rec) if M else None, C.cast(rec, vp) if M else None, M, _ptr(d_views) if V else None,
+                                          vp(h_views.ctypes.data) if V else None, V, _ptr(d_range) if M else None, vp(h_range.ctypes.data) if M else None,
+                                          _ptr(d_begin) if M else None, vp(begin.ctypes.data) if M else None, _ptr(depth) if V else None, H, W,
+                                          float(band), float(near), int(bool(merge)), _ptr(state), int(state.numel()), _stream()), "omgx_carve_views")
+        for t in (d_rec, d_views, d_range, d_begin):
+            t.record_stream(torch.cuda.current_stream(dev))
+    return state, begin
+
+
+def distance_transform(state: torch.Tensor, state_begin, volumes, radius: int, unknown_occupied: bool = True, out: "torch.Tensor | None" = None):
+    """The signed float32 volumes of M volumes' states in three launches (omgx_distance_transform; fusion.distance_transform is
+    the specification: the same bits) -> out: a contiguous float32 device tensor (the SDF pool, for instance) written IN PLACE
+    at every volume's element offset (the fifth field of its layout; the volumes must not overlap), or None -> a new buffer
+    that reaches to the end of the last volume, zero where no volume lies.  Volume m lies at out[offset : offset + X*Y*Z] as
+    [X,Y,Z].  The host arguments are checked first, then the tensors."""
+    radius = _fusion_radius(radius)
+    rec, nodes, begin = _fusion_volumes(volumes, state_begin)
+    _need(state, torch.uint8, "state")
+    dev, vp, l, M = state.device, C.c_void_p, _lib.lib(), len(rec)
+    if out is None:
+        out = torch.zeros(max([int(r.out_offset) + int(n) for r, n in zip(rec, nodes)], default=1), dtype=torch.float32, device=dev)
+    _need(out, torch.float32, "out")
+    if out.device != dev:
+        raise _lib.OmgHipError(f"out must be on {dev}, got {out.device}")
+    nbytes = int(l.omgx_distance_transform_workspace_bytes(C.cast(rec, vp) if M else None, M, radius))
+    check(min(nbytes, 0), "omgx_distance_transform_workspace_bytes")
+    with torch.cuda.device(dev):
+        ws = torch.empty(max(nbytes // 4, 1), dtype=torch.int32, device=dev)
+        d_rec, d_begin = _upload(rec, dev), _upload(begin, dev)
+        check(l.omgx_distance_transform(_ptr(state), int(state.numel()), _ptr(d_begin) if M else None, vp(begin.ctypes.data) if M else None,
+                                        _ptr(d_rec) if M else None, C.cast(rec, vp) if M else None, M, radius, int(bool(unknown_occupied)), _ptr(ws),
+                                        _ptr(out), int(out.numel()), _stream()), "omgx_distance_transform")
+        for t in (ws, d_rec, d_begin):
+            t.record_stream(torch.cuda.current_stream(dev))
+    return out
+
+
+def fuse_views(volumes, views, view_range, depth: torch.Tensor, band: float, near: float, radius: int, unknown_occupied: bool = True,
+               out: "torch.Tensor | None" = None):
+    """carve_views and distance_transform for M volumes, four launches in all (fusion.fuse_views is the specification) -> out,
+    as distance_transform returns it.  The radius is checked before the carve launch."""
+    radius = _fusion_radius(radius)
+    state, begin = carve_views(volumes, views, view_range, depth, band, near)
+    return distance_transform(state, begin, volumes, radius, unknown_occupied, out)
 
 
 class RayBatch:
