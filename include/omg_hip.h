@@ -1016,6 +1016,68 @@ int omgx_distance_transform(const uint8_t* state, int64_t state_elems, const int
                             int32_t unknown_occupied, void* workspace, float* pool, int64_t pool_elems, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * (18) omgx_label_components, omgx_component_records, omgx_component_states: carved states to objects
+ * The reference tells the target from the obstacles by the simulator's instance labels ("non-target points only",
+ * omg/core.py:849-851); a depth sensor gives none.  Here the states that omgx_carve_views writes are split into objects: the
+ * connected components of the foreground nodes of M volumes (a ragged batch), a record per component, and per pick a cropped
+ * state volume that omgx_distance_transform turns into a signed volume in the pool.  omg-planner_amd/segmentation.py
+ * (label_components, component_records, component_states) is the specification.  Integers only, no float arithmetic; every
+ * array equals the specification's exactly, and no result depends on the order in which atomics arrive.  New entry points only:
+ * omgx_abi_version() stays 14.
+ *
+ * Volumes, state_begin and the linear index L are those of (17), first_workgroup = the prefix table with
+ * OMGX_SEGMENT_NODES_PER_WORKGROUP nodes per workgroup; out_offset and the vert / face fields are ignored.
+ *   foreground       select bit 0: nodes of state 1 (SURFACE); bit 1: nodes that are neither 0 nor 1; select = 1, 2 or 3
+ *   neighbours       connectivity 6: the nodes that differ by 1 along one axis; 18: along one or two; 26: along up to three
+ *   label            -1 for background nodes and for the elements of `labels` outside every volume's range; otherwise the rank
+ *                    0, 1, ... of the node's component among the components of its own volume, ordered by their smallest L.
+ *                    Components never join across volumes, however the states lie in the array.
+ *   record           8 int32 per component: (count, first L, lo_i, lo_j, lo_k, hi_i, hi_j, hi_k), the box inclusive; volume
+ *                    m's components are the rows comp_begin[m] .. comp_begin[m+1] of `records`, in rank order
+ *   pick             8 int32: (source volume m, i0, j0, k0, component c as a row of `records`, mode, 0, 0).  Node (a,b,c) of
+ *                    output volume k reads source node (i0+a, j0+b, k0+c); the offsets may be negative.  A source node outside
+ *                    the source grid gives 0 (FREE).  mode 0, the target alone: 1 if the source's label is component c; 2 if the
+ *                    source's state is neither 0 nor 1 and the node lies inside c's box; otherwise 0.  mode 1, everything but
+ *                    the target: 0 in those two cases, otherwise the source's state unchanged.
+ *
+ * omgx_label_components: a union by label equivalence on one int32 link per node, in always the same launches, with no download:
+ *   labels are filled with -1; a workgroup unions the backward neighbours (3, 9 or 13 with a smaller L) inside its own run of
+ *   256 nodes in LDS (1 024 bytes); a second launch unions across the runs' borders in global memory, touching the links only with
+ *   atomic minima and relaxed agent-scope atomic loads; the nodes that are their own parent are counted per workgroup and scanned
+ *   per volume; a last launch follows every node's links with plain loads and writes its root's rank.  counts [M] int32 (device):
+ *   the volumes' numbers of components.  A link only ever moves to a smaller index, so find and union end after a bounded
+ *   number of turns whatever other workgroups do; nothing spins or waits, the stream is the only barrier.  `workspace`:
+ *   omgx_label_workspace_bytes bytes (1 284 per workgroup: links, totals, ranks).
+ * omgx_component_records: after the host has read `counts` and laid out comp_begin [M+1] int64 (from 0).  One launch fills the
+ *   rows, one adds every node with integer atomics (add on the count, min / max on the rest; lanes of a wave that share a
+ *   component are reduced first).  Rows at or beyond comp_begin[m+1] are not written.
+ * omgx_component_states: one thread per node of the K output volumes (omgx_mesh records with their own prefix table), output
+ *   k's node L at out_state[out_begin[k] + L]; `records` (num_records rows) and `labels` as the two calls above left them.
+ * `volumes`, `state_begin`, `comp_begin`, `picks`, `out_volumes`, `out_begin` are on the device, h_* the same on the host; ALL
+ * checks are made on the host copies before any HIP call.  OMGX_ERR_INVALID: a null pointer (with M == 0, or K == 0, everything
+ * may be NULL; records with comp_begin[M] == 0), a negative count, select outside 1..3, a connectivity other than 6, 18, 26, a
+ * bad volume record as in (17) (dims, delta, origin, sample_offset, first_workgroup), a state or output range outside its array,
+ * two that overlap, a comp_begin that does not start at 0 or decreases, record_cap or num_records below comp_begin[M], a pick
+ * whose volume is outside [0, M) or whose component is not a row of that volume, a mode other than 0 or 1, padding that is not
+ * zero.  OMGX_ERR_UNSUPPORTED: more than 2^31 - 1 nodes in one volume, workgroups in all, or components.  M == 0 (K == 0 for
+ * omgx_component_states) returns OMGX_OK and launches nothing.
+ * ------------------------------------------------------------------------------------------- */
+#define OMGX_SEGMENT_NODES_PER_WORKGROUP 256
+int64_t omgx_label_workspace_bytes(const omgx_mesh* h_volumes, int32_t num_volumes);
+int omgx_label_components(const uint8_t* state, int64_t state_elems, const int64_t* state_begin, const int64_t* h_state_begin,
+                          const omgx_mesh* volumes, const omgx_mesh* h_volumes, int32_t num_volumes, int32_t select,
+                          int32_t connectivity, void* workspace, int32_t* labels, int32_t* counts, void* stream);
+int omgx_component_records(const int32_t* labels, int64_t state_elems, const int64_t* state_begin, const int64_t* h_state_begin,
+                           const omgx_mesh* volumes, const omgx_mesh* h_volumes, int32_t num_volumes, const int64_t* comp_begin,
+                           const int64_t* h_comp_begin, int32_t* records, int64_t record_cap, void* stream);
+int omgx_component_states(const uint8_t* state, int64_t state_elems, const int64_t* state_begin, const int64_t* h_state_begin,
+                          const omgx_mesh* volumes, const omgx_mesh* h_volumes, int32_t num_volumes, const int32_t* labels,
+                          const int64_t* comp_begin, const int64_t* h_comp_begin, const int32_t* records, int64_t num_records,
+                          const int32_t* picks, const int32_t* h_picks, const omgx_mesh* out_volumes,
+                          const omgx_mesh* h_out_volumes, int32_t num_picks, const int64_t* out_begin, const int64_t* h_out_begin,
+                          uint8_t* out_state, int64_t out_elems, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Diagnostics
  * ------------------------------------------------------------------------------------------- */
 const char* omgx_last_error(void); /* thread-local text of the last OMGX_ERR_LAUNCH               */

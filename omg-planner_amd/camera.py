@@ -228,6 +228,30 @@ class Observation:
         return table.fuse_obstacles(pairs, depth, views, np.stack([np.arange(len(pairs)), np.ones(len(pairs), np.int64)], -1), layouts, band,
                                     near, reach, unknown_occupied, free_mask)
 
+    def segment_obstacles(self, table, target_pairs, obstacle_pairs, layouts, band: float, near: float, reach: float, seeds,
+                          min_nodes: int, connectivity: int = 6, margin=None, free_mask=None):
+        """The target's and the obstacles' volumes of an ops.DeviceScenes from this observation's depth images ALONE
+        (ops.DeviceScenes.segment_obstacles, which documents the arguments): no instance image is read.  Pair n is seen by the
+        camera of its own scene through the view row of obstacle_pairs[n] (view_rows); the layout, the seed and the target's
+        volume are in that object's frame, so target_pairs[n] should stand at the same pose.  free_mask: bool [n,H,W], the pixels
+        that count as background (explained_mask of the known objects: the support).  -> (radius, records [n,8], Components)."""
+        import torch
+        obstacle_pairs = np.asarray(obstacle_pairs, np.int64).reshape(-1, 2)
+        views = self.view_rows(table, obstacle_pairs)
+        depth = self.t[torch.from_numpy(obstacle_pairs[:, 0].copy()).to(self.t.device)].contiguous()
+        ranges = np.stack([np.arange(len(obstacle_pairs)), np.ones(len(obstacle_pairs), np.int64)], -1)
+        return table.segment_obstacles(target_pairs, obstacle_pairs, depth, views, ranges, layouts, band, near, reach, seeds, min_nodes,
+                                       connectivity, margin, free_mask)
+
+
+def explained_mask(t, t_known, tol: float):
+    """The pixels of the depth images t that the known objects explain: t_known (their rendering, +inf where they are not seen)
+    is finite and t >= t_known - tol.  Torch, elementwise, any shape -> bool.  As the free_mask of segment_obstacles it takes
+    the support surface (observe_table on the table and plane rows) out before carving, so that objects standing on it are
+    separate components; an object in front of the support stays (its depth is smaller by more than tol)."""
+    import torch
+    return torch.isfinite(t_known) & (t >= t_known - float(tol))
+
 
 def observe_scenes(scenes, meshes, cam_from_world, intrinsics, H: int, W: int, cull: bool = True, device="cuda:0") -> Observation:
     """Depth and instance images of S scenes.Scene on the device, one launch (scene_records, ops.CameraBatch, ops.render_depth).

@@ -124,18 +124,6 @@ __global__ __launch_bounds__(FUSE_BLOCK) void k_fusion_slab(const omgx_mesh* __r
     }
 }
 
-// The state ranges of the volumes: inside [0, state_elems), no two overlapping -> OMGX_OK or OMGX_ERR_INVALID.  (node counts
-// above 2^31 - 1 are the caller's OMGX_ERR_UNSUPPORTED; their ranges are checked all the same)
-int check_state_ranges(const omgx_mesh* h_volumes, int32_t M, const int64_t* h_state_begin, int64_t state_elems) {
-    std::vector<std::pair<int64_t, int64_t>> r;
-    for (int32_t m = 0; m < M; ++m) {
-        const int64_t nodes = mesh_node_count(h_volumes[m]), begin = h_state_begin[m];
-        if (begin < 0 || nodes > state_elems || begin > state_elems - nodes) return OMGX_ERR_INVALID;
-        r.emplace_back(begin, nodes);
-    }
-    return mesh_ranges_overlap(r) ? OMGX_ERR_INVALID : OMGX_OK;
-}
-
 int check_radius(int32_t radius) { return radius < 1 ? OMGX_ERR_INVALID : radius > OMGX_FUSION_MAX_RADIUS ? OMGX_ERR_UNSUPPORTED : OMGX_OK; }
 
 // One of the y / x passes over all volumes: blockIdx.y holds at most 65535 volumes, so one launch per that many (one, in
@@ -186,7 +174,7 @@ extern "C" int omgx_carve_views(const omgx_mesh* volumes, const omgx_mesh* h_vol
         const int64_t first = h_view_range[2 * m], count = h_view_range[2 * m + 1];
         if (first < 0 || count < 0 || first + count > V) return OMGX_ERR_INVALID;
     }
-    if (check_state_ranges(h_volumes, M, h_state_begin, state_elems) != OMGX_OK) return OMGX_ERR_INVALID;
+    if (mesh_check_state_ranges(h_volumes, M, h_state_begin, state_elems) != OMGX_OK) return OMGX_ERR_INVALID;
     if (status != OMGX_OK || big_images) return OMGX_ERR_UNSUPPORTED;
     hipLaunchKernelGGL(k_carve_views, dim3((unsigned)wg), dim3(FUSE_BLOCK), 0, (hipStream_t)stream, volumes, (int)M, views, view_range, state_begin,
                        depth, (int)H, (int)W, band, near, (int)merge, state);
@@ -213,7 +201,7 @@ extern "C" int omgx_distance_transform(const uint8_t* state, int64_t state_elems
     int64_t wg = 0;
     const int status = mesh_check_volumes(h_volumes, M, pool_elems, FUSE_BLOCK, &wg);
     if (status == OMGX_ERR_INVALID) return status;
-    if (check_state_ranges(h_volumes, M, h_state_begin, state_elems) != OMGX_OK) return OMGX_ERR_INVALID;
+    if (mesh_check_state_ranges(h_volumes, M, h_state_begin, state_elems) != OMGX_OK) return OMGX_ERR_INVALID;
     std::vector<std::pair<int64_t, int64_t>> in_pool;
     for (int32_t m = 0; m < M; ++m) in_pool.emplace_back(h_volumes[m].out_offset, mesh_node_count(h_volumes[m]));
     if (mesh_ranges_overlap(in_pool)) return OMGX_ERR_INVALID;

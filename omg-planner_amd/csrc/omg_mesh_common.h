@@ -1,6 +1,6 @@
 // omg_mesh_common.h — what the translation units that take omgx_mesh records share: the face tile that k_mesh_sdf and
 // k_mesh_raycast stage in LDS (omg_mesh_sdf.hip, omg_grasp.hip), the checks on one host omgx_mesh record (include/omg_hip.h
-// sections 12 and 13) and on a batch of volumes (omg_surface.hip, omg_fusion.hip: sections 16 and 17).
+// sections 12 and 13) and on a batch of volumes (omg_surface.hip, omg_fusion.hip, omg_segment.hip: sections 16 to 18).
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -81,4 +81,16 @@ static inline bool mesh_ranges_overlap(std::vector<std::pair<int64_t, int64_t>>&
         end = x.first + x.second;
     }
     return false;
+}
+
+// The state ranges of the volumes: inside [0, state_elems), no two overlapping -> OMGX_OK or OMGX_ERR_INVALID.  (node counts
+// above 2^31 - 1 are the caller's OMGX_ERR_UNSUPPORTED; their ranges are checked all the same)
+static inline int mesh_check_state_ranges(const omgx_mesh* h_volumes, int32_t M, const int64_t* h_state_begin, int64_t state_elems) {
+    std::vector<std::pair<int64_t, int64_t>> r;
+    for (int32_t m = 0; m < M; ++m) {
+        const int64_t nodes = mesh_node_count(h_volumes[m]), begin = h_state_begin[m];
+        if (begin < 0 || nodes > state_elems || begin > state_elems - nodes) return OMGX_ERR_INVALID;
+        r.emplace_back(begin, nodes);
+    }
+    return mesh_ranges_overlap(r) ? OMGX_ERR_INVALID : OMGX_OK;
 }

@@ -526,6 +526,63 @@ class DeviceScenes:
             self.replace_grid(int(s), int(o), slot, origin, float(delta), fit="device")
         return radius
 
+    def segment_obstacles(self, target_pairs, obstacle_pairs, depth: torch.Tensor, views, view_range, layouts, band: float, near: float,
+                          reach: float, seeds, min_nodes: int, connectivity: int = 6, margin: "int | None" = None,
+                          free_mask: "torch.Tensor | None" = None):
+        """fuse_obstacles without labels: per scene n the layout (origin [3], delta, dims [3]: voxel centres, in the frame both of
+        the scene's pairs stand in) is carved from its views, the SURFACE nodes are labelled (label_components), the target is the
+        component nearest to seeds[n] (a point of the layout's frame, converted to index units on the host;
+        segmentation.pick_component among the components of at least min_nodes nodes), its crop in mode 0 becomes the volume of
+        target_pairs[n] and the whole layout in mode 1 the volume of obstacle_pairs[n], both through grid_slot and
+        replace_grid(fit="device").  One carve launch, one labelling and one set of crop and transform launches for all scenes;
+        two small downloads (counts, records).  margin: nodes around the target's box (default radius + 1, so that the target's
+        zero level closes inside its crop); free_mask as fuse_obstacles takes it (camera.explained_mask: the support).
+        -> (radius, the chosen records [n,8] int32, the Components).  segmentation.segment_views is the specification."""
+        from . import fusion as _fu, segmentation as _sg
+        self._changing(volumes=True)
+        tp, op = np.asarray(target_pairs, np.int64).reshape(-1, 2), np.asarray(obstacle_pairs, np.int64).reshape(-1, 2)
+        layouts = list(layouts)
+        n = len(layouts)
+        seeds = np.asarray(seeds, np.float64).reshape(-1, 3)
+        if not n or len(tp) != n or len(op) != n or len(seeds) != n:
+            raise _lib.OmgHipError(f"{n} layouts need as many target pairs, obstacle pairs and seeds, and at least one")
+        if len({self._index(int(s), int(o)) for s, o in np.concatenate([tp, op])}) != 2 * n:
+            raise _lib.OmgHipError("a (scene, obj) pair is named twice")
+        if not (np.isfinite(float(reach)) and float(reach) >= 0):
+            raise _lib.OmgHipError("reach must be finite and not negative")
+        if not np.isfinite(seeds).all() or int(min_nodes) < 1 or (margin is not None and int(margin) < 0):
+            raise _lib.OmgHipError("seeds must be finite, min_nodes at least 1 and margin not negative")
+        _segment_arguments(1, connectivity)
+        volumes = [(origin, delta, "centre", dims) for origin, delta, dims in layouts]
+        _carve_arguments(volumes, views, view_range, depth, band, near, None)
+        radius = _fusion_radius(max(_fu.obstacle_radius(reach, float(delta)) for _, delta, _ in layouts))
+        margin = radius + 1 if margin is None else int(margin)
+        _need(depth, torch.float64, "depth")
+        if free_mask is not None:
+            if (not isinstance(free_mask, torch.Tensor) or free_mask.dtype != torch.bool or free_mask.shape != depth.shape
+                    or free_mask.device != depth.device):
+                raise _lib.OmgHipError("free_mask must be a bool tensor of depth's shape, on its device")
+            depth = torch.where(free_mask, torch.full_like(depth, float("inf")), depth).contiguous()
+        state, begin = carve_views(volumes, views, view_range, depth, band, near)
+        comps = label_components(state, begin, volumes, 1, connectivity)
+        try:  # (a scene without a component of min_nodes nodes is refused here: no slot has been offered yet)
+            ranks = [_sg.pick_component(comps.of(m), _sg.point_to_index(volumes[m], seeds[m]), min_nodes) for m in range(n)]
+        except ValueError as e:
+            raise _lib.OmgHipError(str(e)) from None
+        rows = [int(comps.comp_begin[m]) + ranks[m] for m in range(n)]
+        crops = [_sg.crop_layout(volumes[m], comps.records[rows[m]], margin) for m in range(n)]
+        outs, picks, slots = [], [], []
+        for m in range(n):
+            for (s, o), (origin, delta, dims, first), mode in ((tp[m], crops[m], 0), (op[m], tuple(layouts[m]) + ((0, 0, 0),), 1)):
+                slot = self.grid_slot(int(s), int(o), tuple(int(d) for d in dims))
+                slots.append((int(s), int(o), slot, origin, float(delta)))
+                outs.append((origin, delta, "centre", dims, (slot.data_ptr() - self.pool.data_ptr()) // 4))
+                picks.append((m,) + tuple(first) + (rows[m], mode, 0, 0))
+        component_volumes(state, comps, picks, outs, radius, True, out=self.pool)
+        for s, o, slot, origin, delta in slots:
+            self.replace_grid(s, o, slot, origin, delta, fit="device")
+        return radius, comps.records[rows].copy(), comps
+
     def sync_host(self) -> np.ndarray:
         """Bring the host mirror of the records up to date with the device (one small copy; tests, oracle comparisons)."""
         self.host_objects[:] = self.objects.cpu().numpy().view(self.host_objects.dtype)  # in place: scene ranges share the mirror
@@ -1422,6 +1479,123 @@ def fuse_views(volumes, views, view_range, depth: torch.Tensor, band: float, nea
     radius = _fusion_radius(radius)
     state, begin = carve_views(volumes, views, view_range, depth, band, near)
     return distance_transform(state, begin, volumes, radius, unknown_occupied, out)
+
+
+class Components:
+    """What label_components returns: labels (int32 on the device, one per state element), counts [M] and comp_begin [M+1]
+    (host int64), records [C,8] (host int32; the same rows on the device as d_records), and the launch's volumes (rec) and
+    state_begin, which component_states takes again."""
+
+    def __init__(self, labels, counts, comp_begin, records, d_records, rec, begin, select, connectivity):
+        self.labels, self.counts, self.comp_begin, self.records, self.d_records = labels, counts, comp_begin, records, d_records
+        self.rec, self.begin, self.select, self.connectivity = rec, begin, select, connectivity
+
+    def of(self, m: int) -> np.ndarray:
+        """The records of volume m, in rank order."""
+        return self.records[int(self.comp_begin[m]): int(self.comp_begin[m + 1])]
+
+
+def _segment_arguments(select, connectivity):
+    from . import segmentation as _sg
+    if select not in (1, 2, 3):
+        raise _lib.OmgHipError(f"select must be 1, 2 or 3, got {select!r}")
+    if connectivity not in _sg.CONNECTIVITIES:
+        raise _lib.OmgHipError(f"connectivity must be 6, 18 or 26, got {connectivity!r}")
+    return int(select), int(connectivity)
+
+
+def label_components(state: torch.Tensor, state_begin, volumes, select: int = 1, connectivity: int = 6) -> Components:
+    """The connected components of the foreground nodes of M volumes' states (carve_views' array and offsets), on the device
+    (omgx_label_components, omgx_component_records; segmentation.label_components / component_records are the specification: the
+    same integers) -> Components.  select bit 0: SURFACE nodes, bit 1: nodes that are neither FREE nor SURFACE; connectivity 6,
+    18 or 26.  The same launches whatever the states hold; ONE download of the counts and one of the records.  The host
+    arguments are checked first, then the tensor."""
+    select, connectivity = _segment_arguments(select, connectivity)
+    rec, nodes, begin = _fusion_volumes(volumes, state_begin)
+    _need(state, torch.uint8, "state")
+    dev, vp, l, M = state.device, C.c_void_p, _lib.lib(), len(rec)
+    elems = int(state.numel())
+    nbytes = int(l.omgx_label_workspace_bytes(C.cast(rec, vp) if M else None, M))
+    check(min(nbytes, 0), "omgx_label_workspace_bytes")
+    with torch.cuda.device(dev):
+        labels = torch.full((elems,), -1, dtype=torch.int32, device=dev) if M == 0 else torch.empty(elems, dtype=torch.int32, device=dev)
+        if M == 0:
+            return Components(labels, np.zeros(0, np.int64), np.zeros(1, np.int64), np.zeros((0, 8), np.int32),
+                              torch.empty((0, 8), dtype=torch.int32, device=dev), rec, begin, select, connectivity)
+        ws = torch.empty(max(nbytes // 4, 1), dtype=torch.int32, device=dev)
+        counts = torch.empty(M, dtype=torch.int32, device=dev)
+        d_rec, d_begin = _upload(rec, dev), _upload(begin, dev)
+        check(l.omgx_label_components(_ptr(state), elems, _ptr(d_begin), vp(begin.ctypes.data), _ptr(d_rec), C.cast(rec, vp), M, select, connectivity,
+                                      _ptr(ws), _ptr(labels), _ptr(counts), _stream()), "omgx_label_components")
+        h_counts = counts.cpu().numpy().astype(np.int64)
+        comp_begin = np.concatenate([[0], np.cumsum(h_counts)]).astype(np.int64)
+        total = int(comp_begin[-1])
+        d_records = torch.empty((total, 8), dtype=torch.int32, device=dev)
+        d_comp = _upload(comp_begin, dev)
+        check(l.omgx_component_records(_ptr(labels), elems, _ptr(d_begin), vp(begin.ctypes.data), _ptr(d_rec), C.cast(rec, vp), M, _ptr(d_comp),
+                                       vp(comp_begin.ctypes.data), _ptr(d_records) if total else None, total, _stream()), "omgx_component_records")
+        records = d_records.cpu().numpy()
+        for t in (ws, d_rec, d_begin, d_comp):
+            t.record_stream(torch.cuda.current_stream(dev))
+    return Components(labels, h_counts, comp_begin, records, d_records, rec, begin, select, connectivity)
+
+
+def _component_arguments(components, picks, out_volumes, out_begin):
+    """The host side of a component_states launch, checked before anything touches the device -> (picks int32 [K,8], the
+    output records, their node counts, out_begin int64 [K])."""
+    from . import segmentation as _sg
+    if not isinstance(components, Components):
+        raise _lib.OmgHipError("components must be what label_components returned")
+    try:
+        h_picks = np.ascontiguousarray(_sg.check_picks(picks, len(components.rec), components.comp_begin))
+    except ValueError as e:
+        raise _lib.OmgHipError(str(e)) from None
+    out_rec, out_nodes, ob = _fusion_volumes(out_volumes, out_begin)
+    if len(out_rec) != len(h_picks):
+        raise _lib.OmgHipError(f"{len(h_picks)} picks need as many output volumes, got {len(out_rec)}")
+    return h_picks, out_rec, out_nodes, ob
+
+
+def component_states(state: torch.Tensor, components: Components, picks, out_volumes, out_begin=None, out: "torch.Tensor | None" = None):
+    """The states of K cropped output volumes in ONE launch (omgx_component_states; segmentation.component_states is the
+    specification: the same bytes) -> (out_state uint8 on the device, out_begin [K] int64 numpy).  state: the array that
+    label_components labelled; picks [K,8] host integers (source volume, i0, j0, k0, component as a row of components.records,
+    mode 0 the target alone / 1 everything but the target, 0, 0); out_volumes: what surface_records takes, one per pick.
+    out / out_begin: None -> a new buffer, the outputs back to back, UNKNOWN where none lies; or the caller's, written IN PLACE."""
+    from . import fusion as _fu
+    h_picks, out_rec, out_nodes, ob = _component_arguments(components, picks, out_volumes, out_begin)
+    _need(state, torch.uint8, "state")
+    dev, vp, K, M = state.device, C.c_void_p, len(h_picks), len(components.rec)
+    if int(state.numel()) != int(components.labels.numel()) or components.labels.device != dev:
+        raise _lib.OmgHipError("state must be the array that label_components labelled")
+    with torch.cuda.device(dev):
+        if out is None:
+            out = torch.full((max(int((ob + out_nodes).max()) if K else 0, 1),), _fu.UNKNOWN, dtype=torch.uint8, device=dev)
+        _need(out, torch.uint8, "out")
+        if out.device != dev:
+            raise _lib.OmgHipError(f"out must be on {dev}, got {out.device}")
+        if K == 0:
+            return out, ob
+        rec, begin, comp_begin = components.rec, components.begin, components.comp_begin
+        d_rec, d_begin, d_comp, d_picks, d_out, d_ob = (_upload(a, dev) for a in (rec, begin, comp_begin, h_picks, out_rec, ob))
+        check(_lib.lib().omgx_component_states(_ptr(state), int(state.numel()), _ptr(d_begin), vp(begin.ctypes.data), _ptr(d_rec), C.cast(rec, vp), M,
+                                               _ptr(components.labels), _ptr(d_comp), vp(comp_begin.ctypes.data), _ptr(components.d_records),
+                                               int(components.d_records.shape[0]), _ptr(d_picks), vp(h_picks.ctypes.data), _ptr(d_out),
+                                               C.cast(out_rec, vp), K, _ptr(d_ob), vp(ob.ctypes.data), _ptr(out), int(out.numel()), _stream()),
+              "omgx_component_states")
+        for t in (d_rec, d_begin, d_comp, d_picks, d_out, d_ob):
+            t.record_stream(torch.cuda.current_stream(dev))
+    return out, ob
+
+
+def component_volumes(state: torch.Tensor, components: Components, picks, out_volumes, radius: int, unknown_occupied: bool = True,
+                      out: "torch.Tensor | None" = None):
+    """component_states, then distance_transform of the K cropped states: four launches -> out as distance_transform returns it
+    (output k at the element offset of its layout: the SDF pool, for instance).  The radius and the picks are checked before
+    the first launch."""
+    radius = _fusion_radius(radius)
+    cropped, ob = component_states(state, components, picks, out_volumes)
+    return distance_transform(cropped, ob, out_volumes, radius, unknown_occupied, out)
 
 
 class RayBatch:

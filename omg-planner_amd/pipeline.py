@@ -129,3 +129,33 @@ def plan_volumes(model, scenes, starts, cfg, level: float = 0.0, n_rays: int = 5
                                  max_grasps=max_grasps, targets=targets, device=dev, **grasp_kwargs)
     plans = plan_grasps(model, scenes, sets, starts, cfg, ol_alg=ol_alg, rng=rng, obj_coord=True, device=device, layout_scenes=layout_scenes)
     return plans, sets, meshes
+
+
+def plan_observed(model, scenes, obs, obstacles, layouts, band: float, near: float, reach: float, seeds, min_nodes: int, starts, cfg,
+                  connectivity: int = 6, margin=None, free_mask=None, device="cuda:0", **plan_kwargs):
+    """plan_volumes from depth images alone: no instance labels, no target volume from a file.  obs: a camera.Observation of the
+    S scenes (only its depth images and cameras are used); obstacles [S]: the object of each scene that stands for everything
+    observed, at the pose of the layout's frame, as the target (scene.target_idx) should be; layouts, band, near, reach, seeds,
+    min_nodes, connectivity, margin, free_mask: camera.Observation.segment_obstacles'.  A table built from the scenes is segmented
+    on the device, the two small volumes of every scene are downloaded into the scenes' SdfGrids (the target's crop, the layout
+    without the target), then plan_volumes unchanged (plan_kwargs: its other arguments).
+    -> (GraspPlans, grasp poses, meshes, the chosen records [S,8])."""
+    from . import fusion as _fu, scenes as _sc, segmentation as _sg
+    dev = torch.device(device)
+    S = len(scenes)
+    tp = [(s, int(scenes[s].target_idx)) for s in range(S)]
+    op = [(s, int(o)) for s, o in enumerate(obstacles)]
+    # room for every scene's two new volumes: the layout, and a crop that is at most the layout grown by the margin
+    grow = 2 * (max(_fu.obstacle_radius(reach, float(delta)) for _, delta, _ in layouts) + 1 if margin is None else int(margin))
+    reserve = sum(int(np.prod(dims)) + int(np.prod(np.asarray(dims, np.int64) + grow)) for _, _, dims in layouts)
+    table = ops.DeviceScenes.from_scenes(scenes, cfg.layer_kwargs(), device=dev, share_grids=False, reserve_voxels=reserve)
+    radius, records, _ = obs.segment_obstacles(table, tp, op, layouts, band, near, reach, seeds, min_nodes, connectivity, margin, free_mask)
+    host = table.sync_host()
+    for s, (origin, delta, dims) in enumerate(layouts):
+        crop = _sg.crop_layout((origin, delta), records[s], radius + 1 if margin is None else int(margin))
+        # (origins and delta as the host knows them in float64, not the records' float32 limits)
+        for (_, o), (org, n) in ((tp[s], (crop[0], crop[2])), (op[s], (np.asarray(origin, np.float64), tuple(int(d) for d in dims)))):
+            off = int(host[table._index(s, o)]["grid_offset"])
+            scenes[s].objects[o].sdf = _sc.SdfGrid(table.pool[off: off + int(np.prod(n))].view(n).cpu().numpy(), org, float(delta))
+    plans, sets, meshes = plan_volumes(model, scenes, starts, cfg, device=device, **plan_kwargs)
+    return plans, sets, meshes, records
