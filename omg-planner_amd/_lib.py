@@ -32,6 +32,8 @@ CAMERA_PIXELS_PER_WORKGROUP = _K["CAMERA_PIXELS_PER_WORKGROUP"]
 SURFACE_NODES_PER_WORKGROUP = _K["SURFACE_NODES_PER_WORKGROUP"]
 FUSION_NODES_PER_WORKGROUP, FUSION_MAX_RADIUS, FUSION_CHUNK = _K["FUSION_NODES_PER_WORKGROUP"], _K["FUSION_MAX_RADIUS"], _K["FUSION_CHUNK"]
 SEGMENT_NODES_PER_WORKGROUP = _K["SEGMENT_NODES_PER_WORKGROUP"]
+PLANE_PIXELS_PER_WORKGROUP, PLANE_STAGE_HYPOTHESES = _K["PLANE_PIXELS_PER_WORKGROUP"], _K["PLANE_STAGE_HYPOTHESES"]
+PLANE_MAX_HYPOTHESES, PLANE_NODES_PER_WORKGROUP = _K["PLANE_MAX_HYPOTHESES"], _K["PLANE_NODES_PER_WORKGROUP"]
 ALG = {"FTL": _K["ALG_FTL"], "FTC": _K["ALG_FTC"], "Exp": _K["ALG_EXP"], "MD": _K["ALG_MD"], "Proj": _K["ALG_PROJ"]}
 ABI_VERSION = 14  # omgx_abi_version() of the library this package was written against
 

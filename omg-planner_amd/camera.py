@@ -244,6 +244,44 @@ class Observation:
                                        connectivity, margin, free_mask)
 
 
+    def intrinsics(self) -> np.ndarray:
+        """[S,4] float64: fx, fy, cx, cy of every scene's camera, from the batch's host records."""
+        cams = self.batch.h_cameras
+        return np.stack([np.asarray(cams[k], np.float64) for k in ("fx", "fy", "cx", "cy")], -1)
+
+    def fit_supports(self, triples, tol: float, up_world=None, cos_min: float = -1.0, refine: int = 2, min_nn: float = 1e-10):
+        """The support of every scene from its depth image ALONE: one plane per scene fitted to self.t (ops.fit_planes, which
+        documents triples [S,K,3], tol, cos_min, refine and min_nn; planes.fit_planes is the specification), and the pixels on or
+        behind it (ops.plane_mask), which segment_obstacles takes as free_mask in place of explained_mask's rendering of a known
+        table.  up_world [3]: a direction of the world (the table's normal, roughly: gravity) that the plane's normal must agree
+        with to within cos_min; it is turned into every camera's frame on the host (the rows of world_from_cam, transposed).
+        -> (ops.PlaneFit, mask: bool [S,H,W] on the device).  The planes are in the cameras' frames: support_planes moves them."""
+        from . import ops
+        intr = self.intrinsics()
+        up = None
+        if up_world is not None:
+            u = np.asarray(up_world, np.float64).reshape(3)
+            up = np.stack([w.reshape(3, 4)[:, :3].T @ u for w in np.asarray(self.batch.h_cameras["world_from_cam"], np.float64)])
+        fit = ops.fit_planes(intr, self.t, triples, tol, up=up, cos_min=cos_min, min_nn=min_nn, refine=refine)
+        return fit, ops.plane_mask(intr, self.t, fit.planes, tol)
+
+    def support_planes(self, table, pairs, fit) -> np.ndarray:
+        """The fitted planes [n,4] in the frames of the (scene, obj) `pairs` of an ops.DeviceScenes (what
+        DeviceScenes.plane_obstacles takes): pair (s, o) gets the plane of scene s moved by planes.plane_to_frame with
+        obj_from_cam = inv(world_from_obj) @ world_from_cam, the object's pose from the table's host mirror.  A scene without
+        a plane is refused."""
+        from . import planes as _pl
+        cams, poses = self.batch.h_cameras, table_object_poses(table)
+        h_planes = np.asarray(fit.h_planes if hasattr(fit, "h_planes") else fit.planes, np.float64).reshape(-1, 4)
+        out = np.zeros((len(pairs), 4))
+        for m, (s, o) in enumerate(np.asarray(pairs, np.int64).reshape(-1, 2)):
+            if not _pl.has_plane(h_planes[s]):
+                raise ValueError(f"scene {s} has no fitted plane")
+            world_from_cam = np.vstack([np.asarray(cams["world_from_cam"][s], np.float64).reshape(3, 4), [0.0, 0.0, 0.0, 1.0]])
+            out[m] = _pl.plane_to_frame(h_planes[s], np.linalg.inv(poses[table._index(int(s), int(o))]) @ world_from_cam)
+        return out
+
+
 def explained_mask(t, t_known, tol: float):
     """The pixels of the depth images t that the known objects explain: t_known (their rendering, +inf where they are not seen)
     is finite and t >= t_known - tol.  Torch, elementwise, any shape -> bool.  As the free_mask of segment_obstacles it takes

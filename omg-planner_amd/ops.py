@@ -583,6 +583,30 @@ class DeviceScenes:
             self.replace_grid(s, o, slot, origin, delta, fit="device")
         return radius, comps.records[rows].copy(), comps
 
+    def plane_obstacles(self, pairs, planes, layouts) -> None:
+        """The half-space volumes of fitted supports as the volumes of the (scene, obj) `pairs`, written straight into the pool:
+        a support that plane_mask took out of the depth images would otherwise be space the planner believes is free.  planes
+        [n,4] on the host, each in its object's own frame (camera.Observation.support_planes), the normal towards the free side;
+        layouts: one (origin [3], delta, dims [3]) per pair, voxel centres, in the object's frame.  grid_slot, ONE launch
+        (plane_volumes), then replace_grid(fit="device") object by object, as fuse_obstacles does it; everything that can be
+        refused is refused before a slot is offered."""
+        self._changing(volumes=True)
+        pairs = np.asarray(pairs, np.int64).reshape(-1, 2)
+        layouts = list(layouts)
+        if len(layouts) != len(pairs) or not len(pairs):
+            raise _lib.OmgHipError(f"{len(pairs)} pairs need as many layouts, and at least one")
+        if len({self._index(int(s), int(o)) for s, o in pairs}) != len(pairs):
+            raise _lib.OmgHipError("a (scene, obj) pair is named twice")
+        _plane_volume_arguments([(origin, delta, "centre", dims) for origin, delta, dims in layouts], planes)
+        slots, volumes = [], []
+        for (s, o), (origin, delta, dims) in zip(pairs, layouts):
+            slot = self.grid_slot(int(s), int(o), tuple(int(d) for d in dims))
+            slots.append(slot)
+            volumes.append((origin, delta, "centre", dims, (slot.data_ptr() - self.pool.data_ptr()) // 4))
+        plane_volumes(volumes, planes, out=self.pool)
+        for (s, o), (origin, delta, _), slot in zip(pairs, layouts, slots):
+            self.replace_grid(int(s), int(o), slot, origin, float(delta), fit="device")
+
     def sync_host(self) -> np.ndarray:
         """Bring the host mirror of the records up to date with the device (one small copy; tests, oracle comparisons)."""
         self.host_objects[:] = self.objects.cpu().numpy().view(self.host_objects.dtype)  # in place: scene ranges share the mirror
@@ -1596,6 +1620,198 @@ def component_volumes(state: torch.Tensor, components: Components, picks, out_vo
     radius = _fusion_radius(radius)
     cropped, ob = component_states(state, components, picks, out_volumes)
     return distance_transform(cropped, ob, out_volumes, radius, unknown_occupied, out)
+
+
+class PlaneFit:
+    """What fit_planes returns.  On the device: planes [V,4] float64 (the final planes, four zeros without one), hypotheses
+    [V,K,4], counts [V,K] int32 (-1: void), best [V] int32.  On the host (numpy): h_planes [V,4], h_best [V], ransac_counts [V]
+    (the best hypothesis' count, 0 without), inliers [V] int32 (at the final plane), status [V] (planes.NO_PLANE, RANSAC_ONLY,
+    REFINED), anchors [V,3]."""
+
+    def __init__(self, **fields):
+        self.__dict__.update(fields)
+
+
+def _plane_images(intrinsics, depth, skip, tol):
+    """The host side of a launch over depth images, checked before anything touches the device -> (intrinsics float64 [V,4],
+    V, H, W, tol).  depth and skip are only asked for their shape, type and place."""
+    if not isinstance(depth, torch.Tensor) or depth.dim() != 3:
+        raise _lib.OmgHipError("depth must be a tensor [V,H,W]")
+    V, H, W = (int(d) for d in depth.shape)
+    k = np.asarray(intrinsics, np.float64)
+    k = np.ascontiguousarray(np.broadcast_to(k, (V, 4)) if k.ndim == 1 and k.size == 4 else k.reshape(-1, 4))
+    if len(k) != V or not np.isfinite(k).all() or (k[:, :2] == 0).any():
+        raise _lib.OmgHipError(f"intrinsics must be [{V},4] (fx, fy, cx, cy), finite, the focal lengths not zero")
+    if V and (H < 1 or W < 1):
+        raise _lib.OmgHipError("the images are empty")
+    tol = float(tol)
+    if not (np.isfinite(tol) and tol >= 0):
+        raise _lib.OmgHipError("tol must be finite and not negative")
+    if skip is not None and (not isinstance(skip, torch.Tensor) or skip.dtype not in (torch.bool, torch.uint8) or skip.shape != depth.shape
+                             or skip.device != depth.device):
+        raise _lib.OmgHipError("skip must be a bool tensor of depth's shape, on its device")
+    return k, V, H, W, tol
+
+
+def _plane_skip(skip):
+    return None if skip is None else (skip.contiguous().view(torch.uint8) if skip.dtype == torch.bool else skip.contiguous())
+
+
+def _plane_rows(planes, V, dev, name="planes", cols=4):
+    """planes [V,4] (or anchors [V,3]) as a contiguous float64 device tensor: a tensor is checked, a host array uploaded."""
+    if isinstance(planes, torch.Tensor):
+        _need(planes, torch.float64, name)
+        if planes.device != dev or tuple(planes.shape) != (V, cols):
+            raise _lib.OmgHipError(f"{name} must be [{V},{cols}] on {dev}, got {tuple(planes.shape)} on {planes.device}")
+        return planes
+    h = np.ascontiguousarray(planes, np.float64)
+    if h.shape != (V, cols):
+        raise _lib.OmgHipError(f"{name} must be [{V},{cols}], got {h.shape}")
+    return _upload(h, dev)
+
+
+def plane_ransac(intrinsics, depth: torch.Tensor, triples, tol: float, min_nn: float = 1e-10, skip: "torch.Tensor | None" = None, up=None,
+                 cos_min: float = -1.0):
+    """One plane per pixel triple, its inlier count, and the best of every view, in three launches (omgx_plane_ransac;
+    planes.ransac is the specification: the same bits) -> (planes [V,K,4] float64, counts [V,K] int32, best [V] int32,
+    best_planes [V,4], anchors [V,3]) on depth's device.  intrinsics [4] or [V,4] and triples [V,K,3] (planes.draw_triples) are
+    host arrays, up [3] or [V,3] too; depth [V,H,W]: a contiguous float64 device tensor; skip: a bool tensor of its shape.  The
+    host arguments are checked first, then the tensors."""
+    k, V, H, W, tol = _plane_images(intrinsics, depth, skip, tol)
+    h_tri = np.asarray(triples)
+    if h_tri.ndim != 3 or h_tri.shape[0] != V or h_tri.shape[2] != 3 or not np.issubdtype(h_tri.dtype, np.integer):
+        raise _lib.OmgHipError(f"triples must be integers [{V},K,3]")
+    K = int(h_tri.shape[1])
+    if not 1 <= K <= _lib.PLANE_MAX_HYPOTHESES:
+        raise _lib.OmgHipError(f"K must lie in [1, {_lib.PLANE_MAX_HYPOTHESES}], got {K}")
+    if V and (h_tri.min() < 0 or h_tri.max() >= H * W):
+        raise _lib.OmgHipError(f"a triple names a pixel outside [0, {H * W})")
+    h_tri = np.ascontiguousarray(h_tri, np.int32)
+    min_nn, cos_min = float(min_nn), float(cos_min)
+    if not (np.isfinite(min_nn) and min_nn >= 0) or not -1.0 <= cos_min <= 1.0:
+        raise _lib.OmgHipError("min_nn must be finite and not negative and cos_min lie in [-1, 1]")
+    h_up = None
+    if up is not None:
+        h_up = np.asarray(up, np.float64)
+        h_up = np.ascontiguousarray(np.broadcast_to(h_up, (V, 3)) if h_up.ndim == 1 and h_up.size == 3 else h_up.reshape(-1, 3))
+        if len(h_up) != V or not np.isfinite(h_up).all():
+            raise _lib.OmgHipError(f"up must be [{V},3] and finite")
+    _need(depth, torch.float64, "depth")
+    dev, vp = depth.device, C.c_void_p
+    with torch.cuda.device(dev):
+        planes = torch.empty((V, K, 4), dtype=torch.float64, device=dev)
+        counts = torch.empty((V, K), dtype=torch.int32, device=dev)
+        best = torch.empty(V, dtype=torch.int32, device=dev)
+        best_planes, anchors = torch.empty((V, 4), dtype=torch.float64, device=dev), torch.empty((V, 3), dtype=torch.float64, device=dev)
+        if V == 0:
+            return planes, counts, best, best_planes, anchors
+        d_k, d_tri, d_skip = _upload(k, dev), _upload(h_tri, dev), _plane_skip(skip)
+        d_up = None if h_up is None else _upload(h_up, dev)
+        check(_lib.lib().omgx_plane_ransac(_ptr(d_k), vp(k.ctypes.data), _ptr(depth), _ptr(d_skip), V, H, W, _ptr(d_tri), vp(h_tri.ctypes.data), K, tol,
+                                           min_nn, _ptr(d_up), cos_min, _ptr(planes), _ptr(counts), _ptr(best), _ptr(best_planes), _ptr(anchors),
+                                           _stream()), "omgx_plane_ransac")
+        for t in (d_k, d_tri, d_skip, d_up):
+            if t is not None:
+                t.record_stream(torch.cuda.current_stream(dev))
+    return planes, counts, best, best_planes, anchors
+
+
+def plane_moments(intrinsics, depth: torch.Tensor, planes, anchors, tol: float, skip: "torch.Tensor | None" = None):
+    """The inliers' count [V] int32 and sums [V,9] float64 about the anchors, in two launches (omgx_plane_moments;
+    planes.moments is the specification: the same bits), on depth's device.  planes [V,4] and anchors [V,3]: float64 device
+    tensors, or host arrays that are uploaded."""
+    k, V, H, W, tol = _plane_images(intrinsics, depth, skip, tol)
+    _need(depth, torch.float64, "depth")
+    dev, vp, l = depth.device, C.c_void_p, _lib.lib()
+    with torch.cuda.device(dev):
+        d_planes, d_anchors = _plane_rows(planes, V, dev), _plane_rows(anchors, V, dev, "anchors", 3)
+        count, sums = torch.empty(V, dtype=torch.int32, device=dev), torch.empty((V, 9), dtype=torch.float64, device=dev)
+        if V == 0:
+            return count, sums
+        nbytes = int(l.omgx_plane_workspace_bytes(V, H, W))
+        check(min(nbytes, 0), "omgx_plane_workspace_bytes")
+        ws = torch.empty(max(nbytes // 8, 1), dtype=torch.float64, device=dev)
+        d_k, d_skip = _upload(k, dev), _plane_skip(skip)
+        check(l.omgx_plane_moments(_ptr(d_k), vp(k.ctypes.data), _ptr(depth), _ptr(d_skip), V, H, W, _ptr(d_planes), _ptr(d_anchors), tol, _ptr(ws),
+                                   _ptr(count), _ptr(sums), _stream()), "omgx_plane_moments")
+        for t in (ws, d_k, d_skip, d_planes, d_anchors):
+            if t is not None:
+                t.record_stream(torch.cuda.current_stream(dev))
+    return count, sums
+
+
+def fit_planes(intrinsics, depth: torch.Tensor, triples, tol: float, skip: "torch.Tensor | None" = None, up=None, cos_min: float = -1.0,
+               min_nn: float = 1e-10, refine: int = 2) -> PlaneFit:
+    """The dominant plane of every depth view (planes.fit_planes is the specification, and its host half, refine_plane, is the
+    code that runs here too: the same planes bit for bit) -> PlaneFit.  plane_ransac, ONE small download of the best planes
+    (with the counts), then per refinement round plane_moments at the current planes, a download of its 10 numbers per view and
+    an upload of the refined planes; a last moment pass counts the inliers of the final planes.  Arguments: plane_ransac's."""
+    from . import planes as _pl
+    if int(refine) < 0:
+        raise _lib.OmgHipError("refine must not be negative")
+    hyp, counts, best, best_planes, anchors = plane_ransac(intrinsics, depth, triples, tol, min_nn, skip, up, cos_min)
+    h_best, h_counts, h_anchors = best.cpu().numpy(), counts.cpu().numpy(), anchors.cpu().numpy()
+
+    def moments_of(current):
+        count, sums = plane_moments(intrinsics, depth, current, anchors, tol, skip)
+        return count.cpu().numpy(), sums.cpu().numpy()
+
+    final, inliers, status = _pl._fit_rounds(h_best, best_planes.cpu().numpy(), h_anchors, refine, moments_of)
+    ransac_counts = np.array([h_counts[v, h_best[v]] if h_best[v] >= 0 else 0 for v in range(len(h_best))], np.int32)
+    return PlaneFit(planes=_upload(final, depth.device), hypotheses=hyp, counts=counts, best=best, h_planes=final, h_best=h_best,
+                    ransac_counts=ransac_counts, inliers=inliers, status=status, anchors=h_anchors)
+
+
+def plane_mask(intrinsics, depth: torch.Tensor, planes, tol: float, skip: "torch.Tensor | None" = None) -> torch.Tensor:
+    """The pixels on or behind the planes [V,4] (a device tensor, PlaneFit.planes, or a host array) in ONE launch
+    (omgx_plane_mask; planes.plane_mask is the specification) -> a bool tensor of depth's shape on its device, directly usable
+    as the free_mask of segment_obstacles, or as the skip of another fit."""
+    k, V, H, W, tol = _plane_images(intrinsics, depth, skip, tol)
+    _need(depth, torch.float64, "depth")
+    dev, vp = depth.device, C.c_void_p
+    with torch.cuda.device(dev):
+        d_planes = _plane_rows(planes, V, dev)
+        mask = torch.empty((V, H, W), dtype=torch.uint8, device=dev)
+        if V:
+            d_k, d_skip = _upload(k, dev), _plane_skip(skip)
+            check(_lib.lib().omgx_plane_mask(_ptr(d_k), vp(k.ctypes.data), _ptr(depth), _ptr(d_skip), V, H, W, _ptr(d_planes), tol, _ptr(mask), _stream()),
+                  "omgx_plane_mask")
+            for t in (d_k, d_skip, d_planes):
+                if t is not None:
+                    t.record_stream(torch.cuda.current_stream(dev))
+    return mask.view(torch.bool)
+
+
+def _plane_volume_arguments(volumes, planes):
+    """The host side of plane_volumes, checked before anything touches the device -> (records, node counts, planes [M,4])."""
+    assert _lib.PLANE_NODES_PER_WORKGROUP == _lib.SURFACE_NODES_PER_WORKGROUP
+    rec, nodes, _ = _fusion_volumes(volumes, None)
+    h_planes = np.ascontiguousarray(planes, np.float64).reshape(-1, 4)
+    if len(h_planes) != len(rec) or not np.isfinite(h_planes).all():
+        raise _lib.OmgHipError(f"{len(rec)} volumes need as many planes [4], all finite")
+    return rec, nodes, h_planes
+
+
+def plane_volumes(volumes, planes, out: "torch.Tensor | None" = None, device="cuda:0") -> torch.Tensor:
+    """The half-space volumes of M planes in ONE launch (omgx_plane_volumes; planes.halfspace_volume is the specification: the
+    same bits): float32(n.p + off) at every node, positive on the camera's side of the plane.  volumes: what surface_records
+    takes, the fifth field the element offset in `out` (without it: back to back); planes [M,4] on the host, in the grids'
+    frames.  out: a contiguous float32 device tensor (the SDF pool) written IN PLACE, or None -> a new buffer on `device`."""
+    rec, nodes, h_planes = _plane_volume_arguments(volumes, planes)
+    M, vp = len(rec), C.c_void_p
+    if out is None:
+        out = torch.zeros(max([int(r.out_offset) + int(n) for r, n in zip(rec, nodes)], default=1), dtype=torch.float32, device=device)
+    _need(out, torch.float32, "out")
+    dev = out.device
+    if M == 0:
+        return out
+    with torch.cuda.device(dev):
+        d_rec, d_planes = _upload(rec, dev), _upload(h_planes, dev)
+        check(_lib.lib().omgx_plane_volumes(_ptr(d_rec), C.cast(rec, vp), M, _ptr(d_planes), vp(h_planes.ctypes.data), _ptr(out), int(out.numel()),
+                                            _stream()), "omgx_plane_volumes")
+        for t in (d_rec, d_planes):
+            t.record_stream(torch.cuda.current_stream(dev))
+    return out
 
 
 class RayBatch:

@@ -159,3 +159,31 @@ def plan_observed(model, scenes, obs, obstacles, layouts, band: float, near: flo
             scenes[s].objects[o].sdf = _sc.SdfGrid(table.pool[off: off + int(np.prod(n))].view(n).cpu().numpy(), org, float(delta))
     plans, sets, meshes = plan_volumes(model, scenes, starts, cfg, device=device, **plan_kwargs)
     return plans, sets, meshes, records
+
+
+def plan_on_unknown_support(model, scenes, obs, obstacles, supports, layouts, support_layouts, band: float, near: float, reach: float, seeds,
+                            min_nodes: int, starts, cfg, triples, tol: float, up_world=None, cos_min: float = -1.0, refine: int = 2,
+                            connectivity: int = 6, margin=None, device="cuda:0", **plan_kwargs):
+    """plan_observed on a support nobody has modelled: from depth images and seed points alone.  The support's plane is fitted to
+    every scene's depth image (camera.Observation.fit_supports: triples, tol, up_world, cos_min, refine), its pixels are the
+    free_mask that plan_observed takes in place of explained_mask's rendering of a known table, and its half-space becomes the
+    volume of supports[s], an object of scene s at the pose of the layout's frame (support_layouts: one (origin [3], delta,
+    dims [3]) per scene, voxel centres, in that frame), so that the masked-out support is still an obstacle: the volume is
+    written on the device (ops.DeviceScenes.plane_obstacles) and downloaded into the object's SdfGrid as plan_observed downloads
+    its two.  Then plan_observed, unchanged.  A scene without a plane is refused.
+    -> (GraspPlans, grasp poses, meshes, the chosen records [S,8], the ops.PlaneFit)."""
+    from . import scenes as _sc
+    dev = torch.device(device)
+    S = len(scenes)
+    sp = [(s, int(o)) for s, o in enumerate(supports)]
+    fit, mask = obs.fit_supports(triples, tol, up_world, cos_min, refine)
+    table = ops.DeviceScenes.from_scenes(scenes, cfg.layer_kwargs(), device=dev, share_grids=False,
+                                         reserve_voxels=sum(int(np.prod(dims)) for _, _, dims in support_layouts))
+    table.plane_obstacles(sp, obs.support_planes(table, sp, fit), support_layouts)
+    host = table.sync_host()
+    for (s, o), (origin, delta, dims) in zip(sp, support_layouts):
+        off, n = int(host[table._index(s, o)]["grid_offset"]), tuple(int(d) for d in dims)
+        scenes[s].objects[o].sdf = _sc.SdfGrid(table.pool[off: off + int(np.prod(n))].view(n).cpu().numpy(), np.asarray(origin, np.float64), float(delta))
+    plans, sets, meshes, records = plan_observed(model, scenes, obs, obstacles, layouts, band, near, reach, seeds, min_nodes, starts, cfg, connectivity,
+                                                 margin, free_mask=mask, device=device, **plan_kwargs)
+    return plans, sets, meshes, records, fit

@@ -9,7 +9,7 @@ objects by connectivity, the target is the component nearest to a seed point, an
 the target taken out.
 
 Volumes, state_begin and the linear index L = (i * dims[1] + j) * dims[2] + k are fusion.py's.  Not part of the contract:
-splitting objects that touch, colour, tracking labels from frame to frame, fitting planes to unknown supports.
+splitting objects that touch, colour, tracking labels from frame to frame.  (Unknown supports: planes.py.)
 """
 from __future__ import annotations
 
