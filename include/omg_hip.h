@@ -1145,6 +1145,54 @@ int omgx_plane_volumes(const omgx_mesh* volumes, const omgx_mesh* h_volumes, int
                        const double* h_planes, float* pool, int64_t pool_elems, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * (20) omgx_tsdf_integrate, omgx_tsdf_states, omgx_tsdf_blend: depth views to sub-voxel obstacle volumes
+ * (17) puts the zero level on voxel faces, about `band` in front of the observed surface; every noisy frame thickens the
+ * SURFACE shell, and a node once SURFACE stays SURFACE.  Here a node keeps KinectFusion's pair: D, the truncated signed
+ * distance along the optical axis averaged over the views with weights, and W, the accumulated weight, two float32 at
+ * tsdf[state_begin[m] + L] and weight[state_begin[m] + L].  The sign of D and a threshold on W give the state bytes of (17), which
+ * omgx_distance_transform and (18) take as they are, and near the surface the transform's value in the pool is replaced by D,
+ * blended over the truncation: the zero level of the result is the TSDF's.  omg-planner_amd/tsdf.py (integrate, states, blend) is
+ * the specification; all arithmetic is float64 without contraction, dot products as ((a*x + b*y) + c*z) + d, with + - * /,
+ * floor, |x| and comparisons only, and pairs, states and volumes have the specification's bits.  New entry points only, no new
+ * struct: omgx_abi_version() stays 14.
+ *
+ * Volumes, views, view_range, depth, state_begin and the linear index L are those of (17), first_workgroup = the prefix table
+ * with OMGX_TSDF_NODES_PER_WORKGROUP nodes per workgroup; out_offset is read by omgx_tsdf_blend only.
+ *
+ * omgx_tsdf_integrate: one thread per node, one launch.  The node starts from (D, W) = (0, 0); with merge != 0 from the stored
+ *   pair widened to double, (0, 0) if !(W > 0).  The views of its range are applied in order.  The point, q, z, the pixel
+ *   (r, c) and d = depth[v][r][c] are those of omgx_carve_views, operation for operation: a view says nothing if !(z > near),
+ *   if the pixel is outside the image or if !(d > 0).  Then s = d - z: nothing if !(s >= -trunc) (behind the surface by more
+ *   than the truncation); t = s < trunc ? s : trunc (+inf gives trunc: background frees).  w = weights[v], 1.0 with weights ==
+ *   NULL; a view with !(w > 0) says nothing.  Wn = W + w, D = (W*D + w*t) / Wn, W = Wn < wmax ? Wn : wmax.  After the last view
+ *   the pair is rounded to float32 once and written; elements outside every volume's range are not touched.  Two calls round
+ *   in between, so they equal one call over all views to float32 rounding only.
+ * omgx_tsdf_states: state[state_begin[m] + L] = 2 if !(W >= min_weight), else 1 if D < 0, else 0, compared in float32.
+ * omgx_tsdf_blend: E = pool[out_offset + L], what omgx_distance_transform made of those states.  Where W >= min_weight:
+ *   a = |D| / trunc in double, pool[out_offset + L] = a >= 1 ? E : (float)(D + a * (E - D)); every other node keeps E.  The result
+ *   has the sign of D wherever D != 0, and is the transform's bit for bit where the TSDF is saturated or unobserved.
+ * No atomics, nothing spins or waits; the stream is the only barrier.
+ * `volumes`, `views`, `view_range`, `state_begin`, `weights` are on the device, h_* the same on the host; ALL checks are made on
+ * the host copies before any HIP call.  OMGX_ERR_INVALID: every case of (17) about records, views, view ranges, images, state
+ * ranges (here the pairs' ranges in [0, elems), for omgx_tsdf_states also the states') and volumes in the pool; trunc or
+ * min_weight not finite or <= 0; wmax NaN or <= 0 (+inf: no cap); near not finite; weights without h_weights or the reverse; a
+ * weight that is not finite or is negative.  OMGX_ERR_UNSUPPORTED: more than 2^31 - 1 nodes in one volume or workgroups in all,
+ * V * H * W > 2^31 - 1.  M == 0 returns OMGX_OK and launches nothing.
+ * ------------------------------------------------------------------------------------------- */
+#define OMGX_TSDF_NODES_PER_WORKGROUP 256
+int omgx_tsdf_integrate(const omgx_mesh* volumes, const omgx_mesh* h_volumes, int32_t num_volumes, const double* views,
+                        const double* h_views, int32_t num_views, const int32_t* view_range, const int32_t* h_view_range,
+                        const int64_t* state_begin, const int64_t* h_state_begin, const double* depth, int32_t H, int32_t W,
+                        const double* weights /* [V] or NULL */, const double* h_weights, double trunc, double near, double wmax,
+                        int32_t merge, float* tsdf, float* weight, int64_t elems, void* stream);
+int omgx_tsdf_states(const float* tsdf, const float* weight, int64_t elems, const int64_t* state_begin, const int64_t* h_state_begin,
+                     const omgx_mesh* volumes, const omgx_mesh* h_volumes, int32_t num_volumes, float min_weight, uint8_t* state,
+                     void* stream);
+int omgx_tsdf_blend(const float* tsdf, const float* weight, int64_t elems, const int64_t* state_begin, const int64_t* h_state_begin,
+                    const omgx_mesh* volumes, const omgx_mesh* h_volumes, int32_t num_volumes, double trunc, float min_weight,
+                    float* pool, int64_t pool_elems, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Diagnostics
  * ------------------------------------------------------------------------------------------- */
 const char* omgx_last_error(void); /* thread-local text of the last OMGX_ERR_LAUNCH               */

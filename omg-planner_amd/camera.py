@@ -215,6 +215,13 @@ class Observation:
         scene, through the view row fusion.view_rows(intrinsics, cam_from_world @ world_from_obj) with the object's pose from the
         table's host mirror.  target_free: the pixels of label 0 (the target) count as background, so that the volume holds the
         non-target points only, as omg/core.py:849-851 splits them.  Returns the radius used."""
+        pairs, depth, views, ranges, free_mask = self._obstacle_views(table, pairs, target_free)
+        return table.fuse_obstacles(pairs, depth, views, ranges, layouts, band, near, reach, unknown_occupied, free_mask)
+
+    def _obstacle_views(self, table, pairs, target_free: bool):
+        """What DeviceScenes.fuse_obstacles / integrate_obstacles take for the (scene, obj) `pairs`: (pairs [n,2], depth [n,H,W]:
+        image m the one of pair m's scene, the view rows [n,16], view_range [n,2] = (m, 1), the target's pixels as a bool mask
+        [n,H,W] or None)."""
         import torch
         pairs = np.asarray(pairs, np.int64).reshape(-1, 2)
         views = self.view_rows(table, pairs)
@@ -225,8 +232,17 @@ class Observation:
                    for s in range(len(begin) - 1)]  # (the last entry: inst == -1, the background)
             free_mask = torch.stack([lut[int(s)][self.inst[int(s)].long()] for s in pairs[:, 0]])
         depth = self.t[torch.from_numpy(pairs[:, 0].copy()).to(self.t.device)].contiguous()
-        return table.fuse_obstacles(pairs, depth, views, np.stack([np.arange(len(pairs)), np.ones(len(pairs), np.int64)], -1), layouts, band,
-                                    near, reach, unknown_occupied, free_mask)
+        return pairs, depth, views, np.stack([np.arange(len(pairs)), np.ones(len(pairs), np.int64)], -1), free_mask
+
+    def integrate_obstacles(self, table, pairs, layouts, trunc: float, near: float, reach: float, tsdf_volumes=None,
+                            unknown_occupied: bool = True, min_weight: float = 1.0, wmax: float = float("inf"), weights=None,
+                            target_free: bool = True):
+        """fuse_obstacles with weighted TSDF fusion (ops.DeviceScenes.integrate_obstacles, which documents trunc, min_weight,
+        wmax, weights and tsdf_volumes): the same view rows and the same target mask.  Passing the returned TsdfVolumes back in
+        with a later observation adds its frame to the same volumes.  Returns (radius, the TsdfVolumes)."""
+        pairs, depth, views, ranges, free_mask = self._obstacle_views(table, pairs, target_free)
+        return table.integrate_obstacles(pairs, tsdf_volumes, depth, views, ranges, layouts, trunc, near, reach, unknown_occupied, min_weight,
+                                         wmax, weights, free_mask)
 
     def segment_obstacles(self, table, target_pairs, obstacle_pairs, layouts, band: float, near: float, reach: float, seeds,
                           min_nodes: int, connectivity: int = 6, margin=None, free_mask=None):

@@ -15,7 +15,7 @@ the axis.  View v reads image v of depth [V,H,W] float64, the layout camera.rend
 Everything is float64, every operation rounded on its own, dot products written ((a*x + b*y) + c*z) + d, with + - * /, floor
 and sqrt only, so that the device can equal the bits.  Distances are to voxel centres: the fused value is at most
 (sqrt(3)/2) * delta coarser than the distance to the true surface points (plus the band on the free side).  Not part of the
-contract: sub-voxel surfaces, weighted averaging and sensor noise, colour.
+contract: sub-voxel surfaces, weighted averaging and sensor noise (tsdf.py adds them on these states and volumes), colour.
 """
 from __future__ import annotations
 

@@ -181,6 +181,18 @@ def sdf_loss_forward(pose_init, sdf_grids, sdf_limits, points, epsilons, padding
     return [pot, grad, col]
 
 
+def _masked_depth(depth: torch.Tensor, free_mask) -> torch.Tensor:
+    """depth [V,H,W] float64 on the device with the pixels of free_mask (a bool tensor of its shape, on its device; or None) set
+    to +inf, as a new tensor: the caller's images are not changed."""
+    _need(depth, torch.float64, "depth")
+    if free_mask is None:
+        return depth
+    if (not isinstance(free_mask, torch.Tensor) or free_mask.dtype != torch.bool or free_mask.shape != depth.shape
+            or free_mask.device != depth.device):
+        raise _lib.OmgHipError("free_mask must be a bool tensor of depth's shape, on its device")
+    return torch.where(free_mask, torch.full_like(depth, float("inf")), depth).contiguous()
+
+
 class PoolSlots:
     """Which part of the SDF pool each object's volume may use, as offsets and element counts.  Identical volumes are stored once
     (scenes.pack_table(share_grids=True), scene_io); a slot several objects share is never written in place (copy-on-write)."""
@@ -510,12 +522,7 @@ class DeviceScenes:
         # everything that can be refused is refused here, before grid_slot offers a slot: the radius, the layouts, the views
         _carve_arguments([(origin, delta, "centre", dims) for origin, delta, dims in layouts], views, view_range, depth, band, near, None)
         radius = _fusion_radius(max(_fu.obstacle_radius(reach, float(delta)) for _, delta, _ in layouts))
-        _need(depth, torch.float64, "depth")
-        if free_mask is not None:
-            if (not isinstance(free_mask, torch.Tensor) or free_mask.dtype != torch.bool or free_mask.shape != depth.shape
-                    or free_mask.device != depth.device):
-                raise _lib.OmgHipError("free_mask must be a bool tensor of depth's shape, on its device")
-            depth = torch.where(free_mask, torch.full_like(depth, float("inf")), depth).contiguous()
+        depth = _masked_depth(depth, free_mask)
         slots, volumes = [], []
         for (s, o), (origin, delta, dims) in zip(pairs, layouts):
             slot = self.grid_slot(int(s), int(o), tuple(int(d) for d in dims))
@@ -525,6 +532,52 @@ class DeviceScenes:
         for (s, o), (origin, delta, _), slot in zip(pairs, layouts, slots):
             self.replace_grid(int(s), int(o), slot, origin, float(delta), fit="device")
         return radius
+
+    def integrate_obstacles(self, pairs, tsdf_volumes: "TsdfVolumes | None", depth: torch.Tensor, views, view_range, layouts, trunc: float,
+                            near: float, reach: float, unknown_occupied: bool = True, min_weight: float = 1.0, wmax: float = float("inf"),
+                            weights=None, free_mask: "torch.Tensor | None" = None):
+        """fuse_obstacles with weighted TSDF fusion (fuse_tsdf; tsdf.fuse is the specification): the volumes of the (scene, obj)
+        `pairs` have their zero level on the observed surface, between the nodes, not `band` in front of it on voxel faces; with
+        a finite wmax old frames fade, so that an object that was taken away becomes free again.  pairs, depth, views,
+        view_range, layouts, near, reach, unknown_occupied and free_mask as fuse_obstacles takes them; trunc: the truncation (a
+        few voxels, a few sigma of the sensor); weights: one per view.  tsdf_volumes: None for the first frame, or what an
+        earlier call returned: this frame is added to the same pairs (its layouts, trunc, near and wmax must be the call's).
+        One integrate launch, then states, the three transform launches and the blend for all pairs, written straight into
+        grid_slot's slots, which become the objects' volumes through replace_grid(fit="device").  Everything that can be
+        refused is refused before a slot is offered.  Returns (radius, the TsdfVolumes)."""
+        from . import fusion as _fu
+        self._changing(volumes=True)
+        pairs = np.asarray(pairs, np.int64).reshape(-1, 2)
+        layouts = list(layouts)
+        if len(layouts) != len(pairs) or not len(pairs):
+            raise _lib.OmgHipError(f"{len(pairs)} pairs need as many layouts, and at least one")
+        if len({self._index(int(s), int(o)) for s, o in pairs}) != len(pairs):
+            raise _lib.OmgHipError("a (scene, obj) pair is named twice")
+        if not (np.isfinite(float(reach)) and float(reach) >= 0):
+            raise _lib.OmgHipError("reach must be finite and not negative")
+        min_weight = _tsdf_positive("min_weight", min_weight)
+        volumes = [(origin, delta, "centre", dims) for origin, delta, dims in layouts]
+        _, _, _, _, _, _, trunc, wmax = _tsdf_arguments(volumes, views, view_range, depth, trunc, near, weights, wmax, None)
+        radius = _fusion_radius(max(_fu.obstacle_radius(reach, float(delta)) for _, delta, _ in layouts))
+        depth = _masked_depth(depth, free_mask)
+        if depth.device != self.pool.device:
+            raise _lib.OmgHipError(f"depth must be on {self.pool.device}, got {depth.device}")
+        if tsdf_volumes is None:
+            tsdf_volumes = TsdfVolumes(volumes, trunc, near, wmax, device=depth.device)
+        else:
+            same = isinstance(tsdf_volumes, TsdfVolumes) and len(tsdf_volumes.rec) == len(layouts) and all(
+                np.array_equal(a[0], np.asarray(b[0], np.float64).reshape(-1)) and a[1] == float(b[1]) and a[2] == tuple(int(d) for d in b[2])
+                for a, b in zip(tsdf_volumes.layouts(), layouts))
+            if not same or (tsdf_volumes.trunc, tsdf_volumes.near, tsdf_volumes.wmax) != (trunc, float(near), wmax):
+                raise _lib.OmgHipError("tsdf_volumes were started with other layouts, or another trunc, near or wmax")
+            if tsdf_volumes.device != depth.device:
+                raise _lib.OmgHipError(f"tsdf_volumes are on {tsdf_volumes.device}, depth on {depth.device}")
+        slots = [self.grid_slot(int(s), int(o), tuple(int(d) for d in dims)) for (s, o), (_, _, dims) in zip(pairs, layouts)]
+        tsdf_volumes.integrate(depth, views, view_range, weights)
+        tsdf_volumes.signed(radius, unknown_occupied, min_weight, out=self.pool, offsets=[(slot.data_ptr() - self.pool.data_ptr()) // 4 for slot in slots])
+        for (s, o), (origin, delta, _), slot in zip(pairs, layouts, slots):
+            self.replace_grid(int(s), int(o), slot, origin, float(delta), fit="device")
+        return radius, tsdf_volumes
 
     def segment_obstacles(self, target_pairs, obstacle_pairs, depth: torch.Tensor, views, view_range, layouts, band: float, near: float,
                           reach: float, seeds, min_nodes: int, connectivity: int = 6, margin: "int | None" = None,
@@ -557,12 +610,7 @@ class DeviceScenes:
         _carve_arguments(volumes, views, view_range, depth, band, near, None)
         radius = _fusion_radius(max(_fu.obstacle_radius(reach, float(delta)) for _, delta, _ in layouts))
         margin = radius + 1 if margin is None else int(margin)
-        _need(depth, torch.float64, "depth")
-        if free_mask is not None:
-            if (not isinstance(free_mask, torch.Tensor) or free_mask.dtype != torch.bool or free_mask.shape != depth.shape
-                    or free_mask.device != depth.device):
-                raise _lib.OmgHipError("free_mask must be a bool tensor of depth's shape, on its device")
-            depth = torch.where(free_mask, torch.full_like(depth, float("inf")), depth).contiguous()
+        depth = _masked_depth(depth, free_mask)
         state, begin = carve_views(volumes, views, view_range, depth, band, near)
         comps = label_components(state, begin, volumes, 1, connectivity)
         try:  # (a scene without a component of min_nodes nodes is refused here: no slot has been offered yet)
@@ -1503,6 +1551,184 @@ def fuse_views(volumes, views, view_range, depth: torch.Tensor, band: float, nea
     radius = _fusion_radius(radius)
     state, begin = carve_views(volumes, views, view_range, depth, band, near)
     return distance_transform(state, begin, volumes, radius, unknown_occupied, out)
+
+
+def _tsdf_positive(name: str, x, may_be_inf: bool = False) -> float:
+    from . import tsdf as _ts
+    try:  # (the specification's own check of trunc, wmax and min_weight, as this module's error)
+        return _ts._positive(name, x, may_be_inf)
+    except ValueError as e:
+        raise _lib.OmgHipError(str(e)) from None
+
+
+def _tsdf_arguments(volumes, views, view_range, depth, trunc, near, weights, wmax, state_begin):
+    """The host side of an integrate launch, checked before anything touches the device: _carve_arguments' result and
+    (weights float64 [V] or None, trunc, wmax)."""
+    trunc, wmax = _tsdf_positive("trunc", trunc), _tsdf_positive("wmax", wmax, True)
+    rec, nodes, begin, h_views, h_range = _carve_arguments(volumes, views, view_range, depth, 0.0, near, state_begin)
+    h_w = None
+    if weights is not None:
+        h_w = np.ascontiguousarray(weights, np.float64).reshape(-1)
+        if len(h_w) != len(h_views) or not np.isfinite(h_w).all() or (h_w < 0).any():
+            raise _lib.OmgHipError(f"weights must be {len(h_views)} finite numbers >= 0")
+    return rec, nodes, begin, h_views, h_range, h_w, trunc, wmax
+
+
+def _tsdf_pair(tsdf, weight, dev=None):
+    _need(tsdf, torch.float32, "tsdf")
+    _need(weight, torch.float32, "weight")
+    dev = tsdf.device if dev is None else dev
+    if tsdf.device != dev or weight.device != dev or tsdf.numel() != weight.numel():
+        raise _lib.OmgHipError(f"tsdf and weight must have the same number of elements on {dev}")
+
+
+def tsdf_integrate(volumes, views, view_range, depth: torch.Tensor, trunc: float, near: float, weights=None, wmax: float = float("inf"),
+                   tsdf: "torch.Tensor | None" = None, weight: "torch.Tensor | None" = None, state_begin=None, merge: bool = False,
+                   _device_records=None):
+    """The pairs (D: the averaged truncated distance, W: the accumulated weight) of the nodes of M volumes from V depth views in
+    ONE launch (omgx_tsdf_integrate; tsdf.integrate is the specification: the same bits) -> (tsdf, weight: float32 on the
+    device, state_begin [M] int64 numpy): volume m's node L at state_begin[m] + L of both.  volumes, views, view_range, depth and
+    state_begin as carve_views takes them; weights: [V] host numbers >= 0 (None: 1.0 each); wmax caps W, so that old views fade.
+    tsdf / weight: None -> new buffers that reach to the end of the last volume, zero where no volume lies; or the caller's,
+    written IN PLACE.  merge: the pairs start from what the buffers hold (a further frame), otherwise from (0, 0).
+    The host arguments are checked first, then the tensors: a refused call has touched nothing."""
+    rec, nodes, begin, h_views, h_range, h_w, trunc, wmax = _tsdf_arguments(volumes, views, view_range, depth, trunc, near, weights, wmax, state_begin)
+    if (tsdf is None) != (weight is None):
+        raise _lib.OmgHipError("tsdf and weight come together")
+    if tsdf is None and merge:
+        raise _lib.OmgHipError("merge needs the pairs of an earlier call")
+    _need(depth, torch.float64, "depth")
+    dev, vp = depth.device, C.c_void_p
+    (V, H, W), M = (int(d) for d in depth.shape), len(rec)
+    if tsdf is None:
+        n = max(int((begin + nodes).max()) if M else 0, 1)
+        tsdf, weight = torch.zeros(n, dtype=torch.float32, device=dev), torch.zeros(n, dtype=torch.float32, device=dev)
+    _tsdf_pair(tsdf, weight, dev)
+    with torch.cuda.device(dev):
+        d_rec, d_begin = _device_records if _device_records is not None else (_upload(rec, dev), _upload(begin, dev))
+        d_views, d_range = _upload(h_views, dev), _upload(h_range, dev)
+        d_w = _upload(h_w, dev) if h_w is not None and V else None
+        check(_lib.lib().omgx_tsdf_integrate(_ptr(d_rec) if M else None, C.cast(rec, vp) if M else None, M, _ptr(d_views) if V else None,
+                                             vp(h_views.ctypes.data) if V else None, V, _ptr(d_range) if M else None,
+                                             vp(h_range.ctypes.data) if M else None, _ptr(d_begin) if M else None, vp(begin.ctypes.data) if M else None,
+                                             _ptr(depth) if V else None, H, W, _ptr(d_w), vp(h_w.ctypes.data) if d_w is not None else None, trunc,
+                                             float(near), wmax, int(bool(merge)), _ptr(tsdf), _ptr(weight), int(tsdf.numel()), _stream()),
+              "omgx_tsdf_integrate")
+        for t in (d_rec, d_views, d_range, d_begin, d_w):
+            if t is not None:
+                t.record_stream(torch.cuda.current_stream(dev))
+    return tsdf, weight, begin
+
+
+def tsdf_states(tsdf: torch.Tensor, weight: torch.Tensor, state_begin, volumes, min_weight: float = 1.0, state: "torch.Tensor | None" = None,
+                _device_records=None) -> torch.Tensor:
+    """The state bytes of the pairs in one launch (omgx_tsdf_states; tsdf.states is the specification): 2 (unknown) if
+    !(W >= min_weight), else 1 (surface) if D < 0, else 0 (free), at the pairs' own offsets: carve_views' layout, so
+    distance_transform, label_components and component_states take them as they are.  state: None -> a new buffer of the pairs'
+    length, 2 where no volume lies; or the caller's uint8 tensor of that length, written IN PLACE inside the volumes' ranges."""
+    from . import fusion as _fu
+    min_weight = _tsdf_positive("min_weight", min_weight)
+    rec, nodes, begin = _fusion_volumes(volumes, state_begin)
+    _tsdf_pair(tsdf, weight)
+    dev, vp, M = tsdf.device, C.c_void_p, len(rec)
+    if state is None:
+        state = torch.full((tsdf.numel(),), _fu.UNKNOWN, dtype=torch.uint8, device=dev)
+    _need(state, torch.uint8, "state")
+    if state.device != dev or state.numel() != tsdf.numel():
+        raise _lib.OmgHipError(f"state must have the pairs' {tsdf.numel()} elements on {dev}")
+    with torch.cuda.device(dev):
+        d_rec, d_begin = _device_records if _device_records is not None else (_upload(rec, dev), _upload(begin, dev))
+        check(_lib.lib().omgx_tsdf_states(_ptr(tsdf), _ptr(weight), int(tsdf.numel()), _ptr(d_begin) if M else None, vp(begin.ctypes.data) if M else None,
+                                          _ptr(d_rec) if M else None, C.cast(rec, vp) if M else None, M, min_weight, _ptr(state), _stream()),
+              "omgx_tsdf_states")
+        for t in (d_rec, d_begin):
+            t.record_stream(torch.cuda.current_stream(dev))
+    return state
+
+
+def tsdf_blend(tsdf: torch.Tensor, weight: torch.Tensor, state_begin, volumes, trunc: float, min_weight: float, out: torch.Tensor) -> torch.Tensor:
+    """The pairs blended into the volumes distance_transform wrote, IN PLACE in `out` (the SDF pool, for instance) at every
+    volume's element offset, in one launch (omgx_tsdf_blend; tsdf.blend is the specification: the same bits): where
+    W >= min_weight, out = D + (|D| / trunc) * (out - D) unless |D| >= trunc.  The zero level of the result is the TSDF's."""
+    trunc, min_weight = _tsdf_positive("trunc", trunc), _tsdf_positive("min_weight", min_weight)
+    rec, nodes, begin = _fusion_volumes(volumes, state_begin)
+    _tsdf_pair(tsdf, weight)
+    dev, vp, M = tsdf.device, C.c_void_p, len(rec)
+    _need(out, torch.float32, "out")
+    if out.device != dev:
+        raise _lib.OmgHipError(f"out must be on {dev}, got {out.device}")
+    with torch.cuda.device(dev):
+        d_rec, d_begin = _upload(rec, dev), _upload(begin, dev)
+        check(_lib.lib().omgx_tsdf_blend(_ptr(tsdf), _ptr(weight), int(tsdf.numel()), _ptr(d_begin) if M else None, vp(begin.ctypes.data) if M else None,
+                                         _ptr(d_rec) if M else None, C.cast(rec, vp) if M else None, M, trunc, min_weight, _ptr(out), int(out.numel()),
+                                         _stream()), "omgx_tsdf_blend")
+        for t in (d_rec, d_begin):
+            t.record_stream(torch.cuda.current_stream(dev))
+    return out
+
+
+def _tsdf_signed(tsdf, weight, begin, volumes, trunc, radius, unknown_occupied, min_weight, out, device_records=None):
+    state = tsdf_states(tsdf, weight, begin, volumes, min_weight, _device_records=device_records)
+    out = distance_transform(state, begin, volumes, radius, unknown_occupied, out)
+    return tsdf_blend(tsdf, weight, begin, volumes, trunc, min_weight, out)
+
+
+def fuse_tsdf(volumes, views, view_range, depth: torch.Tensor, trunc: float, near: float, radius: int, unknown_occupied: bool = True,
+              min_weight: float = 1.0, weights=None, wmax: float = float("inf"), out: "torch.Tensor | None" = None):
+    """tsdf_integrate, tsdf_states, distance_transform and tsdf_blend for M volumes, six launches in all (tsdf.fuse is the
+    specification) -> out, as distance_transform returns it (with out=pool: written in place, as fuse_views does).  The radius
+    and min_weight are checked before the first launch."""
+    radius, min_weight = _fusion_radius(radius), _tsdf_positive("min_weight", min_weight)
+    tsdf, weight, begin = tsdf_integrate(volumes, views, view_range, depth, trunc, near, weights, wmax)
+    return _tsdf_signed(tsdf, weight, begin, volumes, trunc, radius, unknown_occupied, min_weight, out)
+
+
+class TsdfVolumes:
+    """The pairs of M volumes kept on the device across frames: the records and state_begin (uploaded once), tsdf and weight
+    (float32, zero at first).  volumes: what surface_records takes; trunc, near and wmax hold for every frame."""
+
+    def __init__(self, volumes, trunc: float, near: float, wmax: float = float("inf"), device="cuda:0", state_begin=None):
+        self.trunc, self.wmax, self.near = _tsdf_positive("trunc", trunc), _tsdf_positive("wmax", wmax, True), float(near)
+        if not np.isfinite(self.near):
+            raise _lib.OmgHipError("band and near must be finite")
+        self.volumes = [tuple(v) for v in volumes]
+        self.rec, self.nodes, self.state_begin = _fusion_volumes(self.volumes, state_begin)
+        if not len(self.rec):
+            raise _lib.OmgHipError("TsdfVolumes needs at least one volume")
+        self.device = torch.device(device)
+        n = int((self.state_begin + self.nodes).max())
+        self.tsdf, self.weight = (torch.zeros(n, dtype=torch.float32, device=self.device) for _ in range(2))
+        self._records = (_upload(self.rec, self.device), _upload(self.state_begin, self.device))
+        self.frames = 0
+
+    def layouts(self):
+        """[(origin [3] float64, delta, dims)] of the volumes, for comparison with a caller's layouts."""
+        return [(np.array(r.origin[:], np.float64), float(r.delta), tuple(int(d) for d in r.dims[:])) for r in self.rec]
+
+    def integrate(self, depth: torch.Tensor, views, view_range, weights=None) -> "TsdfVolumes":
+        """One more frame: depth [V,H,W], views [V,16] and view_range [M,2] as tsdf_integrate takes them.  The first call starts
+        from (0, 0), every later one merges."""
+        tsdf_integrate(self.volumes, views, view_range, depth, self.trunc, self.near, weights, self.wmax, self.tsdf, self.weight, self.state_begin,
+                       merge=self.frames > 0, _device_records=self._records)
+        self.frames += 1
+        return self
+
+    def states(self, min_weight: float = 1.0) -> torch.Tensor:
+        """A new uint8 tensor of state bytes at state_begin (tsdf_states)."""
+        return tsdf_states(self.tsdf, self.weight, self.state_begin, self.volumes, min_weight, _device_records=self._records)
+
+    def signed(self, radius: int, unknown_occupied: bool = True, min_weight: float = 1.0, out: "torch.Tensor | None" = None, offsets=None):
+        """The signed float32 volumes: states, distance_transform and tsdf_blend -> out, as distance_transform returns it.
+        offsets: the volumes' element offsets in `out` for this call (a pool's slots change from frame to frame); default: the
+        layouts' own."""
+        radius, min_weight = _fusion_radius(radius), _tsdf_positive("min_weight", min_weight)
+        volumes = self.volumes
+        if offsets is not None:
+            if len(offsets) != len(volumes):
+                raise _lib.OmgHipError(f"{len(volumes)} volumes need as many offsets")
+            volumes = [v[:4] + (int(o),) for v, o in zip(volumes, offsets)]
+        return _tsdf_signed(self.tsdf, self.weight, self.state_begin, volumes, self.trunc, radius, unknown_occupied, min_weight, out,
+                            self._records)
 
 
 class Components:
