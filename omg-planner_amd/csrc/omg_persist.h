@@ -30,7 +30,8 @@
 //   goal cost / count  goal item: sc1 stores, drained, then the arrival       ->  last arriver: acquire fence, plain loads
 //   layer outputs, poses  layer item: plain stores, release fence, then the arrival  ->  last arriver: acquire fence, plain loads
 //   learner state, goal, info  step workgroup: plain stores, release fence, then the activation  ->  the scene's next step workgroup: acquire fence
-// Every spin is bounded (2 s) and reports through the control block; the host zeroes / initialises the queue before every launch.
+// Every spin is bounded — 2 s without PROGRESS OF THE PLAN (out_of_patience below), not 2 s of waiting: a workgroup with nothing to do in a
+// long healthy launch waits on — and reports through the control block; the host zeroes / initialises the queue before every launch.
 #pragma once
 
 typedef const OMG_CONST_AS omgx_plan_iter* IterTablePtr;  // the iteration table is never written by the kernel: scalar loads
@@ -78,6 +79,22 @@ __device__ __forceinline__ unsigned long long ld_u64(const unsigned long long* p
 // a read as a read-modify-write atomic: performed where the word lives, whatever this XCD's L2 still holds of the line
 __device__ __forceinline__ uint32_t rmw_u32(uint32_t* p) { return __hip_atomic_fetch_add(p, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ __forceinline__ unsigned long long rmw_u64(unsigned long long* p) { return __hip_atomic_fetch_add(p, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+
+// The bound of every wait (claim, update requests, tags): PQ_WAIT_TICKS of the 100 MHz clock (2 s) since the waiter's clock was last
+// started — and the clock starts over when the plan has moved since the waiter's last look: ctl[0] (activations made) or ctl[2] (scenes
+// finished).  The look is two atomics in a branch that has just waited 2 s; no other path gains a memory operation.  Fixed-goal iterations
+// have 5 items per scene, so in a long launch of a small plan a workgroup may find nothing to take for seconds: that is no failure.  A plan
+// that stands still is given up 2 to 4 s after its last progress (the first look, with nothing to compare with, always starts over).
+#define PQ_WAIT_TICKS 200000000LL
+struct Patience { long long t_begin; uint32_t act, fin; };  // (act, fin) = ~0: not looked yet (ctl[0] <= 65535 * 65535)
+__device__ __forceinline__ bool out_of_patience(uint32_t* ctl, Patience& w) {
+    const long long now = wall_clock64();
+    if (now - w.t_begin <= PQ_WAIT_TICKS) return false;
+    const uint32_t act = rmw_u32(ctl + 0), fin = rmw_u32(ctl + 2);
+    if (act == w.act && fin == w.fin) return true;
+    w.act = act; w.fin = fin; w.t_begin = now;
+    return false;
+}
 
 // (Re-)initialise the queue for a launch: every active scene activated for iteration 0, in scene order; one workgroup.
 __global__ __launch_bounds__(256) void k_persist_init(PersistArgs pa) {
@@ -314,14 +331,14 @@ __global__ __launch_bounds__(GQ_NT, GQ_WG_PER_CU) void k_plan_persistent(Persist
         for (;;) {
             if (tid == 0) {
                 int got_s = -1, got_t = 0;
-                const long long t_begin = wall_clock64();
+                Patience wait{wall_clock64(), ~0u, ~0u};
                 unsigned long long q = rmw_u64(uht);
                 for (int idle = 1;;) {
                     const uint32_t h = (uint32_t)q, tl = (uint32_t)(q >> 32);
                     if ((int32_t)(tl - h) > 0) {
                         if (!__hip_atomic_compare_exchange_strong(uht, &q, q + 1ull, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) continue;
                         unsigned long long e = rmw_u64(pa.uq + (size_t)xcd * pa.cap + h % (uint32_t)pa.cap);
-                        while ((uint32_t)(e >> 32) != h + 1u && wall_clock64() - t_begin < 200000000LL) { __builtin_amdgcn_s_sleep(1); e = rmw_u64(pa.uq + (size_t)xcd * pa.cap + h % (uint32_t)pa.cap); }
+                        while ((uint32_t)(e >> 32) != h + 1u && !out_of_patience(pa.ctl, wait)) { __builtin_amdgcn_s_sleep(1); e = rmw_u64(pa.uq + (size_t)xcd * pa.cap + h % (uint32_t)pa.cap); }
                         if ((uint32_t)(e >> 32) != h + 1u) { __hip_atomic_store(pa.ctl + 3, 4u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); break; }
                         got_s = (int)(e & 0xffffu); got_t = (int)((e >> 16) & 0xffffu);
                         break;
@@ -329,7 +346,7 @@ __global__ __launch_bounds__(GQ_NT, GQ_WG_PER_CU) void k_plan_persistent(Persist
                     if (rmw_u32(pa.ctl + 2) >= rmw_u32(pa.ctl + 4) || rmw_u32(pa.ctl + 3) != 0u) break;
                     for (int z = 0; z < idle; ++z) __builtin_amdgcn_s_sleep(2);
                     idle = idle < 8 ? idle * 2 : 8;
-                    if (wall_clock64() - t_begin > 200000000LL) { __hip_atomic_store(pa.ctl + 3, 5u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); break; }
+                    if (out_of_patience(pa.ctl, wait)) { __hip_atomic_store(pa.ctl + 3, 5u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); break; }
                     q = rmw_u64(uht);
                 }
                 bc[0] = got_s; bc[1] = got_t;
@@ -360,6 +377,7 @@ __global__ __launch_bounds__(GQ_NT, GQ_WG_PER_CU) void k_plan_persistent(Persist
         if (tid == 0) {
             int got_s = -1, got_t = 0, got_k = 0, got_n = 0, got_mode = 0;
             const long long t_begin = wall_clock64();
+            Patience wait{t_begin, ~0u, ~0u};
             unsigned spins = 0; (void)spins;
             int nap = 1;
             auto items_of = [&](int s, int t, int& mode) {
@@ -422,7 +440,7 @@ __global__ __launch_bounds__(GQ_NT, GQ_WG_PER_CU) void k_plan_persistent(Persist
                     // nothing to take right now: give the word back (another slot of this XCD may still hold items) after a short wait
                     for (int z = 0; z < idle; ++z) __builtin_amdgcn_s_sleep(2);
                     idle = idle < 16 ? idle * 2 : 16;
-                    if (wall_clock64() - t_begin > 200000000LL) { __hip_atomic_store(pa.ctl + 3, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); finished = true; break; }
+                    if (out_of_patience(pa.ctl, wait)) { __hip_atomic_store(pa.ctl + 3, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); finished = true; break; }
                     q = rmw_u64(ht);
                 }
                 if (finished) {
@@ -435,7 +453,7 @@ __global__ __launch_bounds__(GQ_NT, GQ_WG_PER_CU) void k_plan_persistent(Persist
                     e = rmw_u64(pa.ring + pos % (uint32_t)pa.cap);
                     if ((uint32_t)(e >> 32) == pos + 1u) break;
                     __builtin_amdgcn_s_sleep(2);
-                    if (wall_clock64() - t_begin > 200000000LL) { __hip_atomic_store(pa.ctl + 3, 2u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); break; }
+                    if (out_of_patience(pa.ctl, wait)) { __hip_atomic_store(pa.ctl + 3, 2u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); break; }
                 }
                 if ((uint32_t)(e >> 32) != pos + 1u) {
                     for (int a = 0; a < PQ_SLOTS; ++a) __hip_atomic_store(xw0 + 16 * a, PQ_DONE, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);

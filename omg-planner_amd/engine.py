@@ -393,10 +393,13 @@ class ChompEngine:
             self.goal_rows.copy_(self.goal_point[:, None, :])
 
     # ---------------------------------------------------------------------------------------------
-    def _learner_params(self) -> _lib.LearnerParams:
+    def _learner_params(self, alg: "int | None" = None) -> _lib.LearnerParams:
+        """The omgx_learner_params of the engine's rule at Learner.t.  alg: the rule's code where the record goes to a launch that
+        never reads it (run_persistent without a selecting iteration); None: _lib.ALG[ol_alg], a KeyError for a rule that has no
+        learner ("Baseline")."""
         cfg = self.cfg
         p = _lib.LearnerParams()
-        p.alg = _lib.ALG[self.ol_alg]
+        p.alg = _lib.ALG[self.ol_alg] if alg is None else int(alg)
         p.num_goals, p.n_waypoints = self.G, self.n
         p.start_idx = min(int((self.t / cfg.optim_steps) * cfg.timesteps), cfg.timesteps - 1)  # online_learner.py:109-110
         p.constraint_num, p.use_standoff = self.c, int(self.use_standoff)
@@ -467,6 +470,7 @@ class ChompEngine:
         part._batch_scenes = self.S  # the scenes of the whole batch: what the chip holds while this part's launches run
         part._parts, part._forked, part.pipeline = None, False, 1
         part._hot = None
+        part._persist_unchecked = False  # a persistent launch is the whole engine's, and so is the look at its status
         part.scenes = self.scenes.scene_range(lo, hi)  # for launches only; object offsets stay absolute
         part.work = torch.zeros(part.S * self.G * (1 if self.latency else self._parts_max), dtype=torch.int32, device=self.device)
         part.schedule, part._gs_launches, part._measured, part._sched_np = None, 0, False, 1
@@ -504,9 +508,13 @@ class ChompEngine:
             for part in self._parts[1:]:
                 cur.wait_stream(part.stream)
             self._forked = False
+        self._check_persistent()
+
+    def _check_persistent(self):
+        """A persistent launch reports what went wrong inside it (a bounded wait that ran out) through its control block only: look at it
+        before anything else is done with the engine's tensors (one small download per persistent launch, which waits for the launch on
+        the stream it went to).  join(), iterate() and _iterate_pipelined() come through here before they enqueue anything."""
         if self.__dict__.get("_persist_unchecked"):
-            # a persistent launch reports what went wrong inside it (a bounded wait that ran out) through its control block only: look at it
-            # before anything else is done with the engine's tensors (one small download per persistent launch)
             self._persist_unchecked = False
             st = self.persistent_status()
             if st["failure"]:
@@ -515,6 +523,7 @@ class ChompEngine:
     _CFG_SCHEDULE = ("obstacle_weight", "smoothness_weight", "grasp_weight", "step_size")
 
     def _iterate_pipelined(self, t: int, early_stop: bool, k: int):
+        self._check_persistent()  # parts at hand and not forked: nothing below calls join()
         parts = self._get_parts(k)
         if early_stop:
             self._masked = True
@@ -748,6 +757,7 @@ class ChompEngine:
         calls (ops.IterationCalls) — omgx_goalset_cost_layer (goal-set batch + SDF layer of the current trajectories) and
         omgx_goal_update_optimize (Learner.update_goal + Optimizer.optimize); once the goal is fixed (t >= optim_steps, "Proj",
         "Baseline") the layer launch and the step."""
+        self._check_persistent()
         k = self._pipeline_parts()
         select = self._selects(t)
         if k > 1 and self.SMOOTH_SINGLE_PART_BELOW > self.S and not select and not self.separate_launches and self.stream is None:
@@ -868,9 +878,12 @@ class ChompEngine:
         ws = self.__dict__.get("_persist_ws")
         if ws is None:
             ws = self._persist_ws = torch.zeros(int(_lib.lib().omgx_plan_persistent_workspace_bytes(self.S, self.n)), dtype=torch.uint8, device=self.device)
-        lprm = self._learner_params()
+        # a launch without a selecting iteration ("Proj", "Baseline", t >= optim_steps) never reads the rule: omgx_plan_persistent looks
+        # at h_learner->alg only under `if (any_select)` (omg_kernels.hip), and "Baseline" has no code in _lib.ALG
+        lprm = self._learner_params(alg=None if any(r.mode for r in recs) else _lib.ALG["Proj"])
         lprm.cost_parts = 0
         self._parts_last = 1
+        self._persist_stream = torch.cuda.current_stream(self.device)  # where the launch goes: persistent_status() waits for this one
         ops.plan_persistent(self.robot, self.P, self.scenes, self.cv_goals, self.cfg.time_interval, self.traj, (self.pot, self.pgrad, self.col),
                             self.wp_pose, (self.goal_cost, self.goal_col), lprm, self.goal_set, self.reach, self.learner_state, self.goal_idx,
                             self.cost_vec, self._params(True), self.start, self.end, self.goal_rows, self.goal_point,
@@ -879,7 +892,12 @@ class ChompEngine:
         self._persist_unchecked = True  # join() reads the launch's status
 
     def persistent_status(self) -> dict:
-        return ops.plan_persistent_status(self._persist_ws, self.S)
+        """{"failure", "scenes_finished", "scenes_planned", "activations"} of this engine's last run_persistent().  Waits for the launch
+        on the stream it was enqueued on, whatever stream is current now.  ValueError before the first launch: there is no status."""
+        if self.__dict__.get("_persist_ws") is None:
+            raise ValueError("persistent_status: this engine has made no persistent launch (run_persistent) yet")
+        with torch.cuda.stream(self._persist_stream):
+            return ops.plan_persistent_status(self._persist_ws, self.S)
 
     # ---------------------------------------------------------------------------------------------
     _STATE = ("traj", "end", "goal_rows", "goal_point", "goal_idx", "learner_state", "info", "active", "goal_cost", "goal_col",

@@ -106,10 +106,12 @@ def test_persistent_launch_equals_the_iterations_it_replaces(dev, alg, S, G, max
     _same(a, b, "second launch")
 
 
-def test_persistent_launch_fixed_goal_iterations_and_early_stop(dev):
+@pytest.mark.parametrize("alg", ["MD", "Baseline"])
+def test_persistent_launch_fixed_goal_iterations_and_early_stop(dev, alg):
     """A whole plan's iteration sequence: cfg.optim_steps goal-selecting iterations, then fixed-goal ones (layer + step only), with
-    early stop (planner.py:626: a scene that terminates leaves the loop; active[s] <- 0)."""
-    a, b = _pair(dev, 7, 8, 30, "MD", cfg_over={"optim_steps": 9, "extra_smooth_steps": 6})
+    early stop (planner.py:626: a scene that terminates leaves the loop; active[s] <- 0).  "Baseline" never selects: all fifteen
+    iterations are fixed-goal ones, and the launch gets a learner record without a rule (tests/test_gpu_persistent_paths.py)."""
+    a, b = _pair(dev, 7, 8, 30, alg, cfg_over={"optim_steps": 9, "extra_smooth_steps": 6})
     for e in (a, b):
         e.select_initial_goal()
         e.pose_hand_over(True)
