@@ -10,9 +10,6 @@
 //                   flattened as its 64 elements.  The last pass turns the squared distances into the float32 value in the pool.
 // Intermediates: one word per node and pass (two 16-bit channels) at workspace[first_workgroup * 256 + L], two buffers.
 // The arithmetic is omg_fusion_body.h: the bits of fusion.py.  Plain loads and stores only; the stream orders the passes.
-#include <utility>
-#include <vector>
-
 #include "omg_mesh_common.h"
 #include "omg_fusion_body.h"
 
@@ -28,34 +25,20 @@ static_assert(OMGX_FUSION_FREE == FUSION_FREE && OMGX_FUSION_SURFACE == FUSION_S
 
 namespace {
 
-// The volume of this workgroup: the last one whose first_workgroup is <= blockIdx.x (uniform).
-__device__ __forceinline__ int fuse_volume(const omgx_mesh* __restrict__ meshes, int num_meshes) {
-    int lo = 0, hi = num_meshes - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (meshes[mid].first_workgroup <= (int64_t)blockIdx.x) lo = mid; else hi = mid - 1;
-    }
-    return lo;
-}
-
 __global__ __launch_bounds__(FUSE_BLOCK) void k_carve_views(const omgx_mesh* __restrict__ meshes, int num_meshes,
                                                             const double* __restrict__ views, const int32_t* __restrict__ view_range,
                                                             const int64_t* __restrict__ state_begin, const double* __restrict__ depth,
                                                             int H, int W, double band, double near, int merge, uint8_t* __restrict__ state) {
-    const int m = fuse_volume(meshes, num_meshes);
+    // (lanes past the last node of the volume repeat it and write nothing)
+    const volume_node n = volume_locate(meshes, num_meshes, blockIdx.x, threadIdx.x, FUSE_BLOCK);
+    const int m = n.m;
     const omgx_mesh ms = meshes[m];
-    const int dy = ms.dims[1], dz = ms.dims[2];
-    const int64_t total = (int64_t)ms.dims[0] * dy * dz;
-    const int64_t id = ((int64_t)blockIdx.x - ms.first_workgroup) * FUSE_BLOCK + threadIdx.x;
-    const bool live = id < total;
-    // (a volume has at most 2^31 - 1 nodes: 32-bit division; lanes past the last node repeat it and write nothing)
-    const uint32_t idc = (uint32_t)(live ? id : total - 1), plane = (uint32_t)dz * (uint32_t)dy, rest = idc % plane;
     double p[3];
-    fusion_node_point(ms.origin, ms.delta, ms.sample_offset, (int)(idc / plane), (int)(rest / (uint32_t)dz), (int)(rest % (uint32_t)dz), p);
+    volume_node_point(ms, n.idc, p);
     uint8_t* __restrict__ mine = state + state_begin[m];
     bool surface = false, free_ = false;
     if (merge) {
-        const uint8_t s = mine[idc];
+        const uint8_t s = mine[n.idc];
         surface = s == FUSION_SURFACE, free_ = s == FUSION_FREE;
     }
     const int v0 = view_range[2 * m], v1 = v0 + view_range[2 * m + 1];
@@ -64,27 +47,24 @@ __global__ __launch_bounds__(FUSE_BLOCK) void k_carve_views(const omgx_mesh* __r
         const int says = fusion_view_says(views + (int64_t)v * 16, depth + v * image, H, W, p, band, near);
         surface = surface || says == FUSION_SAYS_SURFACE, free_ = free_ || says == FUSION_SAYS_FREE;
     }
-    if (live) mine[id] = fusion_state(surface, free_);
+    if (n.live) mine[n.id] = fusion_state(surface, free_);
 }
 
 __global__ __launch_bounds__(FUSE_BLOCK) void k_fusion_rows(const omgx_mesh* __restrict__ meshes, int num_meshes,
                                                             const uint8_t* __restrict__ state, const int64_t* __restrict__ state_begin,
                                                             int radius, int unknown_occupied, uint32_t* __restrict__ dst) {
     __shared__ uint32_t seeds[FUSE_BLOCK + 2 * OMGX_FUSION_MAX_RADIUS];
-    const int m = fuse_volume(meshes, num_meshes);
-    const omgx_mesh* __restrict__ ms = meshes + m;
-    const int dz = ms->dims[2];
-    const int64_t total = (int64_t)ms->dims[0] * ms->dims[1] * dz, wg0 = ms->first_workgroup;
-    const int64_t id0 = ((int64_t)blockIdx.x - wg0) * FUSE_BLOCK;
-    const int64_t lo = max(id0 - radius, (int64_t)0), hi = min(id0 + FUSE_BLOCK + radius, total);  // hi - lo <= 256 + 2 * radius
+    const volume_node n = volume_locate(meshes, num_meshes, blockIdx.x, threadIdx.x, FUSE_BLOCK);
+    const int dz = meshes[n.m].dims[2];
+    const int64_t wg0 = meshes[n.m].first_workgroup;
+    const int64_t lo = max(n.id0 - radius, (int64_t)0), hi = min(n.id0 + FUSE_BLOCK + radius, n.total);  // hi - lo <= 256 + 2 * radius
     const uint32_t r2 = (uint32_t)(radius * radius);
-    const uint8_t* __restrict__ mine = state + state_begin[m];
+    const uint8_t* __restrict__ mine = state + state_begin[n.m];
     for (int64_t t = lo + threadIdx.x; t < hi; t += FUSE_BLOCK) seeds[t - lo] = fusion_seed(fusion_occupied(mine[t], unknown_occupied), r2);
     __syncthreads();
-    const int64_t id = id0 + threadIdx.x;
-    if (id >= total) return;
+    if (!n.live) return;
     // the window stays inside the node's row, so inside [lo, hi)
-    dst[wg0 * FUSE_BLOCK + id] = fusion_line_pass(seeds + (id - lo), 1, (int)((uint32_t)id % (uint32_t)dz), dz, radius, r2);
+    dst[wg0 * FUSE_BLOCK + n.id] = fusion_line_pass(seeds + (n.id - lo), 1, (int)((uint32_t)n.id % (uint32_t)dz), dz, radius, r2);
 }
 
 // axis 1: lines along y, for every x the elements z; axis 0: lines along x, the elements (y, z) flattened.  blockIdx.y: the
@@ -163,19 +143,12 @@ extern "C" int omgx_carve_views(const omgx_mesh* volumes, const omgx_mesh* h_vol
     if (M < 0 || V < 0 || state_elems < 0 || !std::isfinite(band) || !std::isfinite(near)) return OMGX_ERR_INVALID;
     if (M > 0 && (!volumes || !h_volumes || !view_range || !h_view_range || !state_begin || !h_state_begin || !state)) return OMGX_ERR_INVALID;
     if (V > 0 && (!views || !h_views || !depth || H < 1 || W < 1)) return OMGX_ERR_INVALID;
-    for (int64_t x = 0; x < (int64_t)V * 16; ++x)
-        if (!std::isfinite(h_views[x]) || (x % 16 < 2 && h_views[x] == 0.0)) return OMGX_ERR_INVALID;
-    const bool big_images = V > 0 && (int64_t)V * H > 0x7fffffffll / W;  // V * H * W > 2^31 - 1
-    if (M == 0) return big_images ? OMGX_ERR_UNSUPPORTED : OMGX_OK;
+    const int images = mesh_check_views(h_views, V, H, W, h_view_range, M);
+    if (images == OMGX_ERR_INVALID || M == 0) return images;
     int64_t wg = 0;
-    const int status = mesh_check_volumes(h_volumes, M, -1, FUSE_BLOCK, &wg);
+    const int status = mesh_check_batch(h_volumes, M, h_state_begin, state_elems, -1, FUSE_BLOCK, &wg);
     if (status == OMGX_ERR_INVALID) return status;
-    for (int32_t m = 0; m < M; ++m) {
-        const int64_t first = h_view_range[2 * m], count = h_view_range[2 * m + 1];
-        if (first < 0 || count < 0 || first + count > V) return OMGX_ERR_INVALID;
-    }
-    if (mesh_check_state_ranges(h_volumes, M, h_state_begin, state_elems) != OMGX_OK) return OMGX_ERR_INVALID;
-    if (status != OMGX_OK || big_images) return OMGX_ERR_UNSUPPORTED;
+    if (status != OMGX_OK || images != OMGX_OK) return OMGX_ERR_UNSUPPORTED;
     hipLaunchKernelGGL(k_carve_views, dim3((unsigned)wg), dim3(FUSE_BLOCK), 0, (hipStream_t)stream, volumes, (int)M, views, view_range, state_begin,
                        depth, (int)H, (int)W, band, near, (int)merge, state);
     OMGX_CHECK_LAUNCH("k_carve_views");
@@ -199,12 +172,8 @@ extern "C" int omgx_distance_transform(const uint8_t* state, int64_t state_elems
     if (M > 0 && (!state || !state_begin || !h_state_begin || !volumes || !h_volumes || !workspace || !pool)) return OMGX_ERR_INVALID;
     if (M == 0) return check_radius(radius);
     int64_t wg = 0;
-    const int status = mesh_check_volumes(h_volumes, M, pool_elems, FUSE_BLOCK, &wg);
-    if (status == OMGX_ERR_INVALID) return status;
-    if (mesh_check_state_ranges(h_volumes, M, h_state_begin, state_elems) != OMGX_OK) return OMGX_ERR_INVALID;
-    std::vector<std::pair<int64_t, int64_t>> in_pool;
-    for (int32_t m = 0; m < M; ++m) in_pool.emplace_back(h_volumes[m].out_offset, mesh_node_count(h_volumes[m]));
-    if (mesh_ranges_overlap(in_pool)) return OMGX_ERR_INVALID;
+    const int status = mesh_check_batch(h_volumes, M, h_state_begin, state_elems, pool_elems, FUSE_BLOCK, &wg);
+    if (status == OMGX_ERR_INVALID || mesh_pool_ranges_overlap(h_volumes, M)) return OMGX_ERR_INVALID;
     if (status != OMGX_OK || check_radius(radius) != OMGX_OK) return OMGX_ERR_UNSUPPORTED;
     uint32_t* first = (uint32_t*)workspace;
     uint32_t* second = first + wg * FUSE_BLOCK;

@@ -7,6 +7,8 @@
 #include <cmath>
 #include <cstdint>
 
+#include "omg_volume_body.h"  // fusion_node_point
+
 #if defined(__HIPCC__)
 #define FUSION_HD __host__ __device__ __forceinline__
 #else
@@ -22,13 +24,6 @@
 #define FUSION_SAYS_NOTHING 0
 #define FUSION_SAYS_FREE 1
 #define FUSION_SAYS_SURFACE 2
-
-// p = origin + ((i, j, k) + sample_offset) * delta, per component.
-FUSION_HD void fusion_node_point(const double* origin, double delta, double sample_offset, int i, int j, int k, double* p) {
-    p[0] = origin[0] + ((double)i + sample_offset) * delta;
-    p[1] = origin[1] + ((double)j + sample_offset) * delta;
-    p[2] = origin[2] + ((double)k + sample_offset) * delta;
-}
 
 // What the view (fx, fy, cx, cy, rows of cam_from_grid) with the image img [H][W] says about the point p.  The row and the
 // column are 0 unless the pixel lies inside the image, so that no point can form an address outside it.

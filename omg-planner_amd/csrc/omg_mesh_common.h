@@ -1,6 +1,7 @@
 // omg_mesh_common.h — what the translation units that take omgx_mesh records share: the face tile that k_mesh_sdf and
 // k_mesh_raycast stage in LDS (omg_mesh_sdf.hip, omg_grasp.hip), the checks on one host omgx_mesh record (include/omg_hip.h
-// sections 12 and 13) and on a batch of volumes (omg_surface.hip, omg_fusion.hip, omg_segment.hip: sections 16 to 18).
+// sections 12 and 13), on a batch of volumes and on a view table (omg_surface.hip, omg_fusion.hip, omg_segment.hip, omg_plane.hip,
+// omg_tsdf.hip: sections 16 to 20), and through omg_volume_body.h the way a workgroup of their kernels finds its volume.
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -9,6 +10,7 @@
 #include <vector>
 
 #include "omg_host.h"
+#include "omg_volume_body.h"  // a workgroup's volume and a thread's node of it, on the device
 
 // Faces of a mesh staged in LDS at a time (omgx_mesh_sdf_tile()), 9 doubles each: a, b, c.
 #define OMGX_MESH_FACE_TILE 256
@@ -93,4 +95,33 @@ static inline int mesh_check_state_ranges(const omgx_mesh* h_volumes, int32_t M,
         r.emplace_back(begin, nodes);
     }
     return mesh_ranges_overlap(r) ? OMGX_ERR_INVALID : OMGX_OK;
+}
+
+// mesh_check_volumes, then mesh_check_state_ranges -> OMGX_OK, OMGX_ERR_INVALID, or the records' OMGX_ERR_UNSUPPORTED, which
+// comes last: the caller reports it only after the OMGX_ERR_INVALID of its own further checks.
+static inline int mesh_check_batch(const omgx_mesh* h_volumes, int32_t M, const int64_t* h_state_begin, int64_t state_elems,
+                                   int64_t pool_elems, int per_workgroup, int64_t* workgroups) {
+    const int status = mesh_check_volumes(h_volumes, M, pool_elems, per_workgroup, workgroups);
+    if (status == OMGX_ERR_INVALID) return status;
+    return mesh_check_state_ranges(h_volumes, M, h_state_begin, state_elems) != OMGX_OK ? OMGX_ERR_INVALID : status;
+}
+
+// Do two of the volumes overlap in the pool they are written to (at out_offset)?
+static inline bool mesh_pool_ranges_overlap(const omgx_mesh* h_volumes, int32_t M) {
+    std::vector<std::pair<int64_t, int64_t>> in_pool;
+    for (int32_t m = 0; m < M; ++m) in_pool.emplace_back(h_volumes[m].out_offset, mesh_node_count(h_volumes[m]));
+    return mesh_ranges_overlap(in_pool);
+}
+
+// The host copies of a view table [V][16] (fx, fy, cx, cy, rows of cam_from_grid) and of the volumes' view ranges [M][2] (first,
+// count) -> OMGX_ERR_INVALID for a field that is not finite, a focal length of zero or a range outside [0, V]; then
+// OMGX_ERR_UNSUPPORTED for V * H * W > 2^31 - 1, which the caller reports after its other checks; OMGX_OK.  (V > 0: H, W >= 1)
+static inline int mesh_check_views(const double* h_views, int32_t V, int32_t H, int32_t W, const int32_t* h_view_range, int32_t M) {
+    for (int64_t x = 0; x < (int64_t)V * 16; ++x)
+        if (!std::isfinite(h_views[x]) || (x % 16 < 2 && h_views[x] == 0.0)) return OMGX_ERR_INVALID;
+    for (int32_t m = 0; m < M; ++m) {
+        const int64_t first = h_view_range[2 * m], count = h_view_range[2 * m + 1];
+        if (first < 0 || count < 0 || first + count > V) return OMGX_ERR_INVALID;
+    }
+    return V > 0 && (int64_t)V * H > 0x7fffffffll / W ? OMGX_ERR_UNSUPPORTED : OMGX_OK;
 }

@@ -19,21 +19,12 @@ __global__ __launch_bounds__(MSDF_BLOCK) void k_mesh_sdf(const double* __restric
                                                           const omgx_mesh* __restrict__ meshes, int num_meshes,
                                                           float* __restrict__ out) {
     __shared__ double tile[OMGX_MESH_FACE_TILE * 9];
-    // the mesh of this workgroup: the last one whose first_workgroup is <= blockIdx.x (uniform: scalar loads)
-    int lo = 0, hi = num_meshes - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (meshes[mid].first_workgroup <= (int64_t)blockIdx.x) lo = mid; else hi = mid - 1;
-    }
-    const omgx_mesh ms = meshes[lo];
-    const int dy = ms.dims[1], dz = ms.dims[2];
-    const int64_t total = (int64_t)ms.dims[0] * dy * dz;
-    const int64_t id = ((int64_t)blockIdx.x - ms.first_workgroup) * MSDF_BLOCK + threadIdx.x;
-    const int64_t idc = id < total ? id : total - 1;  // idle lanes of the last workgroup redo the last node and store nothing
-    const int k = (int)(idc % dz), j = (int)((idc / dz) % dy), i = (int)(idc / ((int64_t)dz * dy));
-    const double px = ms.origin[0] + ((double)i + ms.sample_offset) * ms.delta;
-    const double py = ms.origin[1] + ((double)j + ms.sample_offset) * ms.delta;
-    const double pz = ms.origin[2] + ((double)k + ms.sample_offset) * ms.delta;
+    // the mesh of this workgroup (uniform: scalar loads); idle lanes of the last workgroup redo the last node and store nothing
+    const volume_node n = volume_locate(meshes, num_meshes, blockIdx.x, threadIdx.x, MSDF_BLOCK);
+    const omgx_mesh ms = meshes[n.m];
+    double p[3];
+    volume_node_point(ms, n.idc, p);  // (a mesh has at most 2^31 nodes: the index and the 32-bit division hold)
+    const double px = p[0], py = p[1], pz = p[2];
 
     const double* __restrict__ mv = verts + (int64_t)ms.vert_begin * 3;
     const int32_t* __restrict__ mf = faces + (int64_t)ms.face_begin * 3;
@@ -47,10 +38,10 @@ __global__ __launch_bounds__(MSDF_BLOCK) void k_mesh_sdf(const double* __restric
             mesh_sdf_pair(px, py, pz, tile + q * 9, best, wsum);
         }
     }
-    if (id < total) {
+    if (n.live) {
         const double w = wsum * 0.15915494309189535;  // (1 / 4 pi) * 2 * sum
         const double d = sqrt(best);
-        out[ms.out_offset + id] = (float)(fabs(w) > 0.5 ? -d : d);
+        out[ms.out_offset + n.id] = (float)(fabs(w) > 0.5 ? -d : d);
     }
 }
 

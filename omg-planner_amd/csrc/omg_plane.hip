@@ -14,11 +14,7 @@
 //   k_plane_mask        one thread per pixel;  k_plane_volumes  one thread per node of a ragged batch of omgx_mesh records
 // The arithmetic is omg_plane_body.h: the bits of planes.py.  Integer atomics only, so no result depends on the order of arrival;
 // no spin-waits, no flags: the stream is the only barrier between the launches.
-#include <utility>
-#include <vector>
-
 #include "omg_mesh_common.h"
-#include "omg_fusion_body.h"
 #include "omg_plane_body.h"
 
 #pragma clang fp contract(off)
@@ -213,20 +209,12 @@ __global__ __launch_bounds__(PL_BLOCK) void k_plane_mask(const double* __restric
 
 __global__ __launch_bounds__(PL_BLOCK) void k_plane_volumes(const omgx_mesh* __restrict__ meshes, int num_meshes,
                                                             const double* __restrict__ planes, float* __restrict__ pool) {
-    int lo = 0, hi = num_meshes - 1;  // the volume of this workgroup: the last one whose first_workgroup is <= blockIdx.x (uniform)
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (meshes[mid].first_workgroup <= (int64_t)blockIdx.x) lo = mid; else hi = mid - 1;
-    }
-    const omgx_mesh ms = meshes[lo];
-    const int dy = ms.dims[1], dz = ms.dims[2];
-    const int64_t total = (int64_t)ms.dims[0] * dy * dz;
-    const int64_t id = ((int64_t)blockIdx.x - ms.first_workgroup) * PL_BLOCK + threadIdx.x;
-    if (id >= total) return;
-    const uint32_t idc = (uint32_t)id, slab = (uint32_t)dz * (uint32_t)dy, rest = idc % slab;  // (at most 2^31 - 1 nodes)
+    const volume_node n = volume_locate(meshes, num_meshes, blockIdx.x, threadIdx.x, PL_BLOCK);
+    if (!n.live) return;
+    const omgx_mesh ms = meshes[n.m];
     double p[3];
-    fusion_node_point(ms.origin, ms.delta, ms.sample_offset, (int)(idc / slab), (int)(rest / (uint32_t)dz), (int)(rest % (uint32_t)dz), p);
-    pool[ms.out_offset + id] = plane_halfspace(planes + (int64_t)lo * 4, p);
+    volume_node_point(ms, n.idc, p);
+    pool[ms.out_offset + n.id] = plane_halfspace(planes + (int64_t)n.m * 4, p);
 }
 
 // What every entry point over images checks on the host -> OMGX_OK, OMGX_ERR_INVALID, or OMGX_ERR_UNSUPPORTED above 2^31 - 1
@@ -324,9 +312,7 @@ extern "C" int omgx_plane_volumes(const omgx_mesh* volumes, const omgx_mesh* h_v
     if (status == OMGX_ERR_INVALID) return status;
     for (int64_t x = 0; x < (int64_t)M * 4; ++x)
         if (!std::isfinite(h_planes[x])) return OMGX_ERR_INVALID;
-    std::vector<std::pair<int64_t, int64_t>> in_pool;
-    for (int32_t m = 0; m < M; ++m) in_pool.emplace_back(h_volumes[m].out_offset, mesh_node_count(h_volumes[m]));
-    if (mesh_ranges_overlap(in_pool)) return OMGX_ERR_INVALID;
+    if (mesh_pool_ranges_overlap(h_volumes, M)) return OMGX_ERR_INVALID;
     if (status != OMGX_OK) return OMGX_ERR_UNSUPPORTED;
     hipLaunchKernelGGL(k_plane_volumes, dim3((unsigned)wg), dim3(PL_BLOCK), 0, (hipStream_t)stream, volumes, (int)M, planes, pool);
     OMGX_CHECK_LAUNCH("k_plane_volumes");

@@ -16,8 +16,6 @@
 // lanes of a wave that share a component reduced first.  k_component_states: one thread per node of an output volume.
 // The per-node rules are omg_segment_body.h.  No spin-waits, no flags: the stream is the only barrier between the launches.
 #include <climits>
-#include <utility>
-#include <vector>
 
 #include "omg_mesh_common.h"
 #include "omg_segment_body.h"
@@ -32,32 +30,18 @@ static_assert(OMGX_FUSION_FREE == SEG_FREE && OMGX_FUSION_SURFACE == SEG_SURFACE
 
 namespace {
 
-// This thread's node: the volume of the workgroup (the last one whose first_workgroup is <= blockIdx.x; uniform), the node's
-// linear index and coordinates.  Lanes past the last node are not live and repeat it.
-struct seg_node {
-    int m;
+// This thread's node (id0: the run's first node), its volume's record and its coordinates.  Lanes past the last node are not
+// live and repeat it.
+struct seg_node : volume_node {
     const omgx_mesh* ms;
-    int64_t id0, id, total;  // the run's first node, this node, the volume's nodes
-    bool live;
     int i, j, k;
 };
 
 __device__ __forceinline__ seg_node seg_locate(const omgx_mesh* __restrict__ meshes, int num_meshes) {
-    int lo = 0, hi = num_meshes - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (meshes[mid].first_workgroup <= (int64_t)blockIdx.x) lo = mid; else hi = mid - 1;
-    }
     seg_node t;
-    t.m = lo, t.ms = meshes + lo;
-    const int dy = t.ms->dims[1], dz = t.ms->dims[2];
-    t.total = (int64_t)t.ms->dims[0] * dy * dz;
-    t.id0 = ((int64_t)blockIdx.x - t.ms->first_workgroup) * SEG_BLOCK;
-    t.id = t.id0 + threadIdx.x;
-    t.live = t.id < t.total;
-    // (a volume has at most 2^31 - 1 nodes: 32-bit division)
-    const uint32_t idc = (uint32_t)(t.live ? t.id : t.total - 1), plane = (uint32_t)dz * (uint32_t)dy, rest = idc % plane;
-    t.i = (int)(idc / plane), t.j = (int)(rest / (uint32_t)dz), t.k = (int)(rest % (uint32_t)dz);
+    static_cast<volume_node&>(t) = volume_locate(meshes, num_meshes, blockIdx.x, threadIdx.x, SEG_BLOCK);
+    t.ms = meshes + t.m;
+    volume_decode(t.ms->dims, t.idc, &t.i, &t.j, &t.k);
     return t;
 }
 
@@ -257,10 +241,8 @@ extern "C" int omgx_label_components(const uint8_t* state, int64_t state_elems, 
     if (M == 0) return OMGX_OK;
     if (!state || !state_begin || !h_state_begin || !volumes || !h_volumes || !workspace || !labels || !counts) return OMGX_ERR_INVALID;
     int64_t wg = 0;
-    const int status = mesh_check_volumes(h_volumes, M, -1, SEG_BLOCK, &wg);
-    if (status == OMGX_ERR_INVALID) return status;
-    if (mesh_check_state_ranges(h_volumes, M, h_state_begin, state_elems) != OMGX_OK) return OMGX_ERR_INVALID;
-    if (status != OMGX_OK) return OMGX_ERR_UNSUPPORTED;
+    const int status = mesh_check_batch(h_volumes, M, h_state_begin, state_elems, -1, SEG_BLOCK, &wg);
+    if (status != OMGX_OK) return status;
     hipStream_t s = (hipStream_t)stream;
     int32_t* parent = (int32_t*)workspace;
     int32_t* totals = parent + wg * SEG_BLOCK;
@@ -290,9 +272,8 @@ extern "C" int omgx_component_records(const int32_t* labels, int64_t state_elems
     if (M == 0) return OMGX_OK;
     if (!labels || !state_begin || !h_state_begin || !volumes || !h_volumes || !comp_begin || !h_comp_begin) return OMGX_ERR_INVALID;
     int64_t wg = 0;
-    const int status = mesh_check_volumes(h_volumes, M, -1, SEG_BLOCK, &wg);
+    const int status = mesh_check_batch(h_volumes, M, h_state_begin, state_elems, -1, SEG_BLOCK, &wg);
     if (status == OMGX_ERR_INVALID) return status;
-    if (mesh_check_state_ranges(h_volumes, M, h_state_begin, state_elems) != OMGX_OK) return OMGX_ERR_INVALID;
     const int rows_status = check_comp_begin(h_comp_begin, M);
     if (rows_status == OMGX_ERR_INVALID || record_cap < h_comp_begin[M] || (h_comp_begin[M] > 0 && !records)) return OMGX_ERR_INVALID;
     if (status != OMGX_OK || rows_status != OMGX_OK) return OMGX_ERR_UNSUPPORTED;
@@ -319,10 +300,9 @@ extern "C" int omgx_component_states(const uint8_t* state, int64_t state_elems, 
     if (!state || !state_begin || !h_state_begin || !volumes || !h_volumes || !labels || !comp_begin || !h_comp_begin || !records) return OMGX_ERR_INVALID;
     if (!picks || !h_picks || !out_volumes || !h_out_volumes || !out_begin || !h_out_begin || !out_state) return OMGX_ERR_INVALID;
     int64_t wg = 0, out_wg = 0;
-    const int status = mesh_check_volumes(h_volumes, M, -1, SEG_BLOCK, &wg), out_status = mesh_check_volumes(h_out_volumes, K, -1, SEG_BLOCK, &out_wg);
+    const int status = mesh_check_batch(h_volumes, M, h_state_begin, state_elems, -1, SEG_BLOCK, &wg);
+    const int out_status = mesh_check_batch(h_out_volumes, K, h_out_begin, out_elems, -1, SEG_BLOCK, &out_wg);
     if (status == OMGX_ERR_INVALID || out_status == OMGX_ERR_INVALID) return OMGX_ERR_INVALID;
-    if (mesh_check_state_ranges(h_volumes, M, h_state_begin, state_elems) != OMGX_OK) return OMGX_ERR_INVALID;
-    if (mesh_check_state_ranges(h_out_volumes, K, h_out_begin, out_elems) != OMGX_OK) return OMGX_ERR_INVALID;
     const int rows_status = check_comp_begin(h_comp_begin, M);
     if (rows_status == OMGX_ERR_INVALID || num_records < h_comp_begin[M]) return OMGX_ERR_INVALID;
     for (int32_t k = 0; k < K; ++k) {

@@ -27,31 +27,22 @@ namespace {
 
 struct surf_thread {
     omgx_mesh ms;
-    int64_t id, total;  // this thread's sample of the volume, the volume's samples
-    int a[3];
+    int64_t id;         // this thread's sample of the volume
+    int a[3];           // its coordinates (lanes past the volume's last sample: the last one's)
     unsigned mask;      // corners inside
     bool active;        // the cell exists and has a vertex
     bool closed[3], open[3];  // crossing edges with / without their four cells
     float v[8];
 };
 
-// The volume of this workgroup (the last one whose first_workgroup is <= blockIdx.x; uniform) and this thread's flags.  Lanes
-// past the last sample of the volume flag nothing.
+// The volume of this workgroup (uniform) and this thread's flags.  Lanes past the last sample of the volume flag nothing.
 __device__ __forceinline__ void surf_flags(const float* __restrict__ pool, const omgx_mesh* __restrict__ meshes, int num_meshes,
                                            float level, surf_thread& t) {
-    int lo = 0, hi = num_meshes - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (meshes[mid].first_workgroup <= (int64_t)blockIdx.x) lo = mid; else hi = mid - 1;
-    }
-    t.ms = meshes[lo];
-    const int dy = t.ms.dims[1], dz = t.ms.dims[2];
-    t.total = (int64_t)t.ms.dims[0] * dy * dz;
-    t.id = ((int64_t)blockIdx.x - t.ms.first_workgroup) * SURF_BLOCK + threadIdx.x;
-    const bool live = t.id < t.total;
-    // (a volume has at most 2^31 - 1 samples: 32-bit division)
-    const uint32_t idc = (uint32_t)(live ? t.id : t.total - 1), plane = (uint32_t)dz * (uint32_t)dy, rest = idc % plane;
-    t.a[0] = (int)(idc / plane), t.a[1] = (int)(rest / (uint32_t)dz), t.a[2] = (int)(rest % (uint32_t)dz);
+    const volume_node n = volume_locate(meshes, num_meshes, blockIdx.x, threadIdx.x, SURF_BLOCK);
+    t.ms = meshes[n.m];
+    t.id = n.id;
+    const bool live = n.live;
+    volume_decode(t.ms.dims, n.idc, &t.a[0], &t.a[1], &t.a[2]);
     surface_load_corners(pool + t.ms.out_offset, t.ms.dims, t.a[0], t.a[1], t.a[2], t.v);
 #if defined(OMGX_SURFACE_ONE_LOAD)  // measurement build (tools/surface_timing.py --one-load): what the count step costs without its
     for (int c = 1; c < 8; ++c) t.v[c] = t.v[0];  // neighbour loads, the most that staging a tile in LDS could save; wrong meshes

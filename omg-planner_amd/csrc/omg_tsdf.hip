@@ -7,9 +7,6 @@
 //   k_tsdf_states     one thread per node: the pair's state byte (carve's layout)
 //   k_tsdf_blend      one thread per node: the pair blended into the distance transform's value in the pool, in place
 // The arithmetic is omg_tsdf_body.h: the bits of tsdf.py.  Plain loads and stores only; the stream is the only barrier.
-#include <utility>
-#include <vector>
-
 #include "omg_mesh_common.h"
 #include "omg_tsdf_body.h"
 
@@ -20,36 +17,15 @@ static_assert(TSDF_BLOCK == 256 && TSDF_BLOCK == OMGX_FUSION_NODES_PER_WORKGROUP
 
 namespace {
 
-// One thread's node: the volume of this workgroup (the last one whose first_workgroup is <= blockIdx.x: uniform), the node's
-// linear index, and whether the lane has a node at all.  Lanes past the last node repeat it and write nothing.
-struct tsdf_node {
-    int m;
-    uint32_t idc;  // (a volume has at most 2^31 - 1 nodes)
-    bool live;
-};
-
-__device__ __forceinline__ tsdf_node tsdf_locate(const omgx_mesh* __restrict__ meshes, int num_meshes) {
-    int lo = 0, hi = num_meshes - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (meshes[mid].first_workgroup <= (int64_t)blockIdx.x) lo = mid; else hi = mid - 1;
-    }
-    const omgx_mesh* __restrict__ ms = meshes + lo;
-    const int64_t total = (int64_t)ms->dims[0] * ms->dims[1] * ms->dims[2];
-    const int64_t id = ((int64_t)blockIdx.x - ms->first_workgroup) * TSDF_BLOCK + threadIdx.x;
-    return {lo, (uint32_t)(id < total ? id : total - 1), id < total};
-}
-
 __global__ __launch_bounds__(TSDF_BLOCK) void k_tsdf_integrate(const omgx_mesh* __restrict__ meshes, int num_meshes,
                                                                const double* __restrict__ views, const int32_t* __restrict__ view_range,
                                                                const int64_t* __restrict__ state_begin, const double* __restrict__ depth,
                                                                int H, int W, const double* __restrict__ weights, double trunc, double near,
                                                                double wmax, int merge, float* __restrict__ tsdf, float* __restrict__ weight) {
-    const tsdf_node n = tsdf_locate(meshes, num_meshes);
+    const volume_node n = volume_locate(meshes, num_meshes, blockIdx.x, threadIdx.x, TSDF_BLOCK);
     const omgx_mesh ms = meshes[n.m];
-    const uint32_t dz = (uint32_t)ms.dims[2], plane = dz * (uint32_t)ms.dims[1], rest = n.idc % plane;
     double p[3];
-    fusion_node_point(ms.origin, ms.delta, ms.sample_offset, (int)(n.idc / plane), (int)(rest / dz), (int)(rest % dz), p);
+    volume_node_point(ms, n.idc, p);
     const int64_t at = state_begin[n.m] + n.idc;
     double D, Wt;
     tsdf_start(merge != 0, merge ? tsdf[at] : 0.0f, merge ? weight[at] : 0.0f, &D, &Wt);
@@ -67,7 +43,7 @@ __global__ __launch_bounds__(TSDF_BLOCK) void k_tsdf_integrate(const omgx_mesh* 
 __global__ __launch_bounds__(TSDF_BLOCK) void k_tsdf_states(const omgx_mesh* __restrict__ meshes, int num_meshes,
                                                             const int64_t* __restrict__ state_begin, const float* __restrict__ tsdf,
                                                             const float* __restrict__ weight, float min_weight, uint8_t* __restrict__ state) {
-    const tsdf_node n = tsdf_locate(meshes, num_meshes);
+    const volume_node n = volume_locate(meshes, num_meshes, blockIdx.x, threadIdx.x, TSDF_BLOCK);
     const int64_t at = state_begin[n.m] + n.idc;
     const uint8_t s = tsdf_state(tsdf[at], weight[at], min_weight);
     if (n.live) state[at] = s;
@@ -77,22 +53,13 @@ __global__ __launch_bounds__(TSDF_BLOCK) void k_tsdf_blend(const omgx_mesh* __re
                                                            const int64_t* __restrict__ state_begin, const float* __restrict__ tsdf,
                                                            const float* __restrict__ weight, double trunc, float min_weight,
                                                            float* __restrict__ pool) {
-    const tsdf_node n = tsdf_locate(meshes, num_meshes);
+    const volume_node n = volume_locate(meshes, num_meshes, blockIdx.x, threadIdx.x, TSDF_BLOCK);
     const int64_t at = state_begin[n.m] + n.idc, out = meshes[n.m].out_offset + n.idc;
     const float v = tsdf_blend(tsdf[at], weight[at], pool[out], trunc, min_weight);
     if (n.live) pool[out] = v;
 }
 
 bool positive(double x, bool may_be_inf) { return x > 0.0 && (std::isfinite(x) || (may_be_inf && std::isinf(x))); }
-
-// What the three entry points check alike: the records, their prefix table, and the pairs' ranges inside [0, elems) without
-// overlap -> OMGX_OK, OMGX_ERR_INVALID, or OMGX_ERR_UNSUPPORTED (an invalid field of any record first).
-int check_batch(const omgx_mesh* h_volumes, int32_t M, const int64_t* h_state_begin, int64_t elems, int64_t pool_elems, int64_t* wg) {
-    const int status = mesh_check_volumes(h_volumes, M, pool_elems, TSDF_BLOCK, wg);
-    if (status == OMGX_ERR_INVALID) return status;
-    if (mesh_check_state_ranges(h_volumes, M, h_state_begin, elems) != OMGX_OK) return OMGX_ERR_INVALID;
-    return status;
-}
 
 }  // namespace
 
@@ -106,21 +73,15 @@ extern "C" int omgx_tsdf_integrate(const omgx_mesh* volumes, const omgx_mesh* h_
     if (M > 0 && (!volumes || !h_volumes || !view_range || !h_view_range || !state_begin || !h_state_begin || !tsdf || !weight)) return OMGX_ERR_INVALID;
     if (V > 0 && (!views || !h_views || !depth || H < 1 || W < 1)) return OMGX_ERR_INVALID;
     if ((weights != nullptr) != (h_weights != nullptr)) return OMGX_ERR_INVALID;
-    for (int64_t x = 0; x < (int64_t)V * 16; ++x)
-        if (!std::isfinite(h_views[x]) || (x % 16 < 2 && h_views[x] == 0.0)) return OMGX_ERR_INVALID;
+    const int images = mesh_check_views(h_views, V, H, W, h_view_range, M);
+    if (images == OMGX_ERR_INVALID) return images;
     for (int32_t v = 0; h_weights && v < V; ++v)
         if (!std::isfinite(h_weights[v]) || h_weights[v] < 0.0) return OMGX_ERR_INVALID;
-    const bool big_images = V > 0 && (int64_t)V * H > 0x7fffffffll / W;  // V * H * W > 2^31 - 1
-    if (M == 0) return big_images ? OMGX_ERR_UNSUPPORTED : OMGX_OK;
+    if (M == 0) return images;
     int64_t wg = 0;
-    const int status = mesh_check_volumes(h_volumes, M, -1, TSDF_BLOCK, &wg);
+    const int status = mesh_check_batch(h_volumes, M, h_state_begin, elems, -1, TSDF_BLOCK, &wg);
     if (status == OMGX_ERR_INVALID) return status;
-    for (int32_t m = 0; m < M; ++m) {
-        const int64_t first = h_view_range[2 * m], count = h_view_range[2 * m + 1];
-        if (first < 0 || count < 0 || first + count > V) return OMGX_ERR_INVALID;
-    }
-    if (mesh_check_state_ranges(h_volumes, M, h_state_begin, elems) != OMGX_OK) return OMGX_ERR_INVALID;
-    if (status != OMGX_OK || big_images) return OMGX_ERR_UNSUPPORTED;
+    if (status != OMGX_OK || images != OMGX_OK) return OMGX_ERR_UNSUPPORTED;
     hipLaunchKernelGGL(k_tsdf_integrate, dim3((unsigned)wg), dim3(TSDF_BLOCK), 0, (hipStream_t)stream, volumes, (int)M, views, view_range,
                        state_begin, depth, (int)H, (int)W, weights, trunc, near, wmax, (int)merge, tsdf, weight);
     OMGX_CHECK_LAUNCH("k_tsdf_integrate");
@@ -135,7 +96,7 @@ extern "C" int omgx_tsdf_states(const float* tsdf, const float* weight, int64_t 
     if (M > 0 && (!tsdf || !weight || !state_begin || !h_state_begin || !volumes || !h_volumes || !state)) return OMGX_ERR_INVALID;
     if (M == 0) return OMGX_OK;
     int64_t wg = 0;
-    const int status = check_batch(h_volumes, M, h_state_begin, elems, -1, &wg);
+    const int status = mesh_check_batch(h_volumes, M, h_state_begin, elems, -1, TSDF_BLOCK, &wg);
     if (status != OMGX_OK) return status;
     hipLaunchKernelGGL(k_tsdf_states, dim3((unsigned)wg), dim3(TSDF_BLOCK), 0, (hipStream_t)stream, volumes, (int)M, state_begin, tsdf, weight,
                        min_weight, state);
@@ -151,11 +112,8 @@ extern "C" int omgx_tsdf_blend(const float* tsdf, const float* weight, int64_t e
     if (M > 0 && (!tsdf || !weight || !state_begin || !h_state_begin || !volumes || !h_volumes || !pool)) return OMGX_ERR_INVALID;
     if (M == 0) return OMGX_OK;
     int64_t wg = 0;
-    const int status = check_batch(h_volumes, M, h_state_begin, elems, pool_elems, &wg);
-    if (status == OMGX_ERR_INVALID) return status;
-    std::vector<std::pair<int64_t, int64_t>> in_pool;
-    for (int32_t m = 0; m < M; ++m) in_pool.emplace_back(h_volumes[m].out_offset, mesh_node_count(h_volumes[m]));
-    if (mesh_ranges_overlap(in_pool)) return OMGX_ERR_INVALID;
+    const int status = mesh_check_batch(h_volumes, M, h_state_begin, elems, pool_elems, TSDF_BLOCK, &wg);
+    if (status == OMGX_ERR_INVALID || mesh_pool_ranges_overlap(h_volumes, M)) return OMGX_ERR_INVALID;
     if (status != OMGX_OK) return status;
     hipLaunchKernelGGL(k_tsdf_blend, dim3((unsigned)wg), dim3(TSDF_BLOCK), 0, (hipStream_t)stream, volumes, (int)M, state_begin, tsdf, weight,
                        trunc, min_weight, pool);

@@ -557,7 +557,7 @@ class DeviceScenes:
             raise _lib.OmgHipError("reach must be finite and not negative")
         min_weight = _tsdf_positive("min_weight", min_weight)
         volumes = [(origin, delta, "centre", dims) for origin, delta, dims in layouts]
-        _, _, _, _, _, _, trunc, wmax = _tsdf_arguments(volumes, views, view_range, depth, trunc, near, weights, wmax, None)
+        _, _, _, _, trunc, wmax = _tsdf_arguments(volumes, views, view_range, depth, trunc, near, weights, wmax, None)
         radius = _fusion_radius(max(_fu.obstacle_radius(reach, float(delta)) for _, delta, _ in layouts))
         depth = _masked_depth(depth, free_mask)
         if depth.device != self.pool.device:
@@ -1428,26 +1428,80 @@ def surface_mesh(grid: torch.Tensor, origin, delta, sample: str = "centre", leve
     return verts, faces, int(open_edges[0])
 
 
+class _VolumeBatch:
+    """The volumes of a launch over a ragged batch, checked on the host before any tensor is touched: rec (omgx_mesh records), nodes
+    (int64 [M]), begin (state_begin int64 [M]) and M.  volumes: what surface_records takes (the prefix table is the same: 256 nodes
+    per workgroup), or [] for an empty launch; a layout without its fifth field, the element offset in the pool, lies behind the
+    layout before it (the first at 0).  The records and state_begin go to a device (on) once, when a launch first needs them there.
+    like: a batch of the same volumes at other pool offsets, whose state_begin this one shares, uploads included."""
+
+    def __init__(self, volumes, state_begin=None, like: "_VolumeBatch | None" = None):
+        assert _lib.FUSION_NODES_PER_WORKGROUP == _lib.SURFACE_NODES_PER_WORKGROUP == _lib.PLANE_NODES_PER_WORKGROUP
+        rec = volumes if isinstance(volumes, C.Array) else [tuple(v) for v in volumes]
+        if not isinstance(rec, C.Array):
+            at = 0
+            for m, v in enumerate(rec):
+                if len(v) == 4:
+                    rec[m] = v + (at,)
+                if len(rec[m]) != 5:
+                    raise _lib.OmgHipError(f"volume {m}: (origin, delta, sample, dims[, offset]), got {len(v)} fields")
+                at = int(rec[m][4]) + int(np.prod([int(d) for d in np.asarray(v[3]).reshape(-1)]))
+        self.rec = surface_records(rec) if len(rec) else (_lib.Mesh * 0)()
+        self.M = len(self.rec)
+        self.nodes = np.array([int(r.dims[0]) * int(r.dims[1]) * int(r.dims[2]) for r in self.rec], np.int64)
+        if like is not None:
+            state_begin = like.begin
+        self.begin = np.cumsum(self.nodes) - self.nodes if state_begin is None else np.ascontiguousarray(state_begin, np.int64).reshape(-1)
+        if len(self.begin) != self.M:
+            raise _lib.OmgHipError(f"state_begin must have one offset per volume ({self.M}), got {len(self.begin)}")
+        self._d_rec, self._d_begin, self._dev = {}, {} if like is None else like._d_begin, None  # uploads per device, the device in use
+
+    @classmethod
+    def of(cls, volumes, state_begin=None) -> "_VolumeBatch":
+        """A batch passes through as it is (with its own state_begin), anything else is made one."""
+        return volumes if isinstance(volumes, cls) else cls(volumes, state_begin)
+
+    def end(self) -> int:
+        """Elements that the state ranges reach to: what sizes a new state buffer."""
+        return int((self.begin + self.nodes).max()) if self.M else 0
+
+    def pool_end(self) -> int:
+        """Elements of the pool that the volumes reach to, 1 without any: what sizes a new pool."""
+        return max([int(r.out_offset) + int(n) for r, n in zip(self.rec, self.nodes)], default=1)
+
+    def on(self, dev) -> "_VolumeBatch":
+        """The device that the arguments below point into: the records and state_begin are uploaded when first asked for there."""
+        self._dev = torch.device(dev)
+        return self
+
+    def _device(self, cache, host):
+        if self.M and self._dev not in cache:
+            cache[self._dev] = _upload(host, self._dev)
+        return _ptr(cache.get(self._dev))
+
+    def host_args(self):
+        """(h_volumes, num_volumes) of an entry point; no pointer for an empty batch."""
+        return (C.cast(self.rec, C.c_void_p) if self.M else None, self.M)
+
+    def volume_args(self):
+        """(volumes, h_volumes, num_volumes) of an entry point."""
+        return (self._device(self._d_rec, self.rec), *self.host_args())
+
+    def begin_args(self):
+        """(state_begin, h_state_begin) of an entry point."""
+        return (self._device(self._d_begin, self.begin), C.c_void_p(self.begin.ctypes.data) if self.M else None)
+
+    def release(self, *scratch) -> None:
+        """After the last launch: the uploads, and the caller's scratch tensors, are in use by the current stream."""
+        for t in (self._d_rec.get(self._dev), self._d_begin.get(self._dev), *scratch):
+            if t is not None:
+                t.record_stream(torch.cuda.current_stream(self._dev))
+
+
 def _fusion_volumes(volumes, state_begin):
-    """(records, node counts, state_begin int64 [M]) of a fusion launch; volumes: what surface_records takes (the prefix table is
-    the same: 256 nodes per workgroup), or [] for an empty launch; a layout without its fifth field, the element offset in the
-    pool, lies behind the layout before it (the first at 0)."""
-    assert _lib.FUSION_NODES_PER_WORKGROUP == _lib.SURFACE_NODES_PER_WORKGROUP
-    rec = volumes if isinstance(volumes, C.Array) else [tuple(v) for v in volumes]
-    if not isinstance(rec, C.Array):
-        at = 0
-        for m, v in enumerate(rec):
-            if len(v) == 4:
-                rec[m] = v + (at,)
-            if len(rec[m]) != 5:
-                raise _lib.OmgHipError(f"volume {m}: (origin, delta, sample, dims[, offset]), got {len(v)} fields")
-            at = int(rec[m][4]) + int(np.prod([int(d) for d in np.asarray(v[3]).reshape(-1)]))
-    rec = surface_records(rec) if len(rec) else (_lib.Mesh * 0)()
-    nodes = np.array([int(r.dims[0]) * int(r.dims[1]) * int(r.dims[2]) for r in rec], np.int64)
-    begin = np.cumsum(nodes) - nodes if state_begin is None else np.ascontiguousarray(state_begin, np.int64).reshape(-1)
-    if len(begin) != len(rec):
-        raise _lib.OmgHipError(f"state_begin must have one offset per volume ({len(rec)}), got {len(begin)}")
-    return rec, nodes, begin
+    """(records, node counts, state_begin int64 [M]) of a fusion launch: the host half of a _VolumeBatch."""
+    batch = _VolumeBatch(volumes, state_begin)
+    return batch.rec, batch.nodes, batch.begin
 
 
 def _upload(a: np.ndarray, dev) -> torch.Tensor:
@@ -1462,8 +1516,8 @@ def _fusion_radius(radius) -> int:
 
 
 def _carve_arguments(volumes, views, view_range, depth, band, near, state_begin):
-    """The host side of a carve launch, checked before anything touches the device -> (records, node counts, state_begin
-    int64 [M], views float64 [V,16], view_range int32 [M,2]).  depth is only asked for its shape."""
+    """The host side of a carve launch, checked before anything touches the device -> (the _VolumeBatch, views
+    float64 [V,16], view_range int32 [M,2]).  depth is only asked for its shape."""
     if not isinstance(depth, torch.Tensor) or depth.dim() != 3:
         raise _lib.OmgHipError("depth must be a tensor [V,H,W]")
     V = int(depth.shape[0])
@@ -1474,12 +1528,11 @@ def _carve_arguments(volumes, views, view_range, depth, band, near, state_begin)
         raise _lib.OmgHipError("a view is not finite or has a focal length of zero")
     if not (np.isfinite(float(band)) and np.isfinite(float(near))):
         raise _lib.OmgHipError("band and near must be finite")
-    rec, nodes, begin = _fusion_volumes(volumes, state_begin)
-    M = len(rec)
+    batch = _VolumeBatch.of(volumes, state_begin)
     h_range = np.asarray(view_range, np.int64).reshape(-1, 2)
-    if len(h_range) != M or (h_range < 0).any() or (h_range.sum(1) > V).any():
-        raise _lib.OmgHipError(f"view_range must be [{M},2] inside [0, {V}]")
-    return rec, nodes, begin, h_views, np.ascontiguousarray(h_range, np.int32)
+    if len(h_range) != batch.M or (h_range < 0).any() or (h_range.sum(1) > V).any():
+        raise _lib.OmgHipError(f"view_range must be [{batch.M},2] inside [0, {V}]")
+    return batch, h_views, np.ascontiguousarray(h_range, np.int32)
 
 
 def carve_views(volumes, views, view_range, depth: torch.Tensor, band: float, near: float, state: "torch.Tensor | None" = None,
@@ -1494,26 +1547,25 @@ def carve_views(volumes, views, view_range, depth: torch.Tensor, band: float, ne
     merge: the flags start from what `state` holds, so that carving the views A and merging the views B equals carving both.
     The host arguments are checked first, then the tensors: a refused call has touched nothing."""
     from . import fusion as _fu
-    rec, nodes, begin, h_views, h_range = _carve_arguments(volumes, views, view_range, depth, band, near, state_begin)
+    batch, h_views, h_range = _carve_arguments(volumes, views, view_range, depth, band, near, state_begin)
     if state is None and merge:
         raise _lib.OmgHipError("merge needs the state of an earlier call")
     _need(depth, torch.float64, "depth")
     dev, vp = depth.device, C.c_void_p
-    (V, H, W), M = (int(d) for d in depth.shape), len(rec)
+    (V, H, W), M = (int(d) for d in depth.shape), batch.M
     if state is None:
-        state = torch.full((max(int((begin + nodes).max()) if M else 0, 1),), _fu.UNKNOWN, dtype=torch.uint8, device=dev)
+        state = torch.full((max(batch.end(), 1),), _fu.UNKNOWN, dtype=torch.uint8, device=dev)
     _need(state, torch.uint8, "state")
     if state.device != dev:
         raise _lib.OmgHipError(f"state must be on {dev}, got {state.device}")
     with torch.cuda.device(dev):
-        d_rec, d_views, d_range, d_begin = _upload(rec, dev), _upload(h_views, dev), _upload(h_range, dev), _upload(begin, dev)
-        check(_lib.lib().omgx_carve_views(_ptr(d_rec) if M else None, C.cast(rec, vp) if M else None, M, _ptr(d_views) if V else None,
-                                          vp(h_views.ctypes.data) if V else None, V, _ptr(d_range) if M else None, vp(h_range.ctypes.data) if M else None,
-                                          _ptr(d_begin) if M else None, vp(begin.ctypes.data) if M else None, _ptr(depth) if V else None, H, W,
-                                          float(band), float(near), int(bool(merge)), _ptr(state), int(state.numel()), _stream()), "omgx_carve_views")
-        for t in (d_rec, d_views, d_range, d_begin):
-            t.record_stream(torch.cuda.current_stream(dev))
-    return state, begin
+        d_views, d_range = _upload(h_views, dev), _upload(h_range, dev)
+        check(_lib.lib().omgx_carve_views(*batch.on(dev).volume_args(), _ptr(d_views) if V else None, vp(h_views.ctypes.data) if V else None, V,
+                                          _ptr(d_range) if M else None, vp(h_range.ctypes.data) if M else None, *batch.begin_args(),
+                                          _ptr(depth) if V else None, H, W, float(band), float(near), int(bool(merge)), _ptr(state),
+                                          int(state.numel()), _stream()), "omgx_carve_views")
+        batch.release(d_views, d_range)
+    return state, batch.begin
 
 
 def distance_transform(state: torch.Tensor, state_begin, volumes, radius: int, unknown_occupied: bool = True, out: "torch.Tensor | None" = None):
@@ -1523,24 +1575,21 @@ def distance_transform(state: torch.Tensor, state_begin, volumes, radius: int, u
     that reaches to the end of the last volume, zero where no volume lies.  Volume m lies at out[offset : offset + X*Y*Z] as
     [X,Y,Z].  The host arguments are checked first, then the tensors."""
     radius = _fusion_radius(radius)
-    rec, nodes, begin = _fusion_volumes(volumes, state_begin)
+    batch = _VolumeBatch.of(volumes, state_begin)
     _need(state, torch.uint8, "state")
-    dev, vp, l, M = state.device, C.c_void_p, _lib.lib(), len(rec)
+    dev, l = state.device, _lib.lib()
     if out is None:
-        out = torch.zeros(max([int(r.out_offset) + int(n) for r, n in zip(rec, nodes)], default=1), dtype=torch.float32, device=dev)
+        out = torch.zeros(batch.pool_end(), dtype=torch.float32, device=dev)
     _need(out, torch.float32, "out")
     if out.device != dev:
         raise _lib.OmgHipError(f"out must be on {dev}, got {out.device}")
-    nbytes = int(l.omgx_distance_transform_workspace_bytes(C.cast(rec, vp) if M else None, M, radius))
+    nbytes = int(l.omgx_distance_transform_workspace_bytes(*batch.host_args(), radius))
     check(min(nbytes, 0), "omgx_distance_transform_workspace_bytes")
     with torch.cuda.device(dev):
         ws = torch.empty(max(nbytes // 4, 1), dtype=torch.int32, device=dev)
-        d_rec, d_begin = _upload(rec, dev), _upload(begin, dev)
-        check(l.omgx_distance_transform(_ptr(state), int(state.numel()), _ptr(d_begin) if M else None, vp(begin.ctypes.data) if M else None,
-                                        _ptr(d_rec) if M else None, C.cast(rec, vp) if M else None, M, radius, int(bool(unknown_occupied)), _ptr(ws),
-                                        _ptr(out), int(out.numel()), _stream()), "omgx_distance_transform")
-        for t in (ws, d_rec, d_begin):
-            t.record_stream(torch.cuda.current_stream(dev))
+        check(l.omgx_distance_transform(_ptr(state), int(state.numel()), *batch.on(dev).begin_args(), *batch.volume_args(), radius,
+                                        int(bool(unknown_occupied)), _ptr(ws), _ptr(out), int(out.numel()), _stream()), "omgx_distance_transform")
+        batch.release(ws)
     return out
 
 
@@ -1565,13 +1614,13 @@ def _tsdf_arguments(volumes, views, view_range, depth, trunc, near, weights, wma
     """The host side of an integrate launch, checked before anything touches the device: _carve_arguments' result and
     (weights float64 [V] or None, trunc, wmax)."""
     trunc, wmax = _tsdf_positive("trunc", trunc), _tsdf_positive("wmax", wmax, True)
-    rec, nodes, begin, h_views, h_range = _carve_arguments(volumes, views, view_range, depth, 0.0, near, state_begin)
+    batch, h_views, h_range = _carve_arguments(volumes, views, view_range, depth, 0.0, near, state_begin)
     h_w = None
     if weights is not None:
         h_w = np.ascontiguousarray(weights, np.float64).reshape(-1)
         if len(h_w) != len(h_views) or not np.isfinite(h_w).all() or (h_w < 0).any():
             raise _lib.OmgHipError(f"weights must be {len(h_views)} finite numbers >= 0")
-    return rec, nodes, begin, h_views, h_range, h_w, trunc, wmax
+    return batch, h_views, h_range, h_w, trunc, wmax
 
 
 def _tsdf_pair(tsdf, weight, dev=None):
@@ -1583,8 +1632,7 @@ def _tsdf_pair(tsdf, weight, dev=None):
 
 
 def tsdf_integrate(volumes, views, view_range, depth: torch.Tensor, trunc: float, near: float, weights=None, wmax: float = float("inf"),
-                   tsdf: "torch.Tensor | None" = None, weight: "torch.Tensor | None" = None, state_begin=None, merge: bool = False,
-                   _device_records=None):
+                   tsdf: "torch.Tensor | None" = None, weight: "torch.Tensor | None" = None, state_begin=None, merge: bool = False):
     """The pairs (D: the averaged truncated distance, W: the accumulated weight) of the nodes of M volumes from V depth views in
     ONE launch (omgx_tsdf_integrate; tsdf.integrate is the specification: the same bits) -> (tsdf, weight: float32 on the
     device, state_begin [M] int64 numpy): volume m's node L at state_begin[m] + L of both.  volumes, views, view_range, depth and
@@ -1592,57 +1640,50 @@ def tsdf_integrate(volumes, views, view_range, depth: torch.Tensor, trunc: float
     tsdf / weight: None -> new buffers that reach to the end of the last volume, zero where no volume lies; or the caller's,
     written IN PLACE.  merge: the pairs start from what the buffers hold (a further frame), otherwise from (0, 0).
     The host arguments are checked first, then the tensors: a refused call has touched nothing."""
-    rec, nodes, begin, h_views, h_range, h_w, trunc, wmax = _tsdf_arguments(volumes, views, view_range, depth, trunc, near, weights, wmax, state_begin)
+    batch, h_views, h_range, h_w, trunc, wmax = _tsdf_arguments(volumes, views, view_range, depth, trunc, near, weights, wmax, state_begin)
     if (tsdf is None) != (weight is None):
         raise _lib.OmgHipError("tsdf and weight come together")
     if tsdf is None and merge:
         raise _lib.OmgHipError("merge needs the pairs of an earlier call")
     _need(depth, torch.float64, "depth")
     dev, vp = depth.device, C.c_void_p
-    (V, H, W), M = (int(d) for d in depth.shape), len(rec)
+    (V, H, W), M = (int(d) for d in depth.shape), batch.M
     if tsdf is None:
-        n = max(int((begin + nodes).max()) if M else 0, 1)
+        n = max(batch.end(), 1)
         tsdf, weight = torch.zeros(n, dtype=torch.float32, device=dev), torch.zeros(n, dtype=torch.float32, device=dev)
     _tsdf_pair(tsdf, weight, dev)
     with torch.cuda.device(dev):
-        d_rec, d_begin = _device_records if _device_records is not None else (_upload(rec, dev), _upload(begin, dev))
         d_views, d_range = _upload(h_views, dev), _upload(h_range, dev)
         d_w = _upload(h_w, dev) if h_w is not None and V else None
-        check(_lib.lib().omgx_tsdf_integrate(_ptr(d_rec) if M else None, C.cast(rec, vp) if M else None, M, _ptr(d_views) if V else None,
-                                             vp(h_views.ctypes.data) if V else None, V, _ptr(d_range) if M else None,
-                                             vp(h_range.ctypes.data) if M else None, _ptr(d_begin) if M else None, vp(begin.ctypes.data) if M else None,
+        check(_lib.lib().omgx_tsdf_integrate(*batch.on(dev).volume_args(), _ptr(d_views) if V else None, vp(h_views.ctypes.data) if V else None, V,
+                                             _ptr(d_range) if M else None, vp(h_range.ctypes.data) if M else None, *batch.begin_args(),
                                              _ptr(depth) if V else None, H, W, _ptr(d_w), vp(h_w.ctypes.data) if d_w is not None else None, trunc,
                                              float(near), wmax, int(bool(merge)), _ptr(tsdf), _ptr(weight), int(tsdf.numel()), _stream()),
               "omgx_tsdf_integrate")
-        for t in (d_rec, d_views, d_range, d_begin, d_w):
-            if t is not None:
-                t.record_stream(torch.cuda.current_stream(dev))
-    return tsdf, weight, begin
+        batch.release(d_views, d_range, d_w)
+    return tsdf, weight, batch.begin
 
 
-def tsdf_states(tsdf: torch.Tensor, weight: torch.Tensor, state_begin, volumes, min_weight: float = 1.0, state: "torch.Tensor | None" = None,
-                _device_records=None) -> torch.Tensor:
+def tsdf_states(tsdf: torch.Tensor, weight: torch.Tensor, state_begin, volumes, min_weight: float = 1.0,
+                state: "torch.Tensor | None" = None) -> torch.Tensor:
     """The state bytes of the pairs in one launch (omgx_tsdf_states; tsdf.states is the specification): 2 (unknown) if
     !(W >= min_weight), else 1 (surface) if D < 0, else 0 (free), at the pairs' own offsets: carve_views' layout, so
     distance_transform, label_components and component_states take them as they are.  state: None -> a new buffer of the pairs'
     length, 2 where no volume lies; or the caller's uint8 tensor of that length, written IN PLACE inside the volumes' ranges."""
     from . import fusion as _fu
     min_weight = _tsdf_positive("min_weight", min_weight)
-    rec, nodes, begin = _fusion_volumes(volumes, state_begin)
+    batch = _VolumeBatch.of(volumes, state_begin)
     _tsdf_pair(tsdf, weight)
-    dev, vp, M = tsdf.device, C.c_void_p, len(rec)
+    dev = tsdf.device
     if state is None:
         state = torch.full((tsdf.numel(),), _fu.UNKNOWN, dtype=torch.uint8, device=dev)
     _need(state, torch.uint8, "state")
     if state.device != dev or state.numel() != tsdf.numel():
         raise _lib.OmgHipError(f"state must have the pairs' {tsdf.numel()} elements on {dev}")
     with torch.cuda.device(dev):
-        d_rec, d_begin = _device_records if _device_records is not None else (_upload(rec, dev), _upload(begin, dev))
-        check(_lib.lib().omgx_tsdf_states(_ptr(tsdf), _ptr(weight), int(tsdf.numel()), _ptr(d_begin) if M else None, vp(begin.ctypes.data) if M else None,
-                                          _ptr(d_rec) if M else None, C.cast(rec, vp) if M else None, M, min_weight, _ptr(state), _stream()),
-              "omgx_tsdf_states")
-        for t in (d_rec, d_begin):
-            t.record_stream(torch.cuda.current_stream(dev))
+        check(_lib.lib().omgx_tsdf_states(_ptr(tsdf), _ptr(weight), int(tsdf.numel()), *batch.on(dev).begin_args(), *batch.volume_args(), min_weight,
+                                          _ptr(state), _stream()), "omgx_tsdf_states")
+        batch.release()
     return state
 
 
@@ -1651,26 +1692,24 @@ def tsdf_blend(tsdf: torch.Tensor, weight: torch.Tensor, state_begin, volumes, t
     volume's element offset, in one launch (omgx_tsdf_blend; tsdf.blend is the specification: the same bits): where
     W >= min_weight, out = D + (|D| / trunc) * (out - D) unless |D| >= trunc.  The zero level of the result is the TSDF's."""
     trunc, min_weight = _tsdf_positive("trunc", trunc), _tsdf_positive("min_weight", min_weight)
-    rec, nodes, begin = _fusion_volumes(volumes, state_begin)
+    batch = _VolumeBatch.of(volumes, state_begin)
     _tsdf_pair(tsdf, weight)
-    dev, vp, M = tsdf.device, C.c_void_p, len(rec)
+    dev = tsdf.device
     _need(out, torch.float32, "out")
     if out.device != dev:
         raise _lib.OmgHipError(f"out must be on {dev}, got {out.device}")
     with torch.cuda.device(dev):
-        d_rec, d_begin = _upload(rec, dev), _upload(begin, dev)
-        check(_lib.lib().omgx_tsdf_blend(_ptr(tsdf), _ptr(weight), int(tsdf.numel()), _ptr(d_begin) if M else None, vp(begin.ctypes.data) if M else None,
-                                         _ptr(d_rec) if M else None, C.cast(rec, vp) if M else None, M, trunc, min_weight, _ptr(out), int(out.numel()),
-                                         _stream()), "omgx_tsdf_blend")
-        for t in (d_rec, d_begin):
-            t.record_stream(torch.cuda.current_stream(dev))
+        check(_lib.lib().omgx_tsdf_blend(_ptr(tsdf), _ptr(weight), int(tsdf.numel()), *batch.on(dev).begin_args(), *batch.volume_args(), trunc,
+                                         min_weight, _ptr(out), int(out.numel()), _stream()), "omgx_tsdf_blend")
+        batch.release()
     return out
 
 
-def _tsdf_signed(tsdf, weight, begin, volumes, trunc, radius, unknown_occupied, min_weight, out, device_records=None):
-    state = tsdf_states(tsdf, weight, begin, volumes, min_weight, _device_records=device_records)
-    out = distance_transform(state, begin, volumes, radius, unknown_occupied, out)
-    return tsdf_blend(tsdf, weight, begin, volumes, trunc, min_weight, out)
+def _tsdf_signed(tsdf, weight, begin, volumes, trunc, radius, unknown_occupied, min_weight, out):
+    batch = _VolumeBatch.of(volumes, begin)  # (one batch: the records and state_begin go to the device once for the three)
+    state = tsdf_states(tsdf, weight, None, batch, min_weight)
+    out = distance_transform(state, None, batch, radius, unknown_occupied, out)
+    return tsdf_blend(tsdf, weight, None, batch, trunc, min_weight, out)
 
 
 def fuse_tsdf(volumes, views, view_range, depth: torch.Tensor, trunc: float, near: float, radius: int, unknown_occupied: bool = True,
@@ -1692,13 +1731,13 @@ class TsdfVolumes:
         if not np.isfinite(self.near):
             raise _lib.OmgHipError("band and near must be finite")
         self.volumes = [tuple(v) for v in volumes]
-        self.rec, self.nodes, self.state_begin = _fusion_volumes(self.volumes, state_begin)
+        self._batch = _VolumeBatch(self.volumes, state_begin)
+        self.rec, self.nodes, self.state_begin = self._batch.rec, self._batch.nodes, self._batch.begin
         if not len(self.rec):
             raise _lib.OmgHipError("TsdfVolumes needs at least one volume")
         self.device = torch.device(device)
-        n = int((self.state_begin + self.nodes).max())
-        self.tsdf, self.weight = (torch.zeros(n, dtype=torch.float32, device=self.device) for _ in range(2))
-        self._records = (_upload(self.rec, self.device), _upload(self.state_begin, self.device))
+        self.tsdf, self.weight = (torch.zeros(self._batch.end(), dtype=torch.float32, device=self.device) for _ in range(2))
+        self._batch.on(self.device)
         self.frames = 0
 
     def layouts(self):
@@ -1708,27 +1747,25 @@ class TsdfVolumes:
     def integrate(self, depth: torch.Tensor, views, view_range, weights=None) -> "TsdfVolumes":
         """One more frame: depth [V,H,W], views [V,16] and view_range [M,2] as tsdf_integrate takes them.  The first call starts
         from (0, 0), every later one merges."""
-        tsdf_integrate(self.volumes, views, view_range, depth, self.trunc, self.near, weights, self.wmax, self.tsdf, self.weight, self.state_begin,
-                       merge=self.frames > 0, _device_records=self._records)
+        tsdf_integrate(self._batch, views, view_range, depth, self.trunc, self.near, weights, self.wmax, self.tsdf, self.weight, merge=self.frames > 0)
         self.frames += 1
         return self
 
     def states(self, min_weight: float = 1.0) -> torch.Tensor:
         """A new uint8 tensor of state bytes at state_begin (tsdf_states)."""
-        return tsdf_states(self.tsdf, self.weight, self.state_begin, self.volumes, min_weight, _device_records=self._records)
+        return tsdf_states(self.tsdf, self.weight, None, self._batch, min_weight)
 
     def signed(self, radius: int, unknown_occupied: bool = True, min_weight: float = 1.0, out: "torch.Tensor | None" = None, offsets=None):
         """The signed float32 volumes: states, distance_transform and tsdf_blend -> out, as distance_transform returns it.
         offsets: the volumes' element offsets in `out` for this call (a pool's slots change from frame to frame); default: the
         layouts' own."""
         radius, min_weight = _fusion_radius(radius), _tsdf_positive("min_weight", min_weight)
-        volumes = self.volumes
+        batch = self._batch
         if offsets is not None:
-            if len(offsets) != len(volumes):
-                raise _lib.OmgHipError(f"{len(volumes)} volumes need as many offsets")
-            volumes = [v[:4] + (int(o),) for v, o in zip(volumes, offsets)]
-        return _tsdf_signed(self.tsdf, self.weight, self.state_begin, volumes, self.trunc, radius, unknown_occupied, min_weight, out,
-                            self._records)
+            if len(offsets) != batch.M:
+                raise _lib.OmgHipError(f"{batch.M} volumes need as many offsets")
+            batch = _VolumeBatch([v[:4] + (int(o),) for v, o in zip(self.volumes, offsets)], like=batch)  # (new records, the same state_begin)
+        return _tsdf_signed(self.tsdf, self.weight, None, batch, self.trunc, radius, unknown_occupied, min_weight, out)
 
 
 class Components:
@@ -1739,6 +1776,7 @@ class Components:
     def __init__(self, labels, counts, comp_begin, records, d_records, rec, begin, select, connectivity):
         self.labels, self.counts, self.comp_begin, self.records, self.d_records = labels, counts, comp_begin, records, d_records
         self.rec, self.begin, self.select, self.connectivity = rec, begin, select, connectivity
+        self._batch = None  # label_components': its uploads serve component_states too
 
     def of(self, m: int) -> np.ndarray:
         """The records of volume m, in rank order."""
@@ -1761,11 +1799,11 @@ def label_components(state: torch.Tensor, state_begin, volumes, select: int = 1,
     18 or 26.  The same launches whatever the states hold; ONE download of the counts and one of the records.  The host
     arguments are checked first, then the tensor."""
     select, connectivity = _segment_arguments(select, connectivity)
-    rec, nodes, begin = _fusion_volumes(volumes, state_begin)
+    batch = _VolumeBatch.of(volumes, state_begin)
     _need(state, torch.uint8, "state")
-    dev, vp, l, M = state.device, C.c_void_p, _lib.lib(), len(rec)
+    dev, vp, l, M, rec, begin = state.device, C.c_void_p, _lib.lib(), batch.M, batch.rec, batch.begin
     elems = int(state.numel())
-    nbytes = int(l.omgx_label_workspace_bytes(C.cast(rec, vp) if M else None, M))
+    nbytes = int(l.omgx_label_workspace_bytes(*batch.host_args()))
     check(min(nbytes, 0), "omgx_label_workspace_bytes")
     with torch.cuda.device(dev):
         labels = torch.full((elems,), -1, dtype=torch.int32, device=dev) if M == 0 else torch.empty(elems, dtype=torch.int32, device=dev)
@@ -1774,25 +1812,25 @@ def label_components(state: torch.Tensor, state_begin, volumes, select: int = 1,
                               torch.empty((0, 8), dtype=torch.int32, device=dev), rec, begin, select, connectivity)
         ws = torch.empty(max(nbytes // 4, 1), dtype=torch.int32, device=dev)
         counts = torch.empty(M, dtype=torch.int32, device=dev)
-        d_rec, d_begin = _upload(rec, dev), _upload(begin, dev)
-        check(l.omgx_label_components(_ptr(state), elems, _ptr(d_begin), vp(begin.ctypes.data), _ptr(d_rec), C.cast(rec, vp), M, select, connectivity,
-                                      _ptr(ws), _ptr(labels), _ptr(counts), _stream()), "omgx_label_components")
+        check(l.omgx_label_components(_ptr(state), elems, *batch.on(dev).begin_args(), *batch.volume_args(), select, connectivity, _ptr(ws), _ptr(labels),
+                                      _ptr(counts), _stream()), "omgx_label_components")
         h_counts = counts.cpu().numpy().astype(np.int64)
         comp_begin = np.concatenate([[0], np.cumsum(h_counts)]).astype(np.int64)
         total = int(comp_begin[-1])
         d_records = torch.empty((total, 8), dtype=torch.int32, device=dev)
         d_comp = _upload(comp_begin, dev)
-        check(l.omgx_component_records(_ptr(labels), elems, _ptr(d_begin), vp(begin.ctypes.data), _ptr(d_rec), C.cast(rec, vp), M, _ptr(d_comp),
-                                       vp(comp_begin.ctypes.data), _ptr(d_records) if total else None, total, _stream()), "omgx_component_records")
+        check(l.omgx_component_records(_ptr(labels), elems, *batch.begin_args(), *batch.volume_args(), _ptr(d_comp), vp(comp_begin.ctypes.data),
+                                       _ptr(d_records) if total else None, total, _stream()), "omgx_component_records")
         records = d_records.cpu().numpy()
-        for t in (ws, d_rec, d_begin, d_comp):
-            t.record_stream(torch.cuda.current_stream(dev))
-    return Components(labels, h_counts, comp_begin, records, d_records, rec, begin, select, connectivity)
+        batch.release(ws, d_comp)
+    comps = Components(labels, h_counts, comp_begin, records, d_records, rec, begin, select, connectivity)
+    comps._batch = batch
+    return comps
 
 
 def _component_arguments(components, picks, out_volumes, out_begin):
     """The host side of a component_states launch, checked before anything touches the device -> (picks int32 [K,8], the
-    output records, their node counts, out_begin int64 [K])."""
+    _VolumeBatch of the outputs)."""
     from . import segmentation as _sg
     if not isinstance(components, Components):
         raise _lib.OmgHipError("components must be what label_components returned")
@@ -1800,10 +1838,10 @@ def _component_arguments(components, picks, out_volumes, out_begin):
         h_picks = np.ascontiguousarray(_sg.check_picks(picks, len(components.rec), components.comp_begin))
     except ValueError as e:
         raise _lib.OmgHipError(str(e)) from None
-    out_rec, out_nodes, ob = _fusion_volumes(out_volumes, out_begin)
-    if len(out_rec) != len(h_picks):
-        raise _lib.OmgHipError(f"{len(h_picks)} picks need as many output volumes, got {len(out_rec)}")
-    return h_picks, out_rec, out_nodes, ob
+    outs = _VolumeBatch.of(out_volumes, out_begin)
+    if outs.M != len(h_picks):
+        raise _lib.OmgHipError(f"{len(h_picks)} picks need as many output volumes, got {outs.M}")
+    return h_picks, outs
 
 
 def component_states(state: torch.Tensor, components: Components, picks, out_volumes, out_begin=None, out: "torch.Tensor | None" = None):
@@ -1813,28 +1851,26 @@ def component_states(state: torch.Tensor, components: Components, picks, out_vol
     mode 0 the target alone / 1 everything but the target, 0, 0); out_volumes: what surface_records takes, one per pick.
     out / out_begin: None -> a new buffer, the outputs back to back, UNKNOWN where none lies; or the caller's, written IN PLACE."""
     from . import fusion as _fu
-    h_picks, out_rec, out_nodes, ob = _component_arguments(components, picks, out_volumes, out_begin)
+    h_picks, outs = _component_arguments(components, picks, out_volumes, out_begin)
     _need(state, torch.uint8, "state")
-    dev, vp, K, M = state.device, C.c_void_p, len(h_picks), len(components.rec)
+    dev, vp, K, ob = state.device, C.c_void_p, len(h_picks), outs.begin
     if int(state.numel()) != int(components.labels.numel()) or components.labels.device != dev:
         raise _lib.OmgHipError("state must be the array that label_components labelled")
     with torch.cuda.device(dev):
         if out is None:
-            out = torch.full((max(int((ob + out_nodes).max()) if K else 0, 1),), _fu.UNKNOWN, dtype=torch.uint8, device=dev)
+            out = torch.full((max(outs.end(), 1),), _fu.UNKNOWN, dtype=torch.uint8, device=dev)
         _need(out, torch.uint8, "out")
         if out.device != dev:
             raise _lib.OmgHipError(f"out must be on {dev}, got {out.device}")
         if K == 0:
             return out, ob
-        rec, begin, comp_begin = components.rec, components.begin, components.comp_begin
-        d_rec, d_begin, d_comp, d_picks, d_out, d_ob = (_upload(a, dev) for a in (rec, begin, comp_begin, h_picks, out_rec, ob))
-        check(_lib.lib().omgx_component_states(_ptr(state), int(state.numel()), _ptr(d_begin), vp(begin.ctypes.data), _ptr(d_rec), C.cast(rec, vp), M,
-                                               _ptr(components.labels), _ptr(d_comp), vp(comp_begin.ctypes.data), _ptr(components.d_records),
-                                               int(components.d_records.shape[0]), _ptr(d_picks), vp(h_picks.ctypes.data), _ptr(d_out),
-                                               C.cast(out_rec, vp), K, _ptr(d_ob), vp(ob.ctypes.data), _ptr(out), int(out.numel()), _stream()),
-              "omgx_component_states")
-        for t in (d_rec, d_begin, d_comp, d_picks, d_out, d_ob):
-            t.record_stream(torch.cuda.current_stream(dev))
+        src, comp_begin = (components._batch or _VolumeBatch(components.rec, components.begin)).on(dev), components.comp_begin
+        d_comp, d_picks = _upload(comp_begin, dev), _upload(h_picks, dev)
+        check(_lib.lib().omgx_component_states(_ptr(state), int(state.numel()), *src.begin_args(), *src.volume_args(), _ptr(components.labels),
+                                               _ptr(d_comp), vp(comp_begin.ctypes.data), _ptr(components.d_records), int(components.d_records.shape[0]),
+                                               _ptr(d_picks), vp(h_picks.ctypes.data), *outs.on(dev).volume_args(), *outs.begin_args(), _ptr(out),
+                                               int(out.numel()), _stream()), "omgx_component_states")
+        src.release(d_comp, d_picks), outs.release()
     return out, ob
 
 
@@ -2009,13 +2045,12 @@ def plane_mask(intrinsics, depth: torch.Tensor, planes, tol: float, skip: "torch
 
 
 def _plane_volume_arguments(volumes, planes):
-    """The host side of plane_volumes, checked before anything touches the device -> (records, node counts, planes [M,4])."""
-    assert _lib.PLANE_NODES_PER_WORKGROUP == _lib.SURFACE_NODES_PER_WORKGROUP
-    rec, nodes, _ = _fusion_volumes(volumes, None)
+    """The host side of plane_volumes, checked before anything touches the device -> (the _VolumeBatch, planes [M,4])."""
+    batch = _VolumeBatch.of(volumes)
     h_planes = np.ascontiguousarray(planes, np.float64).reshape(-1, 4)
-    if len(h_planes) != len(rec) or not np.isfinite(h_planes).all():
-        raise _lib.OmgHipError(f"{len(rec)} volumes need as many planes [4], all finite")
-    return rec, nodes, h_planes
+    if len(h_planes) != batch.M or not np.isfinite(h_planes).all():
+        raise _lib.OmgHipError(f"{batch.M} volumes need as many planes [4], all finite")
+    return batch, h_planes
 
 
 def plane_volumes(volumes, planes, out: "torch.Tensor | None" = None, device="cuda:0") -> torch.Tensor:
@@ -2023,20 +2058,18 @@ def plane_volumes(volumes, planes, out: "torch.Tensor | None" = None, device="cu
     same bits): float32(n.p + off) at every node, positive on the camera's side of the plane.  volumes: what surface_records
     takes, the fifth field the element offset in `out` (without it: back to back); planes [M,4] on the host, in the grids'
     frames.  out: a contiguous float32 device tensor (the SDF pool) written IN PLACE, or None -> a new buffer on `device`."""
-    rec, nodes, h_planes = _plane_volume_arguments(volumes, planes)
-    M, vp = len(rec), C.c_void_p
+    batch, h_planes = _plane_volume_arguments(volumes, planes)
     if out is None:
-        out = torch.zeros(max([int(r.out_offset) + int(n) for r, n in zip(rec, nodes)], default=1), dtype=torch.float32, device=device)
+        out = torch.zeros(batch.pool_end(), dtype=torch.float32, device=device)
     _need(out, torch.float32, "out")
     dev = out.device
-    if M == 0:
+    if batch.M == 0:
         return out
     with torch.cuda.device(dev):
-        d_rec, d_planes = _upload(rec, dev), _upload(h_planes, dev)
-        check(_lib.lib().omgx_plane_volumes(_ptr(d_rec), C.cast(rec, vp), M, _ptr(d_planes), vp(h_planes.ctypes.data), _ptr(out), int(out.numel()),
+        d_planes = _upload(h_planes, dev)
+        check(_lib.lib().omgx_plane_volumes(*batch.on(dev).volume_args(), _ptr(d_planes), C.c_void_p(h_planes.ctypes.data), _ptr(out), int(out.numel()),
                                             _stream()), "omgx_plane_volumes")
-        for t in (d_rec, d_planes):
-            t.record_stream(torch.cuda.current_stream(dev))
+        batch.release(d_planes)
     return out
 
 

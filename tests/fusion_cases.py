@@ -221,3 +221,25 @@ RAGGED = [((-0.16, -0.16, -0.04), 0.02, "centre", (16, 16, 12)), ((-0.1, -0.12, 
           ((-0.05, -0.05, 0.01), 0.01, "centre", (7, 10, 13))]
 RAGGED_RANGES = [(0, 3), (1, 2), (2, 1)]
 RAGGED_RADIUS = 6
+
+# ---------------------------------------------------------------------------------------------------------------------
+# six volumes for the workgroup-to-volume search: at 256 nodes per workgroup they take 1, 1, 1, 2, 3 and 2 workgroups (the
+# prefix table 0, 1, 2, 3, 5, 8): a single node, a partly and an exactly full workgroup, one node past a full one, a long thin
+# row, and no power of two of them; both sample offsets; two views of 8 x 8 pixels
+# ---------------------------------------------------------------------------------------------------------------------
+LOCATE_DIMS = ((1, 1, 1), (5, 7, 3), (4, 8, 8), (257, 1, 1), (1, 1, 513), (3, 3, 29))
+LOCATE_FIRST_WORKGROUP = (0, 1, 2, 3, 5, 8, 10)
+LOCATE = [((-0.03 + 0.004 * m, -0.02, 0.01 * m), 0.004 + 0.0005 * m, ("centre", "node")[m % 2], d) for m, d in enumerate(LOCATE_DIMS)]
+LOCATE_RANGES = [(0, 2), (1, 1), (0, 1), (0, 2), (0, 2), (1, 1)]
+LOCATE_BAND, LOCATE_NEAR, LOCATE_RADIUS = 0.02, 0.05, 5
+
+
+def locate_views():
+    """(depth [2,8,8] float64 with background and void pixels, view rows [2,16]): a camera 0.3 below the origin that looks along
+    +z and one 0.3 behind it that looks along +x."""
+    r, c = np.meshgrid(np.arange(8), np.arange(8), indexing="ij")
+    depth = np.stack([0.3 + 0.02 * ((3 * r + c) % 7), 0.28 + 0.03 * ((r + 2 * c) % 9)]).astype(np.float64)
+    depth[0, 0, 0], depth[1, 7, 7], depth[1, 2, 3] = np.inf, np.inf, 0.0
+    along_z = np.array([[1.0, 0, 0, 0], [0, 1.0, 0, 0], [0, 0, 1.0, 0.3]])
+    along_x = np.array([[0, 1.0, 0, 0], [0, 0, 1.0, 0], [1.0, 0, 0, 0.3]])
+    return depth, np.stack([view(12.0, 12.0, 3.5, 3.5, along_z), view(10.0, 10.0, 3.5, 3.5, along_x)])

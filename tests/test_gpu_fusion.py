@@ -364,3 +364,73 @@ def test_a_short_seeded_fuzz_run(dev):
     fuzz = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(fuzz)
     assert fuzz.main(trials=fuzz.SMOKE_TRIALS, seed=fuzz.SMOKE_SEED) == 0
+
+
+def test_every_volume_op_finds_the_volumes_of_one_ragged_batch(dev):
+    """The six volumes of fusion_cases.LOCATE (1, 1, 1, 2, 3 and 2 workgroups: a single node, a full workgroup, one node past a
+    full one, a long thin row; both sample offsets) as ONE batch through every op that maps workgroups to volumes by the
+    first_workgroup prefix table: mesh SDF, carve and transform, the three TSDF steps, labelling, half-space volumes and surface
+    extraction, each bit for bit what its specification gives."""
+    from omg_planner_amd import fusion, ops, planes, scenes as sc, segmentation as sg, tsdf
+    from tests import mesh_cases as MC
+    vols, M = FC.LOCATE, len(FC.LOCATE)
+    nodes = [int(np.prod(v[3])) for v in vols]
+    at = fusion.state_offsets(vols)
+    assert [-(-n // 256) for n in nodes] == list(np.diff(FC.LOCATE_FIRST_WORKGROUP)) and {v[2] for v in vols} == {"centre", "node"}
+    t, views = FC.locate_views()
+    depth = torch.from_numpy(t).to(dev)
+    # carve and transform
+    want_state = fusion.carve_views(vols, views, FC.LOCATE_RANGES, t, FC.LOCATE_BAND, FC.LOCATE_NEAR)
+    want_vol = fusion.distance_transform(want_state, vols, FC.LOCATE_RADIUS, True)
+    assert {0, 1, 2} <= set(want_state.tolist())
+    state, begin = ops.carve_views(vols, views, FC.LOCATE_RANGES, depth, FC.LOCATE_BAND, FC.LOCATE_NEAR)
+    pool = ops.distance_transform(state, begin, vols, FC.LOCATE_RADIUS, True)
+    torch.cuda.synchronize()
+    assert np.array_equal(begin, at[:-1]) and np.array_equal(state.cpu().numpy(), want_state)
+    assert np.array_equal(_bits(pool), np.concatenate([FC.bits(v).ravel() for v in want_vol]))
+    # the three TSDF steps
+    trunc, mw = 0.03, 1.0
+    want_d, want_w = tsdf.integrate(vols, views, FC.LOCATE_RANGES, t, trunc, FC.LOCATE_NEAR)
+    want_ts = tsdf.states(want_d, want_w, mw)
+    want_e = fusion.distance_transform(want_ts, vols, FC.LOCATE_RADIUS, True)
+    want_blend = [tsdf.blend(want_e[m], want_d[at[m]: at[m + 1]], want_w[at[m]: at[m + 1]], trunc, mw) for m in range(M)]
+    got_d, got_w, got_begin = ops.tsdf_integrate(vols, views, FC.LOCATE_RANGES, depth, trunc, FC.LOCATE_NEAR)
+    got_ts = ops.tsdf_states(got_d, got_w, got_begin, vols, mw)
+    blended = ops.tsdf_blend(got_d, got_w, got_begin, vols, trunc, mw, ops.distance_transform(got_ts, got_begin, vols, FC.LOCATE_RADIUS, True))
+    torch.cuda.synchronize()
+    assert np.array_equal(_bits(got_d), FC.bits(want_d)) and np.array_equal(_bits(got_w), FC.bits(want_w)) and (want_w > 0).any()
+    assert np.array_equal(got_ts.cpu().numpy(), want_ts)
+    assert np.array_equal(_bits(blended), np.concatenate([FC.bits(v).ravel() for v in want_blend]))
+    # labelling: the nodes that are not free
+    comps = ops.label_components(state, begin, vols, 3, 26)
+    torch.cuda.synchronize()
+    want_labels = sg.label_components(want_state, vols, 3, 26)
+    comp_begin, records = sg.component_records(want_labels, vols)
+    assert np.array_equal(comps.labels.cpu().numpy(), want_labels) and np.array_equal(comps.records, records) and np.array_equal(comps.comp_begin, comp_begin)
+    assert (np.diff(comp_begin) > 0).sum() >= M - 1
+    # half-space volumes
+    pls = [(0.6, 0.0, 0.8, -0.01 * m) for m in range(M)]
+    got_planes = ops.plane_volumes(vols, pls, device=dev)
+    torch.cuda.synchronize()
+    assert np.array_equal(_bits(got_planes), np.concatenate([planes.halfspace_volume(v, p).ravel() for v, p in zip(vols, pls)]).view(np.uint32))
+    # surface extraction: the planes' zero level
+    v, f, vrows, frows, o = ops.surface_meshes(got_planes, [vol + (int(a),) for vol, a in zip(vols, at)], 0.0)
+    torch.cuda.synchronize()
+    want_surf = [sc.surface_nets(planes.halfspace_volume(vol, p), np.array(vol[0]), vol[1], vol[2], 0.0) for vol, p in zip(vols, pls)]
+    assert vrows[:, 1].tolist() == [len(w[0]) for w in want_surf] and frows[:, 1].tolist() == [len(w[1]) for w in want_surf]
+    assert o.tolist() == [w[2] for w in want_surf] and sum(len(w[0]) for w in want_surf) > 0
+    assert np.array_equal(v.cpu().numpy().view(np.uint64), np.concatenate([w[0] for w in want_surf]).view(np.uint64))
+    assert np.array_equal(f.cpu().numpy(), np.concatenate([w[1] for w in want_surf]))
+    # mesh SDF: a closed box about the middle of every volume, the magnitudes bit for bit and the sign by the winding number's decision
+    origins, dims, boxes = [np.array(vol[0]) for vol in vols], [vol[3] for vol in vols], []
+    for origin, delta, sample, d in vols:
+        pose = np.eye(4)
+        pose[:3, 3] = origin + ((np.array(d) - 1) / 2 + {"centre": 0.5, "node": 0.0}[sample]) * delta
+        boxes.append(MC.box_mesh(np.maximum(0.3 * np.array(d) * delta, 0.75 * delta), pose)[:2])
+    grids, _, _, dropped = ops.mesh_sdf_batch(boxes, [vol[1] for vol in vols], 0, [vol[2] for vol in vols], origins, dims, device=dev)
+    torch.cuda.synchronize()
+    assert dropped == [0] * M
+    for m, vol in enumerate(vols):
+        want_sdf = sc.mesh_sdf(boxes[m][0], boxes[m][1], vol[1], 0, vol[2], origins[m], dims[m]).data
+        got_sdf = grids[m].cpu().numpy()
+        assert (want_sdf < 0).any() and np.array_equal(FC.bits(np.abs(got_sdf)), FC.bits(np.abs(want_sdf))) and np.array_equal(got_sdf < 0, want_sdf < 0), m
