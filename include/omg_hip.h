@@ -1193,6 +1193,58 @@ int omgx_tsdf_blend(const float* tsdf, const float* weight, int64_t elems, const
                     float* pool, int64_t pool_elems, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * (21) omgx_render_volumes: a depth camera on the SDF pool
+ * (14) draws triangle meshes; the objects of a scene table that exist as volumes only (the obstacles of (17) and (20), the targets
+ * of (18), the half-spaces of (19)) and the poses (15) refines are drawn here as they stand on the device: one ray per pixel is
+ * sphere-traced through the trilinear interpolant of every object's volume, the one (15) reads, and the nearest crossing of
+ * `level` gives depth, object index and normal.  Every TSDF stack pairs "integrate" with "ray-cast the volume": this is the
+ * second half.  omg-planner_amd/volume_camera.py (render_volumes) is the specification; all arithmetic is float64 without
+ * contraction, dot products as (a*x + b*y) + c*z, with + - * /, sqrt, comparisons and float-to-int truncation only, and t, inst,
+ * normal and steps have the specification's bits.  New entry point only, no new struct: omgx_abi_version() stays 14.
+ *
+ * Scene s owns the records [scene_begin[s], scene_begin[s + 1]) of `objects`; of a record pose_inv, lo, dim, inv_delta and
+ * grid_offset are read (`disabled` is ignored: a camera sees the floor).  cameras [S][16] double: fx, fy, cx, cy and Wc, the rows
+ * of world_from_cam; the pixel's ray is (14)'s: dx = (c - cx) / fx, dy = (r - cy) / fy, dz = 1, so t is the depth along the axis.
+ * visible [num_objects] uint8 or NULL (every object): a record whose flag is 0 is skipped.
+ * Per pixel, from best = +inf, inst = -1, for the scene's objects k = 0, 1, ... in order:
+ *   m = pose_inv (widened) times Wc: m[4i+j] = (P[4i]*Wc[j] + P[4i+1]*Wc[4+j]) + P[4i+2]*Wc[8+j],
+ *     m[4i+3] = ((P[4i]*Wc[3] + P[4i+1]*Wc[7]) + P[4i+2]*Wc[11]) + P[4i+3];  o_a = m[4a+3], d_a = (m[4a]*dx + m[4a+1]*dy) + m[4a+2],
+ *     nrm = sqrt((d0*d0 + d1*d1) + d2*d2);  uo_a = (o_a - (double)lo_a) * inv_delta - 0.5, ud_a = d_a * inv_delta, hi_a = dim_a - 1
+ *   slab: t0 = t_min, t1 = +inf, ok; per axis: ud_a == 0: ok &= 0 <= uo_a <= hi_a; else ta = (0.0 - uo_a) / ud_a,
+ *     tb = (hi_a - uo_a) / ud_a, (l, h) = ta <= tb ? (ta, tb) : (tb, ta), l > t0: t0 = l, h < t1: t1 = h;
+ *     ok &= (t0 <= t1) & (t1 < +inf).  Not ok: the object takes no sample.
+ *   sample(t): u_a = uo_a + t*ud_a, !(u_a >= 0): 0, u_a > hi_a: hi_a; i_a = min((int)u_a, dim_a - 2), f_a = u_a - i_a (1.0 on the
+ *     far face); v and g from the cell's eight corners by the lines of (15) (z first, then y, then x; g times inv_delta).
+ *   march: t = t0, v = sample(t0); v <= level: hit at t0.  Else at most max_steps times: s = (v - level) * relax,
+ *     !(s >= min_step): s = min_step; tn = t + s / nrm, !(tn <= t1): tn = t1; vn = sample(tn); vn <= level:
+ *     th = t + (tn - t) * ((v - level) / (v - vn)), !(th >= t): th = t, !(th <= tn): th = tn, hit; else tn >= t1: miss;
+ *     else (t, v) = (tn, vn).  Out of steps: miss.  NaN and +-inf voxels are harmless: t stays finite inside [t0, t1].
+ *   hit and th < best (the lowest index wins a tie): best = th, inst = k, g = the gradient of sample(th),
+ *     n_j = (m[j]*g0 + m[4+j]*g1) + m[8+j]*g2, nn = (n0*n0 + n1*n1) + n2*n2, normal = n / sqrt(nn) if nn > 0, else 0 (camera frame).
+ * t_out [S][H][W] double, inst_out [S][H][W] int32 (local to the scene), normal_out [S][H][W][3] double or NULL, steps_out
+ * [S][H][W] int32 or NULL: the samples the marches of all objects of the pixel took (the normal's is not counted).  Every pixel of
+ * every image is written; background is (+inf, -1, (0,0,0)).  One workgroup of OMGX_CAMERA_PIXELS_PER_WORKGROUP threads per
+ * 16 x 16 pixel tile of a scene, a wave per 8 x 8 block; a wave none of whose rays meets an object's box skips it.  No LDS, no
+ * atomics, no barrier.
+ * `objects`, `scene_begin`, `cameras`, `visible` are on the device, h_* the same on the host; ALL checks are made on the host
+ * copies before any HIP call (the pose is read from the device record).  OMGX_ERR_INVALID: a null pointer (objects may be NULL
+ * with num_objects == 0, pool with pool_elems == 0, everything per scene with num_scenes == 0; visible and h_visible both or
+ * neither), a negative count, H or W < 1; level, t_min, min_step or relax not finite, t_min < 0, min_step <= 0, relax outside
+ * (0, 1], max_steps outside [1, OMGX_VOLUME_CAMERA_MAX_STEPS]; scene_begin not ascending inside [0, num_objects]; a camera not
+ * finite or with fx or fy zero; a visible object of a scene with a dim < 2, inv_delta not finite or not > 0, or a grid that
+ * leaves [0, pool_elems).  OMGX_ERR_UNSUPPORTED as in (14): more than 65535 scenes, more than 2^23 tiles in one image.
+ * num_scenes == 0 returns OMGX_OK and launches nothing; a scene without visible objects is all background.
+ * ------------------------------------------------------------------------------------------- */
+#define OMGX_VOLUME_CAMERA_MAX_STEPS 4096
+int omgx_render_volumes(const omgx_object* objects, const omgx_object* h_objects, int32_t num_objects,
+                        const int32_t* scene_begin, const int32_t* h_scene_begin, int32_t num_scenes,
+                        const float* pool, int64_t pool_elems, const double* cameras, const double* h_cameras,
+                        const uint8_t* visible /* [num_objects] or NULL */, const uint8_t* h_visible, int32_t H, int32_t W,
+                        double level, double t_min, double min_step, double relax, int32_t max_steps,
+                        double* t_out, int32_t* inst_out, double* normal_out /* or NULL */, int32_t* steps_out /* or NULL */,
+                        void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Diagnostics
  * ------------------------------------------------------------------------------------------- */
 const char* omgx_last_error(void); /* thread-local text of the last OMGX_ERR_LAUNCH               */

@@ -35,6 +35,7 @@ SEGMENT_NODES_PER_WORKGROUP = _K["SEGMENT_NODES_PER_WORKGROUP"]
 PLANE_PIXELS_PER_WORKGROUP, PLANE_STAGE_HYPOTHESES = _K["PLANE_PIXELS_PER_WORKGROUP"], _K["PLANE_STAGE_HYPOTHESES"]
 PLANE_MAX_HYPOTHESES, PLANE_NODES_PER_WORKGROUP = _K["PLANE_MAX_HYPOTHESES"], _K["PLANE_NODES_PER_WORKGROUP"]
 TSDF_NODES_PER_WORKGROUP = _K["TSDF_NODES_PER_WORKGROUP"]
+VOLUME_CAMERA_MAX_STEPS = _K["VOLUME_CAMERA_MAX_STEPS"]
 ALG = {"FTL": _K["ALG_FTL"], "FTC": _K["ALG_FTC"], "Exp": _K["ALG_EXP"], "MD": _K["ALG_MD"], "Proj": _K["ALG_PROJ"]}
 ABI_VERSION = 14  # omgx_abi_version() of the library this package was written against
 

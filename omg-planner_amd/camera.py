@@ -185,10 +185,11 @@ def scene_records(scenes, meshes, cam_from_world, intrinsics):
 
 
 class Observation:
-    """observe_scenes' result: the images on the device (t [S,H,W] float64, inst and face [S,H,W] int32) and the batch."""
+    """observe_scenes' result: the images on the device (t [S,H,W] float64, inst and face [S,H,W] int32) and the batch;
+    observe_volumes' has no face image and may have normals [S,H,W,3] float64."""
 
-    def __init__(self, batch, t, inst, face):
-        self.batch, self.t, self.inst, self.face = batch, t, inst, face
+    def __init__(self, batch, t, inst, face, normals=None):
+        self.batch, self.t, self.inst, self.face, self.normals = batch, t, inst, face, normals
 
     def clouds(self, cls: int):
         """S contiguous float64 [N_s,3] device tensors in the world frame (what ops.point_cloud_sdf takes): class 0 is the
@@ -364,3 +365,27 @@ def observe_table(table, cam_from_world, intrinsics, H: int, W: int, level: floa
     batch = ops.CameraBatch(pool, np.concatenate(recs), np.array(begin, np.int64), cameras, device=table.device)
     t, inst, face = ops.render_depth(batch, H, W, cull=cull)
     return Observation(batch, t, inst, face)
+
+
+def observe_volumes(table, cam_from_world, intrinsics, H: int, W: int, level: float = 0.0, targets=None, skip=(), want_normals: bool = False,
+                    **march) -> Observation:
+    """observe_table without the meshes: the objects of an ops.DeviceScenes are ray-cast as volumes, in place, in one launch
+    (ops.render_volumes; volume_camera.render_volumes is the specification).  Nothing is extracted or downloaded and no pose is
+    read from the host mirror: a pose written on the device is seen without sync_host.  targets [S]: the object of each scene that
+    gets label 0 (default 0), every other object 1; skip: (scene, object) pairs that are not drawn; march: min_step, relax,
+    max_steps, t_min of ops.render_volumes.  The instance image names the object's index in its scene (observe_table's names the
+    drawn instances); face is None; normals [S,H,W,3] (camera frame) with want_normals.  It does not call the planner."""
+    from . import ops
+    S = table.num_scenes
+    cfw = np.broadcast_to(np.asarray(cam_from_world, np.float64), (S, 4, 4))
+    intr = np.broadcast_to(np.asarray(intrinsics, np.float64), (S, 4))
+    cameras = np.stack([camera_rows(intr[s], cfw[s]) for s in range(S)]) if S else np.zeros((0, 16))
+    n = len(table.host_objects)
+    labels, visible = np.ones(n, np.int64), np.ones(n, np.uint8)
+    for s in range(S):
+        labels[table._index(s, 0 if targets is None else int(targets[s]))] = 0
+    for s, o in skip:
+        visible[table._index(int(s), int(o))] = 0
+    batch = ops.VolumeCameraBatch(table, cameras, labels)
+    t, inst, normals, _ = ops.render_volumes(table, cameras, H, W, visible=visible, level=level, want_normals=want_normals, **march)
+    return Observation(batch, t, inst, None, normals)

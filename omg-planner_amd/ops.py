@@ -2390,3 +2390,95 @@ def register_clouds(scenes: DeviceScenes, pairs, poses0, points: torch.Tensor, r
                                               int(stride), float(trunc), float(lambda0), float(step_tol), int(max_passes), _ptr(poses), _ptr(stats),
                                               _stream()), "omgx_register_clouds")
     return poses, stats
+
+
+class VolumeCameraBatch(CameraBatch):
+    """What pixel_clouds needs of a CameraBatch for images rendered from a scene table's volumes (render_volumes): the host and
+    device omgx_camera / omgx_instance records, ONE instance per object record of the table, in record order, so that a scene's
+    instances are its objects and the instance image's k is the object index.  Only label, inst_begin and inst_count matter; no
+    mesh is pooled.  cameras [S,16] (camera.camera_rows); labels: one per record (>= 0)."""
+
+    def __init__(self, table: DeviceScenes, cameras, labels):
+        from . import camera as _cam
+        cameras = np.ascontiguousarray(cameras, np.float64)
+        S, n = table.num_scenes, len(table.host_objects)
+        if cameras.shape != (S, 16):
+            raise _lib.OmgHipError(f"cameras must be [{S},16], got {cameras.shape}")
+        if not np.isfinite(cameras).all() or (cameras[:, :2] == 0).any():
+            raise _lib.OmgHipError("a camera is not finite or has a focal length of zero")
+        labels = np.asarray(labels, np.int64).reshape(-1)
+        if len(labels) != n or (n and labels.min() < 0):
+            raise _lib.OmgHipError(f"labels must be {n} integers >= 0, one per object record")
+        begin = np.asarray(table.host_scene_begin, np.int64)
+        self.device, self.cameras = table.device, cameras
+        self.num_meshes, self.num_instances, self.num_scenes = 0, n, S
+        self.h_instances = np.zeros(n, _cam.INSTANCE_DTYPE)
+        self.h_instances["label"] = labels
+        self.h_inst_begin = begin
+        self.h_cameras = np.zeros(S, _cam.CAMERA_DTYPE)
+        self.h_cameras["fx"], self.h_cameras["fy"], self.h_cameras["cx"], self.h_cameras["cy"] = cameras[:, 0], cameras[:, 1], cameras[:, 2], cameras[:, 3]
+        self.h_cameras["world_from_cam"] = cameras[:, 4:]
+        self.h_cameras["inst_begin"], self.h_cameras["inst_count"] = begin[:-1], np.diff(begin)
+        as_bytes = lambda a: torch.from_numpy(np.frombuffer(a.tobytes(), np.uint8).copy()).to(self.device)
+        self.d_instances, self.d_cameras = as_bytes(self.h_instances), as_bytes(self.h_cameras)
+
+
+def _volume_camera_arguments(table: DeviceScenes, cameras, H, W, visible, level, t_min, min_step, relax, max_steps):
+    """render_volumes' checks that need no device: the specification's own (volume_camera.check_scalars / check_table on the
+    table's host mirror), as OmgHipError -> (H, W, cameras [S,16], visible uint8 [n] or None)."""
+    from . import volume_camera as _vc
+    H, W = _image_size(H, W)
+    try:
+        _vc.check_scalars(level, t_min, min_step, relax, max_steps)
+        _, _, cameras, vis = _vc.check_table(table.host_objects, table.host_scene_begin, int(table.pool.numel()), cameras, visible)
+    except ValueError as e:
+        raise _lib.OmgHipError(str(e)) from None
+    # (flags for no records at all are no flags: an empty tensor has no address to pass beside the host's)
+    return H, W, np.ascontiguousarray(cameras), None if visible is None or not len(vis) else np.ascontiguousarray(vis, np.uint8)
+
+
+def render_volumes(table: DeviceScenes, cameras, H: int, W: int, visible=None, level: float = 0.0, t_min: float = 1e-6,
+                   min_step: "float | None" = None, relax: float = 1.0, max_steps: "int | None" = None, want_normals: bool = False,
+                   want_steps: bool = False, out=None):
+    """Depth, object and normal images of the table's S scenes in ONE launch, straight from the records and the pool as they stand
+    on the device (omgx_render_volumes; volume_camera.render_volumes is the specification: the same float64 t and normal bit for
+    bit, the same inst and steps) -> (t [S,H,W] float64, inst [S,H,W] int32, normal [S,H,W,3] float64 or None, steps [S,H,W] int32
+    or None); background is (+inf, -1, (0,0,0)).  A pose written on the device (set_object_poses, register_clouds' write-back) is
+    seen without sync_host: the host mirror is used for the checks of dims and offsets only.  cameras [S,16]: camera.camera_rows;
+    visible: one flag per object record of the table, or None (all); a scene_range view renders its scenes.  out: None or
+    (t, inst, normal or None, steps or None), contiguous device tensors written IN PLACE.  Ordered on torch's current stream."""
+    from . import volume_camera as _vc
+    min_step = _vc.MIN_STEP if min_step is None else min_step
+    max_steps = _vc.DEFAULT_STEPS if max_steps is None else max_steps
+    H, W, h_cameras, h_visible = _volume_camera_arguments(table, cameras, H, W, visible, level, t_min, min_step, relax, max_steps)
+    S, dev = table.num_scenes, table.device
+    if out is None:
+        out = (torch.empty((S, H, W), dtype=torch.float64, device=dev), torch.empty((S, H, W), dtype=torch.int32, device=dev),
+               torch.empty((S, H, W, 3), dtype=torch.float64, device=dev) if want_normals else None,
+               torch.empty((S, H, W), dtype=torch.int32, device=dev) if want_steps else None)
+    t, inst, normal, steps = out
+    for x, name, dtype, shape in ((t, "out[0]", torch.float64, (S, H, W)), (inst, "out[1]", torch.int32, (S, H, W)),
+                                  (normal, "out[2]", torch.float64, (S, H, W, 3)), (steps, "out[3]", torch.int32, (S, H, W))):
+        if x is None and name in ("out[2]", "out[3]"):
+            continue
+        if not isinstance(x, torch.Tensor):
+            raise _lib.OmgHipError(f"{name} must be a tensor")
+        _need(x, dtype, name)
+        if x.device != dev or tuple(x.shape) != shape:
+            raise _lib.OmgHipError(f"{name} must be {list(shape)} on {dev}, got {tuple(x.shape)} on {x.device}")
+    vp = C.c_void_p
+    h_begin = np.ascontiguousarray(table.host_scene_begin, np.int32)
+    with torch.cuda.device(dev):
+        d_cameras = torch.from_numpy(h_cameras).to(dev)
+        d_visible = None if h_visible is None else torch.from_numpy(h_visible).to(dev)
+        n = len(table.host_objects)
+        check(_lib.lib().omgx_render_volumes(_ptr(table.objects) if n else None, vp(table.host_objects.ctypes.data) if n else None, n,
+                                             _ptr(table.scene_begin), vp(h_begin.ctypes.data), S, _ptr(table.pool) if table.pool.numel() else None,
+                                             int(table.pool.numel()), _ptr(d_cameras) if S else None, vp(h_cameras.ctypes.data) if S else None,
+                                             _ptr(d_visible), None if h_visible is None else vp(h_visible.ctypes.data), H, W, float(level),
+                                             float(t_min), float(min_step), float(relax), int(max_steps), _ptr(t), _ptr(inst), _ptr(normal),
+                                             _ptr(steps), _stream()), "omgx_render_volumes")
+        for x in (d_cameras, d_visible):
+            if x is not None:
+                x.record_stream(torch.cuda.current_stream(dev))
+    return t, inst, normal, steps

@@ -50,6 +50,25 @@ def cayley(a) -> np.ndarray:
                      [(2.0 * (a0 * a2) - 2.0 * a1) / den, (2.0 * (a1 * a2) + 2.0 * a0) / den, (one + 2.0 * (a2 * a2)) / den]])
 
 
+def trilinear(pool, base, sx: int, sy: int, fx, fy, fz, inv_delta: float):
+    """The interpolant of value_gradient's docstring from the cell whose corner (0, 0, 0) is pool[base]; base, fx, fy, fz [n];
+    sx, sy: the element strides of x and y -> (v, g_x, g_y, g_z) [n] float64.  Shared with volume_camera.sample: the same lines,
+    the same order."""
+    pool = np.asarray(pool)
+    c = lambda dx, dy, dz: pool[base + dx * sx + dy * sy + dz].astype(np.float64)
+    c000, c001, c010, c011, c100, c101, c110, c111 = c(0, 0, 0), c(0, 0, 1), c(0, 1, 0), c(0, 1, 1), c(1, 0, 0), c(1, 0, 1), c(1, 1, 0), c(1, 1, 1)
+    d00, d01, d10, d11 = c001 - c000, c011 - c010, c101 - c100, c111 - c110
+    c00, c01, c10, c11 = c000 + fz * d00, c010 + fz * d01, c100 + fz * d10, c110 + fz * d11
+    e0, e1 = c01 - c00, c11 - c10
+    c0, c1 = c00 + fy * e0, c10 + fy * e1
+    v = c0 + fx * (c1 - c0)
+    gx = (c1 - c0) * inv_delta
+    gy = (e0 + fx * (e1 - e0)) * inv_delta
+    dz0, dz1 = d00 + fy * (d01 - d00), d10 + fy * (d11 - d10)
+    gz = (dz0 + fx * (dz1 - dz0)) * inv_delta
+    return v, gx, gy, gz
+
+
 def value_gradient(obj, pool, q):
     """The per-point body: q [n,3] (object frame) -> (inside [n] bool, v [n], g [n,3]); v and g are 0 where not inside.
 
@@ -74,19 +93,7 @@ def value_gradient(obj, pool, q):
     i = [x.astype(np.int64) for x in u]
     fx, fy, fz = (x - k.astype(np.float64) for x, k in zip(u, i))
     base = off + (i[0] * dim[1] + i[1]) * dim[2] + i[2]
-    sx, sy = dim[1] * dim[2], dim[2]
-    pool = np.asarray(pool)
-    c = lambda dx, dy, dz: pool[base + dx * sx + dy * sy + dz].astype(np.float64)
-    c000, c001, c010, c011, c100, c101, c110, c111 = c(0, 0, 0), c(0, 0, 1), c(0, 1, 0), c(0, 1, 1), c(1, 0, 0), c(1, 0, 1), c(1, 1, 0), c(1, 1, 1)
-    d00, d01, d10, d11 = c001 - c000, c011 - c010, c101 - c100, c111 - c110
-    c00, c01, c10, c11 = c000 + fz * d00, c010 + fz * d01, c100 + fz * d10, c110 + fz * d11
-    e0, e1 = c01 - c00, c11 - c10
-    c0, c1 = c00 + fy * e0, c10 + fy * e1
-    v = c0 + fx * (c1 - c0)
-    gx = (c1 - c0) * inv_delta
-    gy = (e0 + fx * (e1 - e0)) * inv_delta
-    dz0, dz1 = d00 + fy * (d01 - d00), d10 + fy * (d11 - d10)
-    gz = (dz0 + fx * (dz1 - dz0)) * inv_delta
+    v, gx, gy, gz = trilinear(pool, base, dim[1] * dim[2], dim[2], fx, fy, fz, inv_delta)
     zero = lambda x: np.where(inside, x, 0.0)
     return inside, zero(v), np.stack([zero(gx), zero(gy), zero(gz)], -1)
 
