@@ -1245,6 +1245,59 @@ int omgx_render_volumes(const omgx_object* objects, const omgx_object* h_objects
                         void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * (22) omgx_render_spheres, omgx_clear_robot: a robot self-filter for depth images and obstacle states
+ * A camera beside or on the arm sees the arm; sections 17 to 20 assume the image shows the scene alone.  Here the arm is N
+ * padded spheres, each fixed in the frame of one of the OMGX_NUM_LINKS links of omgx_forward_kinematics (link_poses
+ * [C][10][4][4], center_offset applied).  omg-planner_amd/robot_filter.py (camera_spheres, render_spheres, clear_states) is
+ * the specification; all arithmetic is float64 without contraction, dot products as (a*x + b*y) + c*z, rejections as negated
+ * comparisons, and the results have the specification's bits.  New entry points only: omgx_abi_version() stays 14.
+ *
+ * omgx_render_spheres: ONE launch for V views, a workgroup of OMGX_CAMERA_PIXELS_PER_WORKGROUP threads per 16 x 16 pixel tile
+ *   (a wave per 8 x 8 block), gridDim.y the view.  View v has the camera cameras[v] (the intrinsics and world_from_cam = (R, t)
+ *   are read) and the configuration config_of_view[v].  Sphere n = (local[n][0..2], local[n][3]) in the frame of link[n]:
+ *     P = link_poses[config][link[n]];  w_k = ((P[k][0]*p0 + P[k][1]*p1) + P[k][2]*p2) + P[k][3];  u = w - t
+ *     c_k = (R[0][k]*u0 + R[1][k]*u1) + R[2][k]*u2;  cam_spheres[v][n] = (c0, c1, c2, local[n][3] + pad)
+ *   staged in LDS OMGX_ROBOT_SPHERE_CHUNK at a time by every workgroup (the same bits) and written by the workgroups of tile 0.
+ *   Pixel (r, c): dx = (c - cx) / fx, dy = (r - cy) / fy, dd = (dx*dx + dy*dy) + 1; per sphere (x, y, z, R) in order:
+ *     b = (x*dx + y*dy) + z;  q = ((x*x + y*y) + z*z) - R*R;  disc = b*b - q*dd;  a miss if !(disc >= 0)
+ *     s = sqrt(disc), t0 = (b - s) / dd, t1 = (b + s) / dd;  a miss if !(t1 > t_min);  entry = t0 > t_min ? t0 : t_min
+ *     if entry < best: best = entry, sphere = n                         (the lowest index wins a tie)
+ *   t_near [V][H][W] double (+inf on a miss), sphere [V][H][W] int32 (-1 on a miss); every pixel is written.
+ *   cull != 0: a wave skips a sphere that none of its rays can meet, one ballot of section 14's `active` on q and the centre
+ *   (q <= 0 | (b > 0 & b*b >= q*dd)).  Where that test says no the ray misses, so the cull changes no bit; cull == 0 proves it.
+ * omgx_clear_robot: ONE launch for M volumes, one thread per node in runs of OMGX_FUSION_NODES_PER_WORKGROUP; volumes, views,
+ *   view_range, state_begin, depth, near and the projection are omgx_carve_views's own.  For the node at p, over the views v of
+ *   its volume's range: q = cam_from_grid p;
+ *     inside: ((q0-x)^2 + (q1-y)^2) + (q2-z)^2 <= R*R for some sphere (x, y, z, R) of cam_spheres[v] (seen or not)
+ *     front:  z > near, the pixel (r, c) inside the image, t_near[v][r][c] < inf, depth[v][r][c] >= t_near[v][r][c] - tol,
+ *             and z < t_near[v][r][c]
+ *   state = FREE if inside held in any view; else FREE if the state is UNKNOWN and front held in any view; else unchanged.
+ *   The state is updated IN PLACE; elements outside every volume's range are not touched.  Per view the spheres pass through
+ *   LDS in chunks; cull != 0: a sphere whose centre is further from the ball around the run's nodes than R + the ball's radius
+ *   + 1e-9 of the scale of the numbers involved is not staged (omg_robot_filter_body.h: robot_run_drops); cull == 0 proves
+ *   that no bit depends on it (a sphere that is not finite is never dropped: the arithmetic above decides).
+ * ALL checks are made on the host copies before any HIP call.  OMGX_ERR_INVALID: a null pointer that a positive count needs, a
+ * negative count, H or W < 1 (with views), pad or t_min negative or not finite, near or tol not finite, a sphere, pose, camera
+ * or view field not finite, a negative radius, fx or fy zero, a link outside [0, OMGX_NUM_LINKS), a configuration outside
+ * [0, num_configs), and omgx_carve_views's errors of the volumes, the view ranges and the state ranges.  h_cam_spheres may be
+ * NULL: the spheres are then not checked (they are omgx_render_spheres's output).  OMGX_ERR_UNSUPPORTED: more than
+ * OMGX_ROBOT_MAX_SPHERES spheres, more than 65535 views or 2^23 tiles (omgx_render_spheres), num_views * H * W > 2^31 - 1.
+ * Zero views, spheres or volumes are legal.  No atomics; every element is written by one thread.
+ * ------------------------------------------------------------------------------------------- */
+#define OMGX_ROBOT_SPHERE_CHUNK 256
+#define OMGX_ROBOT_MAX_SPHERES 65536
+int omgx_render_spheres(const double* local /* [N][4] */, const double* h_local, const int32_t* link /* [N] */, const int32_t* h_link,
+                        int32_t num_spheres, const double* link_poses /* [C][10][16] */, const double* h_link_poses, int32_t num_configs,
+                        const omgx_camera* cameras, const omgx_camera* h_cameras, const int32_t* config_of_view,
+                        const int32_t* h_config_of_view, int32_t num_views, int32_t H, int32_t W, double pad, double t_min, int32_t cull,
+                        double* cam_spheres /* [V][N][4] */, double* t_near, int32_t* sphere, void* stream);
+int omgx_clear_robot(const omgx_mesh* volumes, const omgx_mesh* h_volumes, int32_t num_volumes, const double* views,
+                     const double* h_views, int32_t num_views, const int32_t* view_range, const int32_t* h_view_range,
+                     const int64_t* state_begin, const int64_t* h_state_begin, const double* depth, const double* t_near, int32_t H,
+                     int32_t W, const double* cam_spheres /* [V][N][4] */, const double* h_cam_spheres /* or NULL */,
+                     int32_t num_spheres, double near, double tol, int32_t cull, uint8_t* state, int64_t state_elems, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Diagnostics
  * ------------------------------------------------------------------------------------------- */
 const char* omgx_last_error(void); /* thread-local text of the last OMGX_ERR_LAUNCH               */

@@ -14,7 +14,7 @@ with dx = (c - cx) / fx, dy = (r - cy) / fy, dz = 1, so the hit parameter t is t
 Instance: one (mesh, pose, label), see INSTANCE_DTYPE and instance_records.
 
 Everything specified is plain numpy float64 with every dot product written (x*x' + y*y') + z*z', so that the device can equal
-the bits.  Not part of the contract: colour, textures, lighting, a far plane, noise, the robot's own links in the image.
+the bits.  Not part of the contract: colour, textures, lighting, a far plane, noise.  The robot's own links in a real image: robot_filter.py.
 """
 from __future__ import annotations
 
@@ -209,15 +209,34 @@ class Observation:
             views[m] = fusion.view_rows([cams[k][s] for k in ("fx", "fy", "cx", "cy")], cam_from_world @ poses[table._index(int(s), int(o))])
         return views
 
+    def robot_view(self, spheres, robot_blob, P: int, joints, pad: float, tol: float, cull: bool = True):
+        """The arm as this observation's cameras see it -> ops.RobotView (t_near, sphere, cam_spheres, tol, mask, all on the
+        device).  spheres: ops.RobotSpheres; robot_blob, P: what ops.forward_kinematics takes; joints [S,9] float64 on the device:
+        the arm's configuration in every scene's image.  One kinematics launch and one render launch (ops.render_spheres with the
+        batch's own camera records; robot_filter.py is the specification); mask = explained(self.t, t_near, tol): the pixels
+        that show the arm or what it hides, which serves as the `skip` of fit_supports too."""
+        from . import ops
+        S = self.batch.num_scenes
+        if tuple(joints.shape) != (S, 9):
+            raise _lib.OmgHipError(f"joints must be [{S},9], one configuration per scene, got {tuple(joints.shape)}")
+        poses, _, _ = ops.forward_kinematics(robot_blob, P, joints, want_joint_info=False)
+        H, W = int(self.t.shape[1]), int(self.t.shape[2])
+        t_near, which, cam_spheres = ops.render_spheres(spheres, poses, self.batch, np.arange(S), H, W, pad=pad, cull=cull)
+        view = ops.RobotView(t_near, which, cam_spheres, tol)
+        view.mask = view.explained(self.t)
+        return view
+
     def fuse_obstacles(self, table, pairs, layouts, band: float, near: float, reach: float, unknown_occupied: bool = True,
-                       target_free: bool = True) -> int:
+                       target_free: bool = True, robot=None) -> int:
         """The obstacle volumes of the (scene, obj) `pairs` of an ops.DeviceScenes from this observation's depth images
         (ops.DeviceScenes.fuse_obstacles, which documents layouts, band, near and reach): pair m is seen by the camera of its own
         scene, through the view row fusion.view_rows(intrinsics, cam_from_world @ world_from_obj) with the object's pose from the
         table's host mirror.  target_free: the pixels of label 0 (the target) count as background, so that the volume holds the
-        non-target points only, as omg/core.py:849-851 splits them.  Returns the radius used."""
+        non-target points only, as omg/core.py:849-851 splits them.  robot: robot_view's result (one image per scene): the arm's
+        pixels carry no information and its nodes are cleared.  Returns the radius used."""
         pairs, depth, views, ranges, free_mask = self._obstacle_views(table, pairs, target_free)
-        return table.fuse_obstacles(pairs, depth, views, ranges, layouts, band, near, reach, unknown_occupied, free_mask)
+        return table.fuse_obstacles(pairs, depth, views, ranges, layouts, band, near, reach, unknown_occupied, free_mask,
+                                    robot=None if robot is None else robot.take(pairs[:, 0]))
 
     def _obstacle_views(self, table, pairs, target_free: bool):
         """What DeviceScenes.fuse_obstacles / integrate_obstacles take for the (scene, obj) `pairs`: (pairs [n,2], depth [n,H,W]:
@@ -237,28 +256,30 @@ class Observation:
 
     def integrate_obstacles(self, table, pairs, layouts, trunc: float, near: float, reach: float, tsdf_volumes=None,
                             unknown_occupied: bool = True, min_weight: float = 1.0, wmax: float = float("inf"), weights=None,
-                            target_free: bool = True):
+                            target_free: bool = True, robot=None):
         """fuse_obstacles with weighted TSDF fusion (ops.DeviceScenes.integrate_obstacles, which documents trunc, min_weight,
         wmax, weights and tsdf_volumes): the same view rows and the same target mask.  Passing the returned TsdfVolumes back in
-        with a later observation adds its frame to the same volumes.  Returns (radius, the TsdfVolumes)."""
+        with a later observation adds its frame to the same volumes.  robot as fuse_obstacles takes it.
+        Returns (radius, the TsdfVolumes)."""
         pairs, depth, views, ranges, free_mask = self._obstacle_views(table, pairs, target_free)
         return table.integrate_obstacles(pairs, tsdf_volumes, depth, views, ranges, layouts, trunc, near, reach, unknown_occupied, min_weight,
-                                         wmax, weights, free_mask)
+                                         wmax, weights, free_mask, robot=None if robot is None else robot.take(pairs[:, 0]))
 
     def segment_obstacles(self, table, target_pairs, obstacle_pairs, layouts, band: float, near: float, reach: float, seeds,
-                          min_nodes: int, connectivity: int = 6, margin=None, free_mask=None):
+                          min_nodes: int, connectivity: int = 6, margin=None, free_mask=None, robot=None):
         """The target's and the obstacles' volumes of an ops.DeviceScenes from this observation's depth images ALONE
         (ops.DeviceScenes.segment_obstacles, which documents the arguments): no instance image is read.  Pair n is seen by the
         camera of its own scene through the view row of obstacle_pairs[n] (view_rows); the layout, the seed and the target's
         volume are in that object's frame, so target_pairs[n] should stand at the same pose.  free_mask: bool [n,H,W], the pixels
-        that count as background (explained_mask of the known objects: the support).  -> (radius, records [n,8], Components)."""
+        that count as background (explained_mask of the known objects: the support); robot as fuse_obstacles takes it, so that
+        the arm is no component.  -> (radius, records [n,8], Components)."""
         import torch
         obstacle_pairs = np.asarray(obstacle_pairs, np.int64).reshape(-1, 2)
         views = self.view_rows(table, obstacle_pairs)
         depth = self.t[torch.from_numpy(obstacle_pairs[:, 0].copy()).to(self.t.device)].contiguous()
         ranges = np.stack([np.arange(len(obstacle_pairs)), np.ones(len(obstacle_pairs), np.int64)], -1)
         return table.segment_obstacles(target_pairs, obstacle_pairs, depth, views, ranges, layouts, band, near, reach, seeds, min_nodes,
-                                       connectivity, margin, free_mask)
+                                       connectivity, margin, free_mask, robot=None if robot is None else robot.take(obstacle_pairs[:, 0]))
 
 
     def intrinsics(self) -> np.ndarray:
@@ -266,12 +287,13 @@ class Observation:
         cams = self.batch.h_cameras
         return np.stack([np.asarray(cams[k], np.float64) for k in ("fx", "fy", "cx", "cy")], -1)
 
-    def fit_supports(self, triples, tol: float, up_world=None, cos_min: float = -1.0, refine: int = 2, min_nn: float = 1e-10):
+    def fit_supports(self, triples, tol: float, up_world=None, cos_min: float = -1.0, refine: int = 2, min_nn: float = 1e-10, skip=None):
         """The support of every scene from its depth image ALONE: one plane per scene fitted to self.t (ops.fit_planes, which
         documents triples [S,K,3], tol, cos_min, refine and min_nn; planes.fit_planes is the specification), and the pixels on or
         behind it (ops.plane_mask), which segment_obstacles takes as free_mask in place of explained_mask's rendering of a known
         table.  up_world [3]: a direction of the world (the table's normal, roughly: gravity) that the plane's normal must agree
         with to within cos_min; it is turned into every camera's frame on the host (the rows of world_from_cam, transposed).
+        skip: the pixels that take no part, as ops.fit_planes and ops.plane_mask take them (a RobotView's mask: the arm).
         -> (ops.PlaneFit, mask: bool [S,H,W] on the device).  The planes are in the cameras' frames: support_planes moves them."""
         from . import ops
         intr = self.intrinsics()
@@ -279,8 +301,8 @@ class Observation:
         if up_world is not None:
             u = np.asarray(up_world, np.float64).reshape(3)
             up = np.stack([w.reshape(3, 4)[:, :3].T @ u for w in np.asarray(self.batch.h_cameras["world_from_cam"], np.float64)])
-        fit = ops.fit_planes(intr, self.t, triples, tol, up=up, cos_min=cos_min, min_nn=min_nn, refine=refine)
-        return fit, ops.plane_mask(intr, self.t, fit.planes, tol)
+        fit = ops.fit_planes(intr, self.t, triples, tol, skip=skip, up=up, cos_min=cos_min, min_nn=min_nn, refine=refine)
+        return fit, ops.plane_mask(intr, self.t, fit.planes, tol, skip=skip)
 
     def support_planes(self, table, pairs, fit) -> np.ndarray:
         """The fitted planes [n,4] in the frames of the (scene, obj) `pairs` of an ops.DeviceScenes (what

@@ -500,7 +500,7 @@ class DeviceScenes:
         return verts, faces, vrows[which], frows[which], open_edges[which]
 
     def fuse_obstacles(self, pairs, depth: torch.Tensor, views, view_range, layouts, band: float, near: float, reach: float,
-                       unknown_occupied: bool = True, free_mask: "torch.Tensor | None" = None) -> int:
+                       unknown_occupied: bool = True, free_mask: "torch.Tensor | None" = None, robot: "RobotView | None" = None) -> int:
         """The observed obstacle volumes of the (scene, obj) `pairs` from depth views, written straight into the pool: ONE carve
         launch and three transform launches for all pairs (carve_views, distance_transform), then grid_slot's slot becomes the
         object's volume through replace_grid(fit="device"), object by object.  layouts: one (origin [3], delta, dims [3]) per pair,
@@ -508,7 +508,9 @@ class DeviceScenes:
         object's pose) and view_range [n,2] as carve_views takes them; depth [V,H,W] float64 on the device.  reach: the distance up
         to which the cost reads the volume (epsilon + clearance): radius = ceil(reach / delta + 0.5) + 1 of the finest layout, so
         the saturation lies beyond it.  free_mask: a bool tensor [V,H,W]; its pixels are set to +inf first (the target's pixels:
-        the reference's "non-target points only").  Returns the radius."""
+        the reference's "non-target points only").  robot: a RobotView whose images belong to the views, one by one (the arm as
+        the same cameras see it): the pixels it explains are set to 0.0, no information, before the carve, and clear_robot frees
+        the arm's nodes between the carve and the transform (_robot_step).  Returns the radius."""
         from . import fusion as _fu
         self._changing(volumes=True)
         pairs = np.asarray(pairs, np.int64).reshape(-1, 2)
@@ -522,25 +524,26 @@ class DeviceScenes:
         # everything that can be refused is refused here, before grid_slot offers a slot: the radius, the layouts, the views
         _carve_arguments([(origin, delta, "centre", dims) for origin, delta, dims in layouts], views, view_range, depth, band, near, None)
         radius = _fusion_radius(max(_fu.obstacle_radius(reach, float(delta)) for _, delta, _ in layouts))
-        depth = _masked_depth(depth, free_mask)
+        depth, clear = _robot_step(robot, _masked_depth(depth, free_mask), views, view_range, near)
         slots, volumes = [], []
         for (s, o), (origin, delta, dims) in zip(pairs, layouts):
             slot = self.grid_slot(int(s), int(o), tuple(int(d) for d in dims))
             slots.append(slot)
             volumes.append((origin, delta, "centre", dims, (slot.data_ptr() - self.pool.data_ptr()) // 4))
-        fuse_views(volumes, views, view_range, depth, band, near, radius, unknown_occupied, out=self.pool)
+        fuse_views(volumes, views, view_range, depth, band, near, radius, unknown_occupied, out=self.pool, clear=clear)
         for (s, o), (origin, delta, _), slot in zip(pairs, layouts, slots):
             self.replace_grid(int(s), int(o), slot, origin, float(delta), fit="device")
         return radius
 
     def integrate_obstacles(self, pairs, tsdf_volumes: "TsdfVolumes | None", depth: torch.Tensor, views, view_range, layouts, trunc: float,
                             near: float, reach: float, unknown_occupied: bool = True, min_weight: float = 1.0, wmax: float = float("inf"),
-                            weights=None, free_mask: "torch.Tensor | None" = None):
+                            weights=None, free_mask: "torch.Tensor | None" = None, robot: "RobotView | None" = None):
         """fuse_obstacles with weighted TSDF fusion (fuse_tsdf; tsdf.fuse is the specification): the volumes of the (scene, obj)
         `pairs` have their zero level on the observed surface, between the nodes, not `band` in front of it on voxel faces; with
         a finite wmax old frames fade, so that an object that was taken away becomes free again.  pairs, depth, views,
-        view_range, layouts, near, reach, unknown_occupied and free_mask as fuse_obstacles takes them; trunc: the truncation (a
-        few voxels, a few sigma of the sensor); weights: one per view.  tsdf_volumes: None for the first frame, or what an
+        view_range, layouts, near, reach, unknown_occupied, free_mask and robot as fuse_obstacles takes them (clear_robot runs
+        on the states of this frame's arm, between tsdf_states and the transform: the pairs themselves keep what they saw);
+        trunc: the truncation (a few voxels, a few sigma of the sensor); weights: one per view.  tsdf_volumes: None for the first frame, or what an
         earlier call returned: this frame is added to the same pairs (its layouts, trunc, near and wmax must be the call's).
         One integrate launch, then states, the three transform launches and the blend for all pairs, written straight into
         grid_slot's slots, which become the objects' volumes through replace_grid(fit="device").  Everything that can be
@@ -559,7 +562,7 @@ class DeviceScenes:
         volumes = [(origin, delta, "centre", dims) for origin, delta, dims in layouts]
         _, _, _, _, trunc, wmax = _tsdf_arguments(volumes, views, view_range, depth, trunc, near, weights, wmax, None)
         radius = _fusion_radius(max(_fu.obstacle_radius(reach, float(delta)) for _, delta, _ in layouts))
-        depth = _masked_depth(depth, free_mask)
+        depth, clear = _robot_step(robot, _masked_depth(depth, free_mask), views, view_range, near)
         if depth.device != self.pool.device:
             raise _lib.OmgHipError(f"depth must be on {self.pool.device}, got {depth.device}")
         if tsdf_volumes is None:
@@ -574,14 +577,15 @@ class DeviceScenes:
                 raise _lib.OmgHipError(f"tsdf_volumes are on {tsdf_volumes.device}, depth on {depth.device}")
         slots = [self.grid_slot(int(s), int(o), tuple(int(d) for d in dims)) for (s, o), (_, _, dims) in zip(pairs, layouts)]
         tsdf_volumes.integrate(depth, views, view_range, weights)
-        tsdf_volumes.signed(radius, unknown_occupied, min_weight, out=self.pool, offsets=[(slot.data_ptr() - self.pool.data_ptr()) // 4 for slot in slots])
+        tsdf_volumes.signed(radius, unknown_occupied, min_weight, out=self.pool, offsets=[(slot.data_ptr() - self.pool.data_ptr()) // 4 for slot in slots],
+                            clear=clear)
         for (s, o), (origin, delta, _), slot in zip(pairs, layouts, slots):
             self.replace_grid(int(s), int(o), slot, origin, float(delta), fit="device")
         return radius, tsdf_volumes
 
     def segment_obstacles(self, target_pairs, obstacle_pairs, depth: torch.Tensor, views, view_range, layouts, band: float, near: float,
                           reach: float, seeds, min_nodes: int, connectivity: int = 6, margin: "int | None" = None,
-                          free_mask: "torch.Tensor | None" = None):
+                          free_mask: "torch.Tensor | None" = None, robot: "RobotView | None" = None):
         """fuse_obstacles without labels: per scene n the layout (origin [3], delta, dims [3]: voxel centres, in the frame both of
         the scene's pairs stand in) is carved from its views, the SURFACE nodes are labelled (label_components), the target is the
         component nearest to seeds[n] (a point of the layout's frame, converted to index units on the host;
@@ -589,7 +593,8 @@ class DeviceScenes:
         target_pairs[n] and the whole layout in mode 1 the volume of obstacle_pairs[n], both through grid_slot and
         replace_grid(fit="device").  One carve launch, one labelling and one set of crop and transform launches for all scenes;
         two small downloads (counts, records).  margin: nodes around the target's box (default radius + 1, so that the target's
-        zero level closes inside its crop); free_mask as fuse_obstacles takes it (camera.explained_mask: the support).
+        zero level closes inside its crop); free_mask and robot as fuse_obstacles takes them (camera.explained_mask: the
+        support; the arm is cleared before the labelling, so that it is no component).
         -> (radius, the chosen records [n,8] int32, the Components).  segmentation.segment_views is the specification."""
         from . import fusion as _fu, segmentation as _sg
         self._changing(volumes=True)
@@ -610,8 +615,10 @@ class DeviceScenes:
         _carve_arguments(volumes, views, view_range, depth, band, near, None)
         radius = _fusion_radius(max(_fu.obstacle_radius(reach, float(delta)) for _, delta, _ in layouts))
         margin = radius + 1 if margin is None else int(margin)
-        depth = _masked_depth(depth, free_mask)
+        depth, clear = _robot_step(robot, _masked_depth(depth, free_mask), views, view_range, near)
         state, begin = carve_views(volumes, views, view_range, depth, band, near)
+        if clear is not None:
+            clear(state, begin, volumes)
         comps = label_components(state, begin, volumes, 1, connectivity)
         try:  # (a scene without a component of min_nodes nodes is refused here: no slot has been offered yet)
             ranks = [_sg.pick_component(comps.of(m), _sg.point_to_index(volumes[m], seeds[m]), min_nodes) for m in range(n)]
@@ -1594,11 +1601,14 @@ def distance_transform(state: torch.Tensor, state_begin, volumes, radius: int, u
 
 
 def fuse_views(volumes, views, view_range, depth: torch.Tensor, band: float, near: float, radius: int, unknown_occupied: bool = True,
-               out: "torch.Tensor | None" = None):
+               out: "torch.Tensor | None" = None, clear=None):
     """carve_views and distance_transform for M volumes, four launches in all (fusion.fuse_views is the specification) -> out,
-    as distance_transform returns it.  The radius is checked before the carve launch."""
+    as distance_transform returns it.  The radius is checked before the carve launch.  clear: None, or a step between the two
+    halves, clear(state, state_begin, volumes), that changes the state bytes in place (_robot_step)."""
     radius = _fusion_radius(radius)
     state, begin = carve_views(volumes, views, view_range, depth, band, near)
+    if clear is not None:
+        clear(state, begin, volumes)
     return distance_transform(state, begin, volumes, radius, unknown_occupied, out)
 
 
@@ -1705,9 +1715,11 @@ def tsdf_blend(tsdf: torch.Tensor, weight: torch.Tensor, state_begin, volumes, t
     return out
 
 
-def _tsdf_signed(tsdf, weight, begin, volumes, trunc, radius, unknown_occupied, min_weight, out):
+def _tsdf_signed(tsdf, weight, begin, volumes, trunc, radius, unknown_occupied, min_weight, out, clear=None):
     batch = _VolumeBatch.of(volumes, begin)  # (one batch: the records and state_begin go to the device once for the three)
     state = tsdf_states(tsdf, weight, None, batch, min_weight)
+    if clear is not None:  # (fuse_views' optional step: the state bytes change before the transform reads them)
+        clear(state, None, batch)
     out = distance_transform(state, None, batch, radius, unknown_occupied, out)
     return tsdf_blend(tsdf, weight, None, batch, trunc, min_weight, out)
 
@@ -1755,17 +1767,18 @@ class TsdfVolumes:
         """A new uint8 tensor of state bytes at state_begin (tsdf_states)."""
         return tsdf_states(self.tsdf, self.weight, None, self._batch, min_weight)
 
-    def signed(self, radius: int, unknown_occupied: bool = True, min_weight: float = 1.0, out: "torch.Tensor | None" = None, offsets=None):
+    def signed(self, radius: int, unknown_occupied: bool = True, min_weight: float = 1.0, out: "torch.Tensor | None" = None, offsets=None,
+               clear=None):
         """The signed float32 volumes: states, distance_transform and tsdf_blend -> out, as distance_transform returns it.
         offsets: the volumes' element offsets in `out` for this call (a pool's slots change from frame to frame); default: the
-        layouts' own."""
+        layouts' own.  clear: fuse_views' optional step between the states and the transform."""
         radius, min_weight = _fusion_radius(radius), _tsdf_positive("min_weight", min_weight)
         batch = self._batch
         if offsets is not None:
             if len(offsets) != batch.M:
                 raise _lib.OmgHipError(f"{batch.M} volumes need as many offsets")
             batch = _VolumeBatch([v[:4] + (int(o),) for v, o in zip(self.volumes, offsets)], like=batch)  # (new records, the same state_begin)
-        return _tsdf_signed(self.tsdf, self.weight, None, batch, self.trunc, radius, unknown_occupied, min_weight, out)
+        return _tsdf_signed(self.tsdf, self.weight, None, batch, self.trunc, radius, unknown_occupied, min_weight, out, clear)
 
 
 class Components:
@@ -2482,3 +2495,183 @@ def render_volumes(table: DeviceScenes, cameras, H: int, W: int, visible=None, l
             if x is not None:
                 x.record_stream(torch.cuda.current_stream(dev))
     return t, inst, normal, steps
+
+
+class RobotSpheres:
+    """The arm as N padded spheres on the host and on the device (robot_filter.py): local [N,4] float64, a centre in the frame of
+    link[n] (0..9, the links of forward_kinematics with center_offset applied: the frame of PandaModel.collision_points) and a
+    radius, finite and >= 0."""
+
+    def __init__(self, local, link, device="cuda:0"):
+        from . import robot_filter as _rf
+        try:
+            h_local, h_link = _rf._spheres(local, link)
+        except ValueError as e:
+            raise _lib.OmgHipError(str(e)) from None
+        self.h_local, self.h_link = np.ascontiguousarray(h_local), np.ascontiguousarray(h_link, np.int32)
+        self.N, self.device = len(self.h_link), torch.device(device)
+        self.local, self.link = torch.from_numpy(self.h_local).to(self.device), torch.from_numpy(self.h_link).to(self.device)
+
+    @classmethod
+    def from_points(cls, collision_points, radius, device="cuda:0") -> "RobotSpheres":
+        """One sphere per collision point: collision_points [10,P,3]; radius: a scalar or one value per link."""
+        pts = np.asarray(collision_points, np.float64)
+        if pts.ndim != 3 or pts.shape[0] != 10 or pts.shape[2] != 3:
+            raise _lib.OmgHipError(f"collision_points must be [10,P,3], got {pts.shape}")
+        try:
+            r = np.broadcast_to(np.asarray(radius, np.float64).reshape(-1, 1), (10, pts.shape[1]))
+        except ValueError:
+            raise _lib.OmgHipError("radius must be a scalar or one value per link") from None
+        return cls(np.concatenate([pts.reshape(-1, 3), r.reshape(-1, 1)], 1), np.repeat(np.arange(10), pts.shape[1]), device)
+
+
+def _camera_records(cameras, dev):
+    """(device records, host records) of a CameraBatch or of camera.CAMERA_DTYPE records on the host."""
+    from . import camera as _cam
+    if isinstance(cameras, CameraBatch):
+        return cameras.d_cameras, cameras.h_cameras
+    h = np.ascontiguousarray(cameras).reshape(-1)
+    if h.dtype != _cam.CAMERA_DTYPE:
+        raise _lib.OmgHipError("cameras must be camera.CAMERA_DTYPE records or a CameraBatch")
+    return torch.from_numpy(np.frombuffer(h.tobytes(), np.uint8).copy()).to(dev), h
+
+
+def render_spheres(spheres: RobotSpheres, link_poses: torch.Tensor, cameras, config_of_view, H: int, W: int, pad: float = 0.0,
+                   t_min: float = 1e-6, cull: bool = True):
+    """The arm's spheres as V cameras see them, in ONE launch (omgx_render_spheres; robot_filter.camera_spheres and render_spheres
+    are the specification: the same bits) -> (t_near [V,H,W] float64, +inf where no sphere is seen; sphere [V,H,W] int32, -1
+    there; cam_spheres [V,N,4] float64: centre in the camera's frame and radius + pad).  link_poses [C,10,4,4]: a float64 device
+    tensor (forward_kinematics); cameras: V camera.CAMERA_DTYPE records on the host, or a CameraBatch (its own records, already on
+    the device); config_of_view [V] host integers in 0..C-1.  The poses are downloaded once for the checks (one small copy that
+    waits for the stream).  cull=False walks every sphere in every wave: the same bits."""
+    from . import robot_filter as _rf
+    H, W = _image_size(H, W)
+    _need(link_poses, torch.float64, "link_poses")
+    if link_poses.dim() != 4 or tuple(link_poses.shape[1:]) != (10, 4, 4) or link_poses.device != spheres.device:
+        raise _lib.OmgHipError(f"link_poses must be [C,10,4,4] on {spheres.device}, got {tuple(link_poses.shape)} on {link_poses.device}")
+    dev, N, Cn, vp = spheres.device, spheres.N, int(link_poses.shape[0]), C.c_void_p
+    d_cam, h_cam = _camera_records(cameras, dev)
+    V = len(h_cam)
+    h_cfg = np.ascontiguousarray(np.asarray(config_of_view, np.int64).reshape(-1), np.int32)
+    h_poses = np.ascontiguousarray(link_poses.cpu().numpy())
+    try:  # (the specification's own checks, as this module's error; nothing has touched the device's memory yet)
+        if not (np.isfinite(float(t_min)) and float(t_min) >= 0):
+            raise ValueError("t_min must be finite and not negative")
+        _rf.camera_spheres(h_poses, np.zeros((0, 4)), np.zeros(0, np.int64), h_cam, h_cfg, pad)
+    except ValueError as e:
+        raise _lib.OmgHipError(str(e)) from None
+    t_near = torch.empty((V, H, W), dtype=torch.float64, device=dev)
+    which = torch.empty((V, H, W), dtype=torch.int32, device=dev)
+    cam_spheres = torch.empty((V, N, 4), dtype=torch.float64, device=dev)
+    with torch.cuda.device(dev):
+        d_cfg = torch.from_numpy(h_cfg).to(dev)
+        check(_lib.lib().omgx_render_spheres(_ptr(spheres.local) if N else None, vp(spheres.h_local.ctypes.data) if N else None,
+                                             _ptr(spheres.link) if N else None, vp(spheres.h_link.ctypes.data) if N else None, N,
+                                             _ptr(link_poses) if Cn else None, vp(h_poses.ctypes.data) if Cn else None, Cn,
+                                             _ptr(d_cam) if V else None, vp(h_cam.ctypes.data) if V else None, _ptr(d_cfg) if V else None,
+                                             vp(h_cfg.ctypes.data) if V else None, V, H, W, float(pad), float(t_min), int(bool(cull)),
+                                             _ptr(cam_spheres) if V and N else None, _ptr(t_near) if V else None, _ptr(which) if V else None,
+                                             _stream()), "omgx_render_spheres")
+        for x in (d_cfg, d_cam):
+            x.record_stream(torch.cuda.current_stream(dev))
+    return t_near, which, cam_spheres
+
+
+def clear_robot(state: torch.Tensor, state_begin, volumes, views, view_range, depth: torch.Tensor, near: float, t_near: torch.Tensor,
+                cam_spheres: torch.Tensor, tol: float, cull: bool = True, h_cam_spheres=None) -> torch.Tensor:
+    """The arm taken out of the states of M volumes, IN PLACE, in ONE launch (omgx_clear_robot; robot_filter.clear_states is the
+    specification: the same bytes): a node inside a sphere of one of its volume's views becomes FREE, an UNKNOWN node between the
+    camera and the arm too.  state, state_begin, volumes, views, view_range, depth and near as carve_views takes them (depth:
+    the images BEFORE filter_depth); t_near [V,H,W] and cam_spheres [V,N,4]: render_spheres' for the same views.  h_cam_spheres:
+    cam_spheres on the host, if the caller has them; otherwise they are downloaded once for the checks.  cull=False stages every
+    sphere for every run of nodes: the same bytes."""
+    batch, h_views, h_range = _carve_arguments(volumes, views, view_range, depth, 0.0, near, state_begin)
+    if not np.isfinite(float(tol)):
+        raise _lib.OmgHipError("near and tol must be finite")
+    _need(depth, torch.float64, "depth")
+    dev, vp = depth.device, C.c_void_p
+    (V, H, W), M = (int(d) for d in depth.shape), batch.M
+    _need(t_near, torch.float64, "t_near")
+    if t_near.device != dev or tuple(t_near.shape) != (V, H, W):
+        raise _lib.OmgHipError(f"t_near must be {[V, H, W]} on {dev}, got {tuple(t_near.shape)} on {t_near.device}")
+    _need(cam_spheres, torch.float64, "cam_spheres")
+    if cam_spheres.device != dev or cam_spheres.dim() != 3 or cam_spheres.shape[0] != V or cam_spheres.shape[2] != 4:
+        raise _lib.OmgHipError(f"cam_spheres must be [{V},N,4] on {dev}, got {tuple(cam_spheres.shape)} on {cam_spheres.device}")
+    N = int(cam_spheres.shape[1])
+    h_sph = np.ascontiguousarray(cam_spheres.cpu().numpy() if h_cam_spheres is None else h_cam_spheres, np.float64)
+    if h_sph.shape != (V, N, 4) or not np.isfinite(h_sph).all() or (h_sph[:, :, 3] < 0).any():
+        raise _lib.OmgHipError("a sphere is not finite or has a negative radius")
+    _need(state, torch.uint8, "state")
+    if state.device != dev:
+        raise _lib.OmgHipError(f"state must be on {dev}, got {state.device}")
+    with torch.cuda.device(dev):
+        d_views, d_range = _upload(h_views, dev), _upload(h_range, dev)
+        check(_lib.lib().omgx_clear_robot(*batch.on(dev).volume_args(), _ptr(d_views) if V else None, vp(h_views.ctypes.data) if V else None, V,
+                                          _ptr(d_range) if M else None, vp(h_range.ctypes.data) if M else None, *batch.begin_args(),
+                                          _ptr(depth) if V else None, _ptr(t_near) if V else None, H, W, _ptr(cam_spheres) if V and N else None,
+                                          vp(h_sph.ctypes.data) if V and N else None, N, float(near), float(tol), int(bool(cull)), _ptr(state),
+                                          int(state.numel()), _stream()), "omgx_clear_robot")
+        batch.release(d_views, d_range)
+    return state
+
+
+class RobotView:
+    """What the arm looks like to V cameras (camera.Observation.robot_view): t_near [V,H,W] float64 and sphere [V,H,W] int32
+    (render_spheres), cam_spheres [V,N,4] on the device and on the host, tol, and mask = explained(depth, t_near, tol): the
+    pixels that show the arm, or what the arm hides.  As the `robot` of fuse_obstacles, integrate_obstacles and segment_obstacles
+    its images belong to the call's views, one by one (take gathers them)."""
+
+    def __init__(self, t_near, sphere, cam_spheres, tol: float, mask=None, h_cam_spheres=None):
+        if not np.isfinite(float(tol)):
+            raise _lib.OmgHipError("near and tol must be finite")
+        self.t_near, self.sphere, self.cam_spheres, self.tol, self.mask = t_near, sphere, cam_spheres, float(tol), mask
+        self.h_cam_spheres = np.ascontiguousarray(cam_spheres.cpu().numpy()) if h_cam_spheres is None else h_cam_spheres
+
+    def explained(self, depth: torch.Tensor) -> torch.Tensor:
+        """robot_filter.explained on the device, elementwise: t_near < inf and depth >= t_near - tol."""
+        if depth.shape != self.t_near.shape or depth.device != self.t_near.device:
+            raise _lib.OmgHipError(f"depth must be {list(self.t_near.shape)} on {self.t_near.device}, as the images of the arm")
+        return (self.t_near < float("inf")) & (depth >= self.t_near - self.tol)
+
+    def filter_depth(self, depth: torch.Tensor) -> torch.Tensor:
+        """A new tensor: depth with the explained pixels set to 0.0, no information (robot_filter.filter_depth)."""
+        return torch.where(self.explained(depth), torch.zeros_like(depth), depth).contiguous()
+
+    def take(self, index) -> "RobotView":
+        """The view whose image k is this one's image index[k]: a gather on the device."""
+        index = np.asarray(index, np.int64).reshape(-1)
+        at = torch.from_numpy(index.copy()).to(self.t_near.device)
+        return RobotView(self.t_near[at].contiguous(), self.sphere[at].contiguous(), self.cam_spheres[at].contiguous(), self.tol,
+                         None if self.mask is None else self.mask[at].contiguous(), np.ascontiguousarray(self.h_cam_spheres[index]))
+
+    def filtered(self, obs):
+        """A new camera.Observation whose t is 0.0 and whose inst is -1 on the mask."""
+        from . import camera as _cam
+        mask = self.explained(obs.t)
+        return _cam.Observation(obs.batch, torch.where(mask, torch.zeros_like(obs.t), obs.t).contiguous(),
+                                torch.where(mask, torch.full_like(obs.inst, -1), obs.inst).contiguous(), obs.face, obs.normals)
+
+
+def _robot_step(robot: "RobotView | None", depth: torch.Tensor, views, view_range, near: float):
+    """The self-filter's two halves for a call that turns depth views into states (fuse_obstacles, integrate_obstacles,
+    segment_obstacles) -> (the depth to carve or integrate, clear).  Without a robot: the depth as it is and None, so that the
+    call launches what it launched before.  With one: the explained pixels set to 0.0, and clear(state, state_begin, volumes),
+    which runs clear_robot on the state bytes, with the images before the filter, before anything reads them."""
+    if robot is None:
+        return depth, None
+    if not isinstance(robot, RobotView):
+        raise _lib.OmgHipError("robot must be a RobotView (camera.Observation.robot_view)")
+    _need(depth, torch.float64, "depth")
+    filtered = robot.filter_depth(depth)
+    # (what clear_robot would refuse is refused here, before the caller takes a slot of the pool)
+    V, s, h = int(depth.shape[0]), robot.cam_spheres, robot.h_cam_spheres
+    _need(robot.t_near, torch.float64, "robot.t_near"), _need(s, torch.float64, "robot.cam_spheres")
+    if s.device != depth.device or s.dim() != 3 or s.shape[0] != V or s.shape[2] != 4 or tuple(h.shape) != tuple(s.shape):
+        raise _lib.OmgHipError(f"robot.cam_spheres must be [{V},N,4] on {depth.device} and on the host, got {tuple(s.shape)} on {s.device}")
+    if not np.isfinite(h).all() or (h[:, :, 3] < 0).any() or not np.isfinite(float(near)):
+        raise _lib.OmgHipError("a sphere is not finite or has a negative radius, or near is not finite")
+
+    def clear(state, state_begin, volumes):
+        return clear_robot(state, state_begin, volumes, views, view_range, depth, near, robot.t_near, robot.cam_spheres, robot.tol,
+                           h_cam_spheres=robot.h_cam_spheres)
+    return filtered, clear

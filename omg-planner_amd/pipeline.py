@@ -132,11 +132,12 @@ def plan_volumes(model, scenes, starts, cfg, level: float = 0.0, n_rays: int = 5
 
 
 def plan_observed(model, scenes, obs, obstacles, layouts, band: float, near: float, reach: float, seeds, min_nodes: int, starts, cfg,
-                  connectivity: int = 6, margin=None, free_mask=None, device="cuda:0", **plan_kwargs):
+                  connectivity: int = 6, margin=None, free_mask=None, device="cuda:0", robot=None, **plan_kwargs):
     """plan_volumes from depth images alone: no instance labels, no target volume from a file.  obs: a camera.Observation of the
     S scenes (only its depth images and cameras are used); obstacles [S]: the object of each scene that stands for everything
     observed, at the pose of the layout's frame, as the target (scene.target_idx) should be; layouts, band, near, reach, seeds,
-    min_nodes, connectivity, margin, free_mask: camera.Observation.segment_obstacles'.  A table built from the scenes is segmented
+    min_nodes, connectivity, margin, free_mask, robot: camera.Observation.segment_obstacles' (robot: the arm in the images,
+    camera.Observation.robot_view's result).  A table built from the scenes is segmented
     on the device, the two small volumes of every scene are downloaded into the scenes' SdfGrids (the target's crop, the layout
     without the target), then plan_volumes unchanged (plan_kwargs: its other arguments).
     -> (GraspPlans, grasp poses, meshes, the chosen records [S,8])."""
@@ -149,7 +150,8 @@ def plan_observed(model, scenes, obs, obstacles, layouts, band: float, near: flo
     grow = 2 * (max(_fu.obstacle_radius(reach, float(delta)) for _, delta, _ in layouts) + 1 if margin is None else int(margin))
     reserve = sum(int(np.prod(dims)) + int(np.prod(np.asarray(dims, np.int64) + grow)) for _, _, dims in layouts)
     table = ops.DeviceScenes.from_scenes(scenes, cfg.layer_kwargs(), device=dev, share_grids=False, reserve_voxels=reserve)
-    radius, records, _ = obs.segment_obstacles(table, tp, op, layouts, band, near, reach, seeds, min_nodes, connectivity, margin, free_mask)
+    radius, records, _ = obs.segment_obstacles(table, tp, op, layouts, band, near, reach, seeds, min_nodes, connectivity, margin, free_mask,
+                                                robot=robot)
     host = table.sync_host()
     for s, (origin, delta, dims) in enumerate(layouts):
         crop = _sg.crop_layout((origin, delta), records[s], radius + 1 if margin is None else int(margin))
@@ -163,20 +165,21 @@ def plan_observed(model, scenes, obs, obstacles, layouts, band: float, near: flo
 
 def plan_on_unknown_support(model, scenes, obs, obstacles, supports, layouts, support_layouts, band: float, near: float, reach: float, seeds,
                             min_nodes: int, starts, cfg, triples, tol: float, up_world=None, cos_min: float = -1.0, refine: int = 2,
-                            connectivity: int = 6, margin=None, device="cuda:0", **plan_kwargs):
+                            connectivity: int = 6, margin=None, device="cuda:0", robot=None, **plan_kwargs):
     """plan_observed on a support nobody has modelled: from depth images and seed points alone.  The support's plane is fitted to
     every scene's depth image (camera.Observation.fit_supports: triples, tol, up_world, cos_min, refine), its pixels are the
     free_mask that plan_observed takes in place of explained_mask's rendering of a known table, and its half-space becomes the
     volume of supports[s], an object of scene s at the pose of the layout's frame (support_layouts: one (origin [3], delta,
     dims [3]) per scene, voxel centres, in that frame), so that the masked-out support is still an obstacle: the volume is
     written on the device (ops.DeviceScenes.plane_obstacles) and downloaded into the object's SdfGrid as plan_observed downloads
-    its two.  Then plan_observed, unchanged.  A scene without a plane is refused.
+    its two.  Then plan_observed, unchanged.  A scene without a plane is refused.  robot: the
+    arm in the images (camera.Observation.robot_view's result): its pixels take no part in the fit, and plan_observed gets it.
     -> (GraspPlans, grasp poses, meshes, the chosen records [S,8], the ops.PlaneFit)."""
     from . import scenes as _sc
     dev = torch.device(device)
     S = len(scenes)
     sp = [(s, int(o)) for s, o in enumerate(supports)]
-    fit, mask = obs.fit_supports(triples, tol, up_world, cos_min, refine)
+    fit, mask = obs.fit_supports(triples, tol, up_world, cos_min, refine, skip=None if robot is None else robot.mask)
     table = ops.DeviceScenes.from_scenes(scenes, cfg.layer_kwargs(), device=dev, share_grids=False,
                                          reserve_voxels=sum(int(np.prod(dims)) for _, _, dims in support_layouts))
     table.plane_obstacles(sp, obs.support_planes(table, sp, fit), support_layouts)
@@ -185,5 +188,5 @@ def plan_on_unknown_support(model, scenes, obs, obstacles, supports, layouts, su
         off, n = int(host[table._index(s, o)]["grid_offset"]), tuple(int(d) for d in dims)
         scenes[s].objects[o].sdf = _sc.SdfGrid(table.pool[off: off + int(np.prod(n))].view(n).cpu().numpy(), np.asarray(origin, np.float64), float(delta))
     plans, sets, meshes, records = plan_observed(model, scenes, obs, obstacles, layouts, band, near, reach, seeds, min_nodes, starts, cfg, connectivity,
-                                                 margin, free_mask=mask, device=device, **plan_kwargs)
+                                                 margin, free_mask=mask, device=device, robot=robot, **plan_kwargs)
     return plans, sets, meshes, records, fit
