@@ -33,6 +33,30 @@ def camera_rows(intrinsics, cam_from_world) -> np.ndarray:
     return np.concatenate([k, w[:3].ravel()])
 
 
+def check_camera_rows(rows, S=None) -> np.ndarray:
+    """`cameras` [S,16] (camera_rows) as float64, or ValueError: a wrong shape, a field that is not finite, a focal length of zero."""
+    rows = np.asarray(rows, np.float64)
+    if rows.ndim != 2 or rows.shape[1] != 16 or (S is not None and len(rows) != S):
+        raise ValueError(f"cameras must be [{'S' if S is None else S},16], got {rows.shape}")
+    if not np.isfinite(rows).all() or (rows[:, :2] == 0).any():
+        raise ValueError("a camera is not finite or has a focal length of zero")
+    return rows
+
+
+def camera_records(rows, inst_begin=None) -> np.ndarray:
+    """CAMERA_DTYPE records of `cameras` [S,16] (camera_rows).  inst_begin [S+1]: scene s owns instances [inst_begin[s],
+    inst_begin[s+1]); without it the instance range of every record stays (0, 0)."""
+    rows = np.asarray(rows, np.float64).reshape(-1, 16)
+    rec = np.zeros(len(rows), CAMERA_DTYPE)
+    for k, name in enumerate(("fx", "fy", "cx", "cy")):
+        rec[name] = rows[:, k]
+    rec["world_from_cam"] = rows[:, 4:]
+    if inst_begin is not None:
+        begin = np.asarray(inst_begin, np.int64).reshape(-1)
+        rec["inst_begin"], rec["inst_count"] = begin[:-1], np.diff(begin)
+    return rec
+
+
 def instance_records(meshes, mesh_idx, poses, labels, cam_from_world) -> np.ndarray:
     """INSTANCE_DTYPE records of one scene's instances as one camera sees them.  meshes: the pool [(verts, faces)]; mesh_idx,
     poses [I,4,4] (object -> world), labels [I] (>= 0): one per instance; cam_from_world [4,4].

@@ -15,12 +15,8 @@
 #pragma clang fp contract(off)
 
 #define CAM_BLOCK OMGX_CAMERA_PIXELS_PER_WORKGROUP
-#define CAM_TILE 16
-static_assert(CAM_BLOCK == CAM_TILE * CAM_TILE && CAM_BLOCK == OMGX_MESH_FACE_TILE, "mesh_stage_faces moves one face per thread");
+static_assert(CAM_BLOCK == IMAGE_TILE * IMAGE_TILE && CAM_BLOCK == OMGX_MESH_FACE_TILE, "mesh_stage_faces moves one face per thread");
 static_assert(sizeof(omgx_camera) == 136 && sizeof(omgx_instance) == 136, "records as include/omg_hip.h documents them");
-// Tiles of one image (gridDim.x; gridDim.x * 256 threads must stay below 2^32) and scenes of one launch (gridDim.y).
-#define CAM_MAX_TILES (1 << 23)
-#define CAM_MAX_SCENES 65535
 
 namespace {
 
@@ -34,10 +30,11 @@ __global__ __launch_bounds__(CAM_BLOCK) void k_render_depth(const double* __rest
     __shared__ int wave_any[2][CAM_BLOCK / 64];
     const omgx_camera* __restrict__ cam = cameras + blockIdx.y;  // uniform: scalar loads
     const int tid = threadIdx.x;
-    const int pr = (int)(blockIdx.x / tiles_x) * CAM_TILE + (tid >> 4), pc = (int)(blockIdx.x % tiles_x) * CAM_TILE + (tid & 15);
+    int pr, pc;
+    image_row_pixel(blockIdx.x, tiles_x, tid, &pr, &pc);
     // lanes outside the image redo the last valid pixel of their row or column and store nothing
     double dx, dy;
-    camera_pixel_dir(min(pr, H - 1), min(pc, W - 1), cam->fx, cam->fy, cam->cx, cam->cy, dx, dy);
+    image_pixel_dir(min(pr, H - 1), min(pc, W - 1), cam->fx, cam->fy, cam->cx, cam->cy, dx, dy);
 
     double best = __builtin_inf();
     int32_t inst = -1, face = -1;
@@ -163,16 +160,10 @@ __global__ __launch_bounds__(CAM_BLOCK) void k_pixel_gather(const omgx_instance*
     const int64_t row = (int64_t)offsets[(int64_t)blockIdx.y * gridDim.x + blockIdx.x] + before + __popcll(mask & ((1ull << lane) - 1ull));
     if (keep && row >= 0 && row < cap) {
         double dx, dy, w[3];
-        camera_pixel_dir((int)(p / W), (int)(p % W), cam->fx, cam->fy, cam->cx, cam->cy, dx, dy);
+        image_pixel_dir((int)(p / W), (int)(p % W), cam->fx, cam->fy, cam->cx, cam->cy, dx, dy);
         camera_world_point(cam->world_from_cam, t_img[at], dx, dy, w);
         points[row * 3] = w[0], points[row * 3 + 1] = w[1], points[row * 3 + 2] = w[2];
     }
-}
-
-bool all_finite(const double* x, int n) {
-    for (int i = 0; i < n; ++i)
-        if (!std::isfinite(x[i])) return false;
-    return true;
 }
 
 // The host copies of the records and the image size -> OMGX_OK or OMGX_ERR_INVALID.  num_meshes < 0: the mesh indices are not checked (the cloud kernels do not read them).
@@ -182,25 +173,20 @@ int check_records(const omgx_instance* h_instances, int32_t num_instances, const
     if ((num_instances > 0 && !h_instances) || (num_scenes > 0 && !h_cameras)) return OMGX_ERR_INVALID;
     for (int32_t i = 0; i < num_instances; ++i) {
         const omgx_instance& in = h_instances[i];
-        if (!all_finite(in.m, 12) || !all_finite(in.centre, 3) || !std::isfinite(in.q) || in.label < 0 || in.mesh < 0) return OMGX_ERR_INVALID;
+        if (!image_all_finite(in.m, 12) || !image_all_finite(in.centre, 3) || !std::isfinite(in.q) || in.label < 0 || in.mesh < 0) return OMGX_ERR_INVALID;
         if (num_meshes >= 0 && in.mesh >= num_meshes) return OMGX_ERR_INVALID;
     }
     for (int32_t s = 0; s < num_scenes; ++s) {
         const omgx_camera& c = h_cameras[s];
-        if (!std::isfinite(c.fx) || !std::isfinite(c.fy) || c.fx == 0.0 || c.fy == 0.0) return OMGX_ERR_INVALID;
-        if (!std::isfinite(c.cx) || !std::isfinite(c.cy) || !all_finite(c.world_from_cam, 12)) return OMGX_ERR_INVALID;
+        if (image_check_camera(c) != OMGX_OK) return OMGX_ERR_INVALID;
         if (c.inst_begin < 0 || c.inst_count < 0 || (int64_t)c.inst_begin + c.inst_count > num_instances) return OMGX_ERR_INVALID;
     }
     return OMGX_OK;
 }
 
-// What the grids and the index types admit (sizes already known to be valid) -> OMGX_OK or OMGX_ERR_UNSUPPORTED.  Scenes are
-// gridDim.y of every kernel.  render: the tile index is k_render_depth's gridDim.x.  Otherwise (the cloud kernels, whose gridDim.x
-// is a group of 256 pixels): scene_begin and the offsets are int32.
-int check_limits(int32_t num_scenes, int32_t H, int32_t W, bool render) {
-    if (num_scenes > CAM_MAX_SCENES) return OMGX_ERR_UNSUPPORTED;
-    if (render) return (int64_t)((H + CAM_TILE - 1) / CAM_TILE) * ((W + CAM_TILE - 1) / CAM_TILE) > CAM_MAX_TILES ? OMGX_ERR_UNSUPPORTED : OMGX_OK;
-    return (int64_t)num_scenes * H * W > 0x7fffffffll ? OMGX_ERR_UNSUPPORTED : OMGX_OK;
+// What the cloud kernels admit (valid sizes) -> OMGX_OK or OMGX_ERR_UNSUPPORTED: scenes are gridDim.y, the offsets are int32.
+int check_cloud_limits(int32_t num_scenes, int32_t H, int32_t W) {
+    return num_scenes > IMAGE_MAX_VIEWS || !image_pixels_fit(num_scenes, H, W) ? OMGX_ERR_UNSUPPORTED : OMGX_OK;
 }
 
 int64_t pixel_groups(int32_t H, int32_t W) { return ((int64_t)H * W + CAM_BLOCK - 1) / CAM_BLOCK; }
@@ -219,11 +205,12 @@ extern "C" int omgx_render_depth(const double* verts, const int32_t* faces, cons
     for (int32_t m = 0; m < num_meshes; ++m)
         if (mesh_check_ranges(h_meshes[m]) != OMGX_OK) return OMGX_ERR_INVALID;  // the volume fields are not read here
     int status = check_records(h_instances, num_instances, h_cameras, num_scenes, H, W, num_meshes);
-    if (status == OMGX_OK) status = check_limits(num_scenes, H, W, true);
+    if (status == OMGX_OK) status = image_check_grid(num_scenes, H, W);
     if (status != OMGX_OK) return status;
     if (num_scenes == 0) return OMGX_OK;
-    const int tiles_x = (W + CAM_TILE - 1) / CAM_TILE, tiles_y = (H + CAM_TILE - 1) / CAM_TILE;
-    hipLaunchKernelGGL(k_render_depth, dim3((unsigned)(tiles_x * tiles_y), (unsigned)num_scenes), dim3(CAM_BLOCK), 0, (hipStream_t)stream, verts,
+    int tiles_x;
+    const int64_t tiles = image_tile_grid(H, W, &tiles_x);
+    hipLaunchKernelGGL(k_render_depth, dim3((unsigned)tiles, (unsigned)num_scenes), dim3(CAM_BLOCK), 0, (hipStream_t)stream, verts,
                        faces, meshes, instances, cameras, (int)H, (int)W, tiles_x, (int)(cull != 0), t_min, -tol, 1.0 + tol, t_out, inst_out,
                        face_out);
     OMGX_CHECK_LAUNCH("k_render_depth");
@@ -242,7 +229,7 @@ extern "C" int omgx_pixel_count(const omgx_instance* instances, const omgx_insta
     if (num_instances > 0 && !instances) return OMGX_ERR_INVALID;
     if (num_scenes > 0 && (!cameras || !inst_img || !workspace)) return OMGX_ERR_INVALID;
     int status = check_records(h_instances, num_instances, h_cameras, num_scenes, H, W, -1);
-    if (status == OMGX_OK) status = check_limits(num_scenes, H, W, false);
+    if (status == OMGX_OK) status = check_cloud_limits(num_scenes, H, W);
     if (status != OMGX_OK) return status;
     const int64_t groups = pixel_groups(H, W);
     if (num_scenes > 0) {
@@ -264,7 +251,7 @@ extern "C" int omgx_pixel_gather(const omgx_instance* instances, int32_t num_ins
     if (num_instances > 0 && !instances) return OMGX_ERR_INVALID;
     if (num_scenes > 0 && (!cameras || !t_img || !inst_img || !workspace)) return OMGX_ERR_INVALID;
     if (cap > 0 && !points) return OMGX_ERR_INVALID;
-    if (check_limits(num_scenes, H, W, false) != OMGX_OK) return OMGX_ERR_UNSUPPORTED;
+    if (check_cloud_limits(num_scenes, H, W) != OMGX_OK) return OMGX_ERR_UNSUPPORTED;
     if (num_scenes == 0 || cap == 0) return OMGX_OK;
     hipLaunchKernelGGL(k_pixel_gather, dim3((unsigned)pixel_groups(H, W), (unsigned)num_scenes), dim3(CAM_BLOCK), 0, (hipStream_t)stream, instances,
                        cameras, (int64_t)H * W, (int)W, t_img, inst_img, cls, (const int32_t*)workspace, points, cap);

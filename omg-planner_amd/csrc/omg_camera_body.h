@@ -7,14 +7,9 @@
 #include <cstdint>
 
 #include "omg_grasp_body.h"
+#include "omg_image_body.h"  // the ray of a pixel: image_pixel_dir
 
 #pragma clang fp contract(off)
-
-// The ray of pixel (row r, column c): direction (dx, dy, 1) from the camera origin.
-GRASP_HD void camera_pixel_dir(int r, int c, double fx, double fy, double cx, double cy, double& dx, double& dy) {
-    dx = ((double)c - cx) / fx;
-    dy = ((double)r - cy) / fy;
-}
 
 // Can the ray meet the instance's bounding ball (centre, q = |centre|^2 - r2, camera frame)?  q <= 0: the camera is inside it.
 GRASP_HD bool camera_instance_active(const double* centre, double q, double dx, double dy) {

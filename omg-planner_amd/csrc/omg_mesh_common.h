@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "omg_host.h"
+#include "omg_image_body.h"   // the checks of camera rows and of the pixel count
 #include "omg_volume_body.h"  // a workgroup's volume and a thread's node of it, on the device
 
 // Faces of a mesh staged in LDS at a time (omgx_mesh_sdf_tile()), 9 doubles each: a, b, c.
@@ -117,11 +118,10 @@ static inline bool mesh_pool_ranges_overlap(const omgx_mesh* h_volumes, int32_t 
 // count) -> OMGX_ERR_INVALID for a field that is not finite, a focal length of zero or a range outside [0, V]; then
 // OMGX_ERR_UNSUPPORTED for V * H * W > 2^31 - 1, which the caller reports after its other checks; OMGX_OK.  (V > 0: H, W >= 1)
 static inline int mesh_check_views(const double* h_views, int32_t V, int32_t H, int32_t W, const int32_t* h_view_range, int32_t M) {
-    for (int64_t x = 0; x < (int64_t)V * 16; ++x)
-        if (!std::isfinite(h_views[x]) || (x % 16 < 2 && h_views[x] == 0.0)) return OMGX_ERR_INVALID;
+    if (image_check_rows(h_views, V, 16) != OMGX_OK) return OMGX_ERR_INVALID;
     for (int32_t m = 0; m < M; ++m) {
         const int64_t first = h_view_range[2 * m], count = h_view_range[2 * m + 1];
         if (first < 0 || count < 0 || first + count > V) return OMGX_ERR_INVALID;
     }
-    return V > 0 && (int64_t)V * H > 0x7fffffffll / W ? OMGX_ERR_UNSUPPORTED : OMGX_OK;
+    return image_pixels_fit(V, H, W) ? OMGX_OK : OMGX_ERR_UNSUPPORTED;
 }

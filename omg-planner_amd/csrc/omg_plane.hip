@@ -223,9 +223,8 @@ int check_images(const double* h_intrinsics, int32_t V, int32_t H, int32_t W, do
     if (V < 0 || !std::isfinite(tol) || tol < 0.0) return OMGX_ERR_INVALID;
     if (V == 0) return OMGX_OK;
     if (!h_intrinsics || H < 1 || W < 1) return OMGX_ERR_INVALID;
-    for (int64_t x = 0; x < (int64_t)V * 4; ++x)
-        if (!std::isfinite(h_intrinsics[x]) || (x % 4 < 2 && h_intrinsics[x] == 0.0)) return OMGX_ERR_INVALID;
-    return (int64_t)V * H > 0x7fffffffll / W ? OMGX_ERR_UNSUPPORTED : OMGX_OK;
+    if (image_check_rows(h_intrinsics, V, 4) != OMGX_OK) return OMGX_ERR_INVALID;
+    return image_pixels_fit(V, H, W) ? OMGX_OK : OMGX_ERR_UNSUPPORTED;
 }
 
 int64_t chunks_of(int32_t H, int32_t W) { return ((int64_t)H * W + PL_CHUNK - 1) / PL_CHUNK; }
@@ -263,7 +262,7 @@ extern "C" int omgx_plane_ransac(const double* intrinsics, const double* h_intri
 extern "C" int64_t omgx_plane_workspace_bytes(int32_t num_views, int32_t H, int32_t W) {
     if (num_views < 0 || (num_views > 0 && (H < 1 || W < 1))) return OMGX_ERR_INVALID;
     if (num_views == 0) return 0;
-    if ((int64_t)num_views * H > 0x7fffffffll / W) return OMGX_ERR_UNSUPPORTED;
+    if (!image_pixels_fit(num_views, H, W)) return OMGX_ERR_UNSUPPORTED;
     return (int64_t)num_views * chunks_of(H, W) * PL_PARTIALS * (int64_t)sizeof(double);
 }
 

@@ -18,15 +18,11 @@
 #pragma clang fp contract(off)
 
 #define RF_BLOCK 256
-#define RF_TILE 16
-#define RF_WAVE_TILE 8
 #define RF_CHUNK OMGX_ROBOT_SPHERE_CHUNK
 static_assert(RF_BLOCK == OMGX_CAMERA_PIXELS_PER_WORKGROUP && RF_BLOCK == OMGX_FUSION_NODES_PER_WORKGROUP, "a pixel or a node per thread");
 static_assert(RF_CHUNK == RF_BLOCK, "a sphere of a chunk per thread");
 static_assert(OMGX_FUSION_FREE == ROBOT_FREE && OMGX_FUSION_UNKNOWN == ROBOT_UNKNOWN, "states");
 static_assert(sizeof(omgx_camera) == 136, "records as include/omg_hip.h documents them");
-#define RF_MAX_TILES (1 << 23)
-#define RF_MAX_VIEWS 65535
 
 namespace {
 
@@ -40,12 +36,12 @@ __global__ __launch_bounds__(RF_BLOCK) void k_render_spheres(const double* __res
     const omgx_camera* __restrict__ cam = cameras + blockIdx.y;  // uniform: scalar loads
     // (the entry point has checked the host copy; clamped once more so that no index can read outside the poses)
     const int cfg = min(max(config_of_view[blockIdx.y], 0), num_configs - 1);
-    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-    const int pr = (int)(blockIdx.x / tiles_x) * RF_TILE + (wave >> 1) * RF_WAVE_TILE + (lane >> 3);
-    const int pc = (int)(blockIdx.x % tiles_x) * RF_TILE + (wave & 1) * RF_WAVE_TILE + (lane & 7);
+    const int tid = threadIdx.x;
+    int pr, pc;
+    image_wave_pixel(blockIdx.x, tiles_x, tid, &pr, &pc);
     // lanes outside the image redo the last valid pixel of their row or column and store nothing
-    const double dx = ((double)min(pc, W - 1) - cam->cx) / cam->fx;
-    const double dy = ((double)min(pr, H - 1) - cam->cy) / cam->fy;
+    double dx, dy;
+    image_pixel_dir(min(pr, H - 1), min(pc, W - 1), cam->fx, cam->fy, cam->cx, cam->cy, dx, dy);
     const double dd = (dx * dx + dy * dy) + 1.0;
 
     double best = __builtin_inf();
@@ -139,15 +135,9 @@ __global__ __launch_bounds__(RF_BLOCK) void k_clear_robot(const omgx_mesh* __res
     if (n.live) mine[n.id] = robot_new_state(old, inside, front);
 }
 
-bool all_finite(const double* x, int64_t count) {
-    for (int64_t k = 0; k < count; ++k)
-        if (!std::isfinite(x[k])) return false;
-    return true;
-}
-
 // [count][4] spheres on the host: finite, radius >= 0.
 bool spheres_valid(const double* h, int64_t count) {
-    if (!all_finite(h, count * 4)) return false;
+    if (!image_all_finite(h, count * 4)) return false;
     for (int64_t k = 0; k < count; ++k)
         if (h[k * 4 + 3] < 0.0) return false;
     return true;
@@ -167,20 +157,17 @@ extern "C" int omgx_render_spheres(const double* local, const double* h_local, c
     if (C > 0 && (!link_poses || !h_link_poses)) return OMGX_ERR_INVALID;
     if (V > 0 && (!cameras || !h_cameras || !config_of_view || !h_config_of_view || !t_near || !sphere || H < 1 || W < 1)) return OMGX_ERR_INVALID;
     if (V > 0 && N > 0 && !cam_spheres) return OMGX_ERR_INVALID;
-    if (!spheres_valid(h_local, N) || !all_finite(h_link_poses, (int64_t)C * OMGX_NUM_LINKS * 16)) return OMGX_ERR_INVALID;
+    if (!spheres_valid(h_local, N) || !image_all_finite(h_link_poses, (int64_t)C * OMGX_NUM_LINKS * 16)) return OMGX_ERR_INVALID;
     for (int32_t n = 0; n < N; ++n)
         if (h_link[n] < 0 || h_link[n] >= OMGX_NUM_LINKS) return OMGX_ERR_INVALID;
     for (int32_t v = 0; v < V; ++v) {
-        const omgx_camera& c = h_cameras[v];
-        if (!std::isfinite(c.fx) || !std::isfinite(c.fy) || c.fx == 0.0 || c.fy == 0.0 || !std::isfinite(c.cx) || !std::isfinite(c.cy) ||
-            !all_finite(c.world_from_cam, 12))
-            return OMGX_ERR_INVALID;
-        if (h_config_of_view[v] < 0 || h_config_of_view[v] >= C) return OMGX_ERR_INVALID;
+        if (image_check_camera(h_cameras[v]) != OMGX_OK || h_config_of_view[v] < 0 || h_config_of_view[v] >= C) return OMGX_ERR_INVALID;
     }
     if (V == 0) return OMGX_OK;
-    const int tiles_x = (W + RF_TILE - 1) / RF_TILE, tiles_y = (H + RF_TILE - 1) / RF_TILE;
-    if (N > OMGX_ROBOT_MAX_SPHERES || V > RF_MAX_VIEWS || (int64_t)tiles_x * tiles_y > RF_MAX_TILES) return OMGX_ERR_UNSUPPORTED;
-    hipLaunchKernelGGL(k_render_spheres, dim3((unsigned)(tiles_x * tiles_y), (unsigned)V), dim3(RF_BLOCK), 0, (hipStream_t)stream, local, link,
+    if (N > OMGX_ROBOT_MAX_SPHERES || image_check_grid(V, H, W) != OMGX_OK) return OMGX_ERR_UNSUPPORTED;
+    int tiles_x;
+    const int64_t tiles = image_tile_grid(H, W, &tiles_x);
+    hipLaunchKernelGGL(k_render_spheres, dim3((unsigned)tiles, (unsigned)V), dim3(RF_BLOCK), 0, (hipStream_t)stream, local, link,
                        (int)N, link_poses, (int)C, cameras, config_of_view, (int)H, (int)W, tiles_x, pad, t_min, (int)cull, cam_spheres, t_near,
                        sphere);
     OMGX_CHECK_LAUNCH("k_render_spheres");

@@ -10,18 +10,14 @@
 // arithmetic is omg_volume_camera_body.h: the bits of volume_camera.render_volumes (omg-planner_amd/volume_camera.py).  Plain
 // loads and stores only; every pixel of every image is written once.
 #include "omg_host.h"
+#include "omg_image_body.h"
 #include "omg_volume_camera_body.h"
 
 #pragma clang fp contract(off)
 
 #define VCAM_BLOCK OMGX_CAMERA_PIXELS_PER_WORKGROUP
-#define VCAM_TILE 16
-#define VCAM_WAVE_TILE 8
-static_assert(VCAM_BLOCK == VCAM_TILE * VCAM_TILE && VCAM_WAVE_TILE * VCAM_WAVE_TILE == 64, "a wave is an 8 x 8 block of a 16 x 16 tile");
+static_assert(VCAM_BLOCK == IMAGE_TILE * IMAGE_TILE, "a pixel of a tile per thread");
 static_assert(sizeof(omgx_object) == 184, "records as include/omg_hip.h documents them");
-// Tiles of one image (gridDim.x) and scenes of one launch (gridDim.y): the limits of section 14.
-#define VCAM_MAX_TILES (1 << 23)
-#define VCAM_MAX_SCENES 65535
 
 namespace {
 
@@ -33,12 +29,11 @@ __global__ __launch_bounds__(VCAM_BLOCK) void k_render_volumes(const omgx_object
                                                                double* __restrict__ t_out, int32_t* __restrict__ inst_out,
                                                                double* __restrict__ normal_out, int32_t* __restrict__ steps_out) {
     const double* __restrict__ cam = cameras + (int64_t)blockIdx.y * 16;  // uniform: scalar loads
-    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-    const int pr = (int)(blockIdx.x / tiles_x) * VCAM_TILE + (wave >> 1) * VCAM_WAVE_TILE + (lane >> 3);
-    const int pc = (int)(blockIdx.x % tiles_x) * VCAM_TILE + (wave & 1) * VCAM_WAVE_TILE + (lane & 7);
+    int pr, pc;
+    image_wave_pixel(blockIdx.x, tiles_x, threadIdx.x, &pr, &pc);
     // lanes outside the image redo the last valid pixel of their row or column and store nothing
-    const double dx = ((double)min(pc, W - 1) - cam[2]) / cam[0];
-    const double dy = ((double)min(pr, H - 1) - cam[3]) / cam[1];
+    double dx, dy;
+    image_pixel_dir(min(pr, H - 1), min(pc, W - 1), cam[0], cam[1], cam[2], cam[3], dx, dy);
 
     double best = __builtin_inf(), n0 = 0.0, n1 = 0.0, n2 = 0.0;
     int32_t inst = -1, samples = 0;
@@ -99,16 +94,16 @@ extern "C" int omgx_render_volumes(const omgx_object* objects, const omgx_object
     if (h_scene_begin[0] < 0 || h_scene_begin[S] > num_objects) return OMGX_ERR_INVALID;
     for (int32_t s = 0; s < S; ++s)
         if (h_scene_begin[s + 1] < h_scene_begin[s]) return OMGX_ERR_INVALID;
-    for (int64_t x = 0; x < (int64_t)S * 16; ++x)
-        if (!std::isfinite(h_cameras[x]) || (x % 16 < 2 && h_cameras[x] == 0.0)) return OMGX_ERR_INVALID;
+    if (image_check_rows(h_cameras, S, 16) != OMGX_OK) return OMGX_ERR_INVALID;
     for (int32_t o = h_scene_begin[0]; o < h_scene_begin[S]; ++o) {
         if (h_visible && !h_visible[o]) continue;
         const omgx_object& r = h_objects[o];
         if (!std::isfinite(r.inv_delta) || !(r.inv_delta > 0.0) || !vcam_grid_usable(r.dim, r.grid_offset, pool_elems)) return OMGX_ERR_INVALID;
     }
-    const int tiles_x = (W + VCAM_TILE - 1) / VCAM_TILE, tiles_y = (H + VCAM_TILE - 1) / VCAM_TILE;
-    if (S > VCAM_MAX_SCENES || (int64_t)tiles_x * tiles_y > VCAM_MAX_TILES) return OMGX_ERR_UNSUPPORTED;
-    hipLaunchKernelGGL(k_render_volumes, dim3((unsigned)(tiles_x * tiles_y), (unsigned)S), dim3(VCAM_BLOCK), 0, (hipStream_t)stream, objects,
+    if (image_check_grid(S, H, W) != OMGX_OK) return OMGX_ERR_UNSUPPORTED;
+    int tiles_x;
+    const int64_t tiles = image_tile_grid(H, W, &tiles_x);
+    hipLaunchKernelGGL(k_render_volumes, dim3((unsigned)tiles, (unsigned)S), dim3(VCAM_BLOCK), 0, (hipStream_t)stream, objects,
                        (int)num_objects, scene_begin, pool, pool_elems, cameras, visible, (int)H, (int)W, tiles_x, level, t_min, min_step, relax,
                        (int)max_steps, t_out, inst_out, normal_out, steps_out);
     OMGX_CHECK_LAUNCH("k_render_volumes");

@@ -32,6 +32,23 @@ def _need(t: torch.Tensor, dtype, name: str):
         raise _lib.OmgHipError(f"{name} must be {dtype}, got {t.dtype}")
 
 
+def _tensor(t, name: str, dtype, shape, dev) -> torch.Tensor:
+    """t as it is if it is a contiguous device tensor of `dtype` on `dev` with `shape` (None: a free dimension, or any shape)."""
+    if not isinstance(t, torch.Tensor):
+        raise _lib.OmgHipError(f"{name} must be a tensor")
+    _need(t, dtype, name)
+    shape = (None,) * t.dim() if shape is None else shape
+    if t.device != dev or t.dim() != len(shape) or any(w is not None and n != w for n, w in zip(t.shape, shape)):
+        want = ", ".join("*" if w is None else str(w) for w in shape)
+        raise _lib.OmgHipError(f"{name} must be [{want}] on {dev}, got {tuple(t.shape)} on {t.device}")
+    return t
+
+
+def _nonneg_finite(**named) -> None:
+    if not all(np.isfinite(float(x)) and float(x) >= 0 for x in named.values()):
+        raise _lib.OmgHipError(f"{' and '.join(named)} must be finite and not negative")
+
+
 def _workspace(nbytes: int, device) -> torch.Tensor:
     key = (device, torch.cuda.current_stream().cuda_stream)
     ws = _ws_cache.get(key)
@@ -519,8 +536,7 @@ class DeviceScenes:
             raise _lib.OmgHipError(f"{len(pairs)} pairs need as many layouts, and at least one")
         if len({self._index(int(s), int(o)) for s, o in pairs}) != len(pairs):
             raise _lib.OmgHipError("a (scene, obj) pair is named twice")
-        if not (np.isfinite(float(reach)) and float(reach) >= 0):
-            raise _lib.OmgHipError("reach must be finite and not negative")
+        _nonneg_finite(reach=reach)
         # everything that can be refused is refused here, before grid_slot offers a slot: the radius, the layouts, the views
         _carve_arguments([(origin, delta, "centre", dims) for origin, delta, dims in layouts], views, view_range, depth, band, near, None)
         radius = _fusion_radius(max(_fu.obstacle_radius(reach, float(delta)) for _, delta, _ in layouts))
@@ -556,8 +572,7 @@ class DeviceScenes:
             raise _lib.OmgHipError(f"{len(pairs)} pairs need as many layouts, and at least one")
         if len({self._index(int(s), int(o)) for s, o in pairs}) != len(pairs):
             raise _lib.OmgHipError("a (scene, obj) pair is named twice")
-        if not (np.isfinite(float(reach)) and float(reach) >= 0):
-            raise _lib.OmgHipError("reach must be finite and not negative")
+        _nonneg_finite(reach=reach)
         min_weight = _tsdf_positive("min_weight", min_weight)
         volumes = [(origin, delta, "centre", dims) for origin, delta, dims in layouts]
         _, _, _, _, trunc, wmax = _tsdf_arguments(volumes, views, view_range, depth, trunc, near, weights, wmax, None)
@@ -606,8 +621,7 @@ class DeviceScenes:
             raise _lib.OmgHipError(f"{n} layouts need as many target pairs, obstacle pairs and seeds, and at least one")
         if len({self._index(int(s), int(o)) for s, o in np.concatenate([tp, op])}) != 2 * n:
             raise _lib.OmgHipError("a (scene, obj) pair is named twice")
-        if not (np.isfinite(float(reach)) and float(reach) >= 0):
-            raise _lib.OmgHipError("reach must be finite and not negative")
+        _nonneg_finite(reach=reach)
         if not np.isfinite(seeds).all() or int(min_nodes) < 1 or (margin is not None and int(margin) < 0):
             raise _lib.OmgHipError("seeds must be finite, min_nodes at least 1 and margin not negative")
         _segment_arguments(1, connectivity)
@@ -1398,9 +1412,7 @@ def surface_meshes(pool: torch.Tensor, records_or_layouts, level: float = 0.0, o
             raise _lib.OmgHipError(f"volume {m} (offset {r.out_offset}, {n} elements) leaves the pool of {elems}")
     if out is not None:
         for t, name, dt in ((out[0], "out[0]", torch.float64), (out[1], "out[1]", torch.int32)):
-            _need(t, dt, name)
-            if t.device != dev or t.dim() != 2 or t.shape[1] != 3:
-                raise _lib.OmgHipError(f"{name} must be [cap,3] on {dev}, got {tuple(t.shape)} on {t.device}")
+            _tensor(t, name, dt, (None, 3), dev)
     nbytes = int(l.omgx_surface_workspace_bytes(C.cast(rec, vp), M))
     check(min(nbytes, 0), "omgx_surface_workspace_bytes")
     with torch.cuda.device(dev):
@@ -1500,9 +1512,7 @@ class _VolumeBatch:
 
     def release(self, *scratch) -> None:
         """After the last launch: the uploads, and the caller's scratch tensors, are in use by the current stream."""
-        for t in (self._d_rec.get(self._dev), self._d_begin.get(self._dev), *scratch):
-            if t is not None:
-                t.record_stream(torch.cuda.current_stream(self._dev))
+        _release(self._dev, self._d_rec.get(self._dev), self._d_begin.get(self._dev), *scratch)
 
 
 def _fusion_volumes(volumes, state_begin):
@@ -1513,6 +1523,18 @@ def _fusion_volumes(volumes, state_begin):
 
 def _upload(a: np.ndarray, dev) -> torch.Tensor:
     return torch.from_numpy(np.frombuffer(bytes(a), np.uint8).copy() if isinstance(a, C.Array) else np.ascontiguousarray(a)).to(dev)
+
+
+def _record_bytes(a: np.ndarray, dev) -> torch.Tensor:
+    """Records of a structured dtype as the bytes they are, on dev."""
+    return torch.from_numpy(np.frombuffer(a.tobytes(), np.uint8).copy()).to(dev)
+
+
+def _release(dev, *scratch) -> None:
+    """After the last launch that reads them: temporary uploads (None is skipped) are in use by dev's current stream."""
+    for t in scratch:
+        if t is not None:
+            t.record_stream(torch.cuda.current_stream(dev))
 
 
 def _fusion_radius(radius) -> int:
@@ -1562,9 +1584,7 @@ def carve_views(volumes, views, view_range, depth: torch.Tensor, band: float, ne
     (V, H, W), M = (int(d) for d in depth.shape), batch.M
     if state is None:
         state = torch.full((max(batch.end(), 1),), _fu.UNKNOWN, dtype=torch.uint8, device=dev)
-    _need(state, torch.uint8, "state")
-    if state.device != dev:
-        raise _lib.OmgHipError(f"state must be on {dev}, got {state.device}")
+    _tensor(state, "state", torch.uint8, None, dev)
     with torch.cuda.device(dev):
         d_views, d_range = _upload(h_views, dev), _upload(h_range, dev)
         check(_lib.lib().omgx_carve_views(*batch.on(dev).volume_args(), _ptr(d_views) if V else None, vp(h_views.ctypes.data) if V else None, V,
@@ -1587,9 +1607,7 @@ def distance_transform(state: torch.Tensor, state_begin, volumes, radius: int, u
     dev, l = state.device, _lib.lib()
     if out is None:
         out = torch.zeros(batch.pool_end(), dtype=torch.float32, device=dev)
-    _need(out, torch.float32, "out")
-    if out.device != dev:
-        raise _lib.OmgHipError(f"out must be on {dev}, got {out.device}")
+    _tensor(out, "out", torch.float32, None, dev)
     nbytes = int(l.omgx_distance_transform_workspace_bytes(*batch.host_args(), radius))
     check(min(nbytes, 0), "omgx_distance_transform_workspace_bytes")
     with torch.cuda.device(dev):
@@ -1705,9 +1723,7 @@ def tsdf_blend(tsdf: torch.Tensor, weight: torch.Tensor, state_begin, volumes, t
     batch = _VolumeBatch.of(volumes, state_begin)
     _tsdf_pair(tsdf, weight)
     dev = tsdf.device
-    _need(out, torch.float32, "out")
-    if out.device != dev:
-        raise _lib.OmgHipError(f"out must be on {dev}, got {out.device}")
+    _tensor(out, "out", torch.float32, None, dev)
     with torch.cuda.device(dev):
         check(_lib.lib().omgx_tsdf_blend(_ptr(tsdf), _ptr(weight), int(tsdf.numel()), *batch.on(dev).begin_args(), *batch.volume_args(), trunc,
                                          min_weight, _ptr(out), int(out.numel()), _stream()), "omgx_tsdf_blend")
@@ -1872,9 +1888,7 @@ def component_states(state: torch.Tensor, components: Components, picks, out_vol
     with torch.cuda.device(dev):
         if out is None:
             out = torch.full((max(outs.end(), 1),), _fu.UNKNOWN, dtype=torch.uint8, device=dev)
-        _need(out, torch.uint8, "out")
-        if out.device != dev:
-            raise _lib.OmgHipError(f"out must be on {dev}, got {out.device}")
+        _tensor(out, "out", torch.uint8, None, dev)
         if K == 0:
             return out, ob
         src, comp_begin = (components._batch or _VolumeBatch(components.rec, components.begin)).on(dev), components.comp_begin
@@ -1920,8 +1934,7 @@ def _plane_images(intrinsics, depth, skip, tol):
     if V and (H < 1 or W < 1):
         raise _lib.OmgHipError("the images are empty")
     tol = float(tol)
-    if not (np.isfinite(tol) and tol >= 0):
-        raise _lib.OmgHipError("tol must be finite and not negative")
+    _nonneg_finite(tol=tol)
     if skip is not None and (not isinstance(skip, torch.Tensor) or skip.dtype not in (torch.bool, torch.uint8) or skip.shape != depth.shape
                              or skip.device != depth.device):
         raise _lib.OmgHipError("skip must be a bool tensor of depth's shape, on its device")
@@ -1935,9 +1948,7 @@ def _plane_skip(skip):
 def _plane_rows(planes, V, dev, name="planes", cols=4):
     """planes [V,4] (or anchors [V,3]) as a contiguous float64 device tensor: a tensor is checked, a host array uploaded."""
     if isinstance(planes, torch.Tensor):
-        _need(planes, torch.float64, name)
-        if planes.device != dev or tuple(planes.shape) != (V, cols):
-            raise _lib.OmgHipError(f"{name} must be [{V},{cols}] on {dev}, got {tuple(planes.shape)} on {planes.device}")
+        _tensor(planes, name, torch.float64, (V, cols), dev)
         return planes
     h = np.ascontiguousarray(planes, np.float64)
     if h.shape != (V, cols):
@@ -2146,11 +2157,7 @@ class RayBatch:
                 _ptr(self.d_work), vp(self.h_work.ctypes.data), self.num_work, self.chunks)
 
     def _rays(self, t, name, cols=3, dtype=torch.float64):
-        _need(t, dtype, name)
-        want = (self.num_rays, cols) if cols else (self.num_rays,)
-        if t.device != self.device or tuple(t.shape) != want:
-            raise _lib.OmgHipError(f"{name} must be {want} on {self.device}, got {tuple(t.shape)} on {t.device}")
-        return t
+        return _tensor(t, name, dtype, (self.num_rays, cols) if cols else (self.num_rays,), self.device)
 
 
 def mesh_raycast_batch(batch: RayBatch, origins: torch.Tensor, dirs: torch.Tensor, t_min: float = 1e-6, tol: float = 1e-9, out=None):
@@ -2159,8 +2166,7 @@ def mesh_raycast_batch(batch: RayBatch, origins: torch.Tensor, dirs: torch.Tenso
     m's rays in rows [ray_begin[m], ray_begin[m] + ray_count[m]).  out: None or (t [num_rays] float64, face [num_rays] int32)
     written IN PLACE on those rows only.  -> (t, face); face is local to the mesh, (+inf, -1) is a miss; rows outside every
     range are left as they were (zeros in a fresh output)."""
-    if not (float(t_min) >= 0 and np.isfinite(float(t_min)) and float(tol) >= 0 and np.isfinite(float(tol))):
-        raise _lib.OmgHipError("t_min and tol must be finite and not negative")
+    _nonneg_finite(t_min=t_min, tol=tol)
     batch._rays(origins, "origins"), batch._rays(dirs, "dirs")
     if out is None:
         out = (torch.zeros(batch.num_rays, dtype=torch.float64, device=batch.device), torch.zeros(batch.num_rays, dtype=torch.int32, device=batch.device))
@@ -2197,16 +2203,11 @@ def grasp_poses(batch: RayBatch, p1, n1, dirs, t, face2, normals, cs, probe, poo
     if not batch.has_layout:
         raise _lib.OmgHipError("grasp_poses needs a RayBatch with the layout of the volumes")
     dev = batch.device
-    up = lambda x: x if isinstance(x, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(x, np.float64)).to(dev)
-    cs, probe = up(cs), up(probe)
-    for x, name in ((cs, "cs"), (probe, "probe"), (normals, "normals")):
-        _need(x, torch.float64, name)
-    if cs.dim() != 2 or cs.shape[1] != 2 or not 1 <= cs.shape[0] <= 65535:
+    up = lambda x: x if isinstance(x, torch.Tensor) else _upload(np.asarray(x, np.float64), dev)
+    cs, probe = _tensor(up(cs), "cs", torch.float64, (None, 2), dev), _tensor(up(probe), "probe", torch.float64, (None, 3), dev)
+    _tensor(normals, "normals", torch.float64, (batch.num_faces, 3), dev)  # one per face of the batch
+    if not 1 <= cs.shape[0] <= 65535:
         raise _lib.OmgHipError(f"cs must be [A,2] with 1 <= A <= 65535, got {tuple(cs.shape)}")
-    if probe.dim() != 2 or probe.shape[1] != 3:
-        raise _lib.OmgHipError(f"probe must be [Q,3], got {tuple(probe.shape)}")
-    if tuple(normals.shape) != (batch.num_faces, 3):
-        raise _lib.OmgHipError(f"normals must be ({batch.num_faces}, 3): one per face of the batch, got {tuple(normals.shape)}")
     _need(pool, torch.float32, "pool")
     for m in range(batch.num_meshes):
         r = batch.rec[m]
@@ -2218,17 +2219,13 @@ def grasp_poses(batch: RayBatch, p1, n1, dirs, t, face2, normals, cs, probe, poo
     A, N = int(cs.shape[0]), batch.num_rays
     if out is None:
         out = (torch.zeros((N, A, 4, 4), dtype=torch.float64, device=dev), torch.zeros((N, A), dtype=torch.uint8, device=dev))
-    poses, valid = out
-    _need(poses, torch.float64, "out[0]"), _need(valid, torch.uint8, "out[1]")
-    if tuple(poses.shape) != (N, A, 4, 4) or tuple(valid.shape) != (N, A) or poses.device != dev or valid.device != dev:
-        raise _lib.OmgHipError(f"out must be ({N}, {A}, 4, 4) float64 and ({N}, {A}) uint8 on {dev}")
+    poses, valid = _tensor(out[0], "out[0]", torch.float64, (N, A, 4, 4), dev), _tensor(out[1], "out[1]", torch.uint8, (N, A), dev)
     with torch.cuda.device(dev):
         check(_lib.lib().omgx_grasp_poses(*batch._args(), _ptr(p1), _ptr(n1), _ptr(dirs), _ptr(t), _ptr(face2), N, _ptr(normals), _ptr(cs), A,
                                           _ptr(probe), int(probe.shape[0]), _ptr(pool), pool.numel(), float(max_width), float(min_width),
                                           float(cos_cone), float(pad_depth), float(clearance), _ptr(poses), _ptr(valid), _stream()),
               "omgx_grasp_poses")
-        for x in (cs, probe):
-            x.record_stream(torch.cuda.current_stream(dev))
+        _release(dev, cs, probe)
     return poses, valid
 
 
@@ -2247,34 +2244,34 @@ class CameraBatch:
         instances = np.ascontiguousarray(instances)
         if instances.dtype != _cam.INSTANCE_DTYPE or instances.ndim != 1:
             raise _lib.OmgHipError("instances must be a 1-d array of camera.INSTANCE_DTYPE records")
-        cameras = np.ascontiguousarray(cameras, np.float64)
-        if cameras.ndim != 2 or cameras.shape[1] != 16:
-            raise _lib.OmgHipError(f"cameras must be [S,16], got {cameras.shape}")
+        for name in ("m", "centre", "q"):
+            if not np.isfinite(instances[name]).all():
+                raise _lib.OmgHipError(f"an instance's {name} is not finite")
+        if len(instances) and (instances["label"].min() < 0 or instances["mesh"].min() < 0 or instances["mesh"].max() >= len(meshes)):
+            raise _lib.OmgHipError(f"labels must be >= 0 and mesh indices inside the pool of {len(meshes)}")
+        self.num_meshes = len(meshes)
+        for m in range(self.num_meshes):
+            mp.set_volume(m, (0.0, 0.0, 0.0), 1.0, "centre", (1, 1, 1), 0)  # no volume is read; the fields stay defined
+        self.rec = mp.rec
+        self._set_records(instances, inst_begin, cameras, None, torch.device(device))
+        self.verts, self.faces, self.d_rec = mp.upload(self.device)
+
+    def _set_records(self, instances, inst_begin, cameras, S, device):
+        """What every kind of batch holds: the instance records as they are, the checked cameras [S,16] as omgx_camera records
+        with their instance ranges, both on the host and on the device.  S: the scenes there must be, if known."""
+        from . import camera as _cam
+        try:
+            cameras = _cam.check_camera_rows(cameras, S)
+        except ValueError as e:
+            raise _lib.OmgHipError(str(e)) from None
         S, I = len(cameras), len(instances)
         begin = np.asarray(inst_begin, np.int64).reshape(-1)
         if len(begin) != S + 1 or begin[0] < 0 or (np.diff(begin) < 0).any() or begin[-1] > I:
             raise _lib.OmgHipError(f"inst_begin must be [S+1] = [{S + 1}], ascending, inside the {I} instances")
-        if not np.isfinite(cameras).all() or (cameras[:, :2] == 0).any():
-            raise _lib.OmgHipError("a camera is not finite or has a focal length of zero")
-        for name in ("m", "centre", "q"):
-            if not np.isfinite(instances[name]).all():
-                raise _lib.OmgHipError(f"an instance's {name} is not finite")
-        if I and (instances["label"].min() < 0 or instances["mesh"].min() < 0 or instances["mesh"].max() >= len(meshes)):
-            raise _lib.OmgHipError(f"labels must be >= 0 and mesh indices inside the pool of {len(meshes)}")
-        self.device = torch.device(device)
-        self.num_meshes, self.num_instances, self.num_scenes = len(meshes), I, S
-        for m in range(self.num_meshes):
-            mp.set_volume(m, (0.0, 0.0, 0.0), 1.0, "centre", (1, 1, 1), 0)  # no volume is read; the fields stay defined
-        self.rec = mp.rec
-        self.h_instances = instances
-        self.h_inst_begin = begin
-        self.h_cameras = np.zeros(S, _cam.CAMERA_DTYPE)
-        self.h_cameras["fx"], self.h_cameras["fy"], self.h_cameras["cx"], self.h_cameras["cy"] = cameras[:, 0], cameras[:, 1], cameras[:, 2], cameras[:, 3]
-        self.h_cameras["world_from_cam"] = cameras[:, 4:]
-        self.h_cameras["inst_begin"], self.h_cameras["inst_count"] = begin[:-1], np.diff(begin)
-        self.verts, self.faces, self.d_rec = mp.upload(self.device)
-        as_bytes = lambda a: torch.from_numpy(np.frombuffer(a.tobytes(), np.uint8).copy()).to(self.device)
-        self.d_instances, self.d_cameras = as_bytes(self.h_instances), as_bytes(self.h_cameras)
+        self.device, self.num_instances, self.num_scenes = device, I, S
+        self.h_instances, self.h_inst_begin, self.h_cameras = instances, begin, _cam.camera_records(cameras, begin)
+        self.d_instances, self.d_cameras = _record_bytes(self.h_instances, device), _record_bytes(self.h_cameras, device)
+        return cameras
 
     def _records(self, host: bool = True):
         """(instances, [h_instances,] num_instances, cameras, [h_cameras,] num_scenes) as the entry points take them."""
@@ -2284,10 +2281,7 @@ class CameraBatch:
         return (_ptr(self.d_instances), *hi, self.num_instances, _ptr(self.d_cameras), *hc, self.num_scenes)
 
     def _image(self, t, name, dtype, H=None, W=None):
-        _need(t, dtype, name)
-        if t.device != self.device or t.dim() != 3 or t.shape[0] != self.num_scenes or (H is not None and tuple(t.shape[1:]) != (H, W)):
-            raise _lib.OmgHipError(f"{name} must be [{self.num_scenes}, H, W] on {self.device}, got {tuple(t.shape)} on {t.device}")
-        return t
+        return _tensor(t, name, dtype, (self.num_scenes, H, W), self.device)
 
 
 def _image_size(H, W):
@@ -2304,8 +2298,7 @@ def render_depth(batch: CameraBatch, H: int, W: int, cull: bool = True, want_fac
     face [S,H,W] int32 or None without want_face); background is (+inf, -1, -1).  out: None or (t, inst, face or None),
     contiguous device tensors written IN PLACE."""
     H, W = _image_size(H, W)
-    if not (float(t_min) >= 0 and np.isfinite(float(t_min)) and float(tol) >= 0 and np.isfinite(float(tol))):
-        raise _lib.OmgHipError("t_min and tol must be finite and not negative")
+    _nonneg_finite(t_min=t_min, tol=tol)
     S, dev = batch.num_scenes, batch.device
     if out is None:
         out = (torch.empty((S, H, W), dtype=torch.float64, device=dev), torch.empty((S, H, W), dtype=torch.int32, device=dev),
@@ -2334,9 +2327,7 @@ def pixel_clouds(batch: CameraBatch, t: torch.Tensor, inst: torch.Tensor, cls: i
     if not -(1 << 31) <= cls < (1 << 31):
         raise _lib.OmgHipError(f"cls must fit int32, got {cls}")
     if out is not None:
-        _need(out, torch.float64, "out")
-        if out.device != dev or out.dim() != 2 or out.shape[1] != 3:
-            raise _lib.OmgHipError(f"out must be [cap,3] on {dev}, got {tuple(out.shape)} on {out.device}")
+        _tensor(out, "out", torch.float64, (None, 3), dev)
     ws = torch.empty(max(int(l.omgx_pixel_clouds_workspace_bytes(S, H, W)) // 4, 1), dtype=torch.int32, device=dev)
     begin = torch.empty(S + 1, dtype=torch.int32, device=dev)
     with torch.cuda.device(dev):
@@ -2383,17 +2374,10 @@ def register_clouds(scenes: DeviceScenes, pairs, poses0, points: torch.Tensor, r
         poses0 = torch.from_numpy(h_poses0).to(dev)
     if tuple(poses0.shape) != (M, 12):
         raise _lib.OmgHipError(f"poses0 must be [{M},12], got {tuple(poses0.shape)}")
-    _need(points, torch.float64, "points")
-    _need(poses0, torch.float64, "poses0")
-    if points.device != dev or poses0.device != dev:
-        raise _lib.OmgHipError(f"points and poses0 must be on {dev}, got {points.device} and {poses0.device}")
+    _tensor(points, "points", torch.float64, (None, 3), dev), _tensor(poses0, "poses0", torch.float64, (M, 12), dev)
     if out is None:
         out = (torch.empty((M, 12), dtype=torch.float64, device=dev), torch.empty((M, _reg.STATS), dtype=torch.float64, device=dev))
-    poses, stats = out
-    for t, name, cols in ((poses, "out[0]", 12), (stats, "out[1]", _reg.STATS)):
-        _need(t, torch.float64, name)
-        if t.device != dev or tuple(t.shape) != (M, cols):
-            raise _lib.OmgHipError(f"{name} must be [{M},{cols}] on {dev}, got {tuple(t.shape)} on {t.device}")
+    poses, stats = _tensor(out[0], "out[0]", torch.float64, (M, 12), dev), _tensor(out[1], "out[1]", torch.float64, (M, _reg.STATS), dev)
     vp = C.c_void_p
     with torch.cuda.device(dev):
         d_index, d_ranges = torch.from_numpy(h_index).to(dev), torch.from_numpy(h_ranges).to(dev)
@@ -2413,27 +2397,14 @@ class VolumeCameraBatch(CameraBatch):
 
     def __init__(self, table: DeviceScenes, cameras, labels):
         from . import camera as _cam
-        cameras = np.ascontiguousarray(cameras, np.float64)
-        S, n = table.num_scenes, len(table.host_objects)
-        if cameras.shape != (S, 16):
-            raise _lib.OmgHipError(f"cameras must be [{S},16], got {cameras.shape}")
-        if not np.isfinite(cameras).all() or (cameras[:, :2] == 0).any():
-            raise _lib.OmgHipError("a camera is not finite or has a focal length of zero")
+        n = len(table.host_objects)
         labels = np.asarray(labels, np.int64).reshape(-1)
         if len(labels) != n or (n and labels.min() < 0):
             raise _lib.OmgHipError(f"labels must be {n} integers >= 0, one per object record")
-        begin = np.asarray(table.host_scene_begin, np.int64)
-        self.device, self.cameras = table.device, cameras
-        self.num_meshes, self.num_instances, self.num_scenes = 0, n, S
-        self.h_instances = np.zeros(n, _cam.INSTANCE_DTYPE)
-        self.h_instances["label"] = labels
-        self.h_inst_begin = begin
-        self.h_cameras = np.zeros(S, _cam.CAMERA_DTYPE)
-        self.h_cameras["fx"], self.h_cameras["fy"], self.h_cameras["cx"], self.h_cameras["cy"] = cameras[:, 0], cameras[:, 1], cameras[:, 2], cameras[:, 3]
-        self.h_cameras["world_from_cam"] = cameras[:, 4:]
-        self.h_cameras["inst_begin"], self.h_cameras["inst_count"] = begin[:-1], np.diff(begin)
-        as_bytes = lambda a: torch.from_numpy(np.frombuffer(a.tobytes(), np.uint8).copy()).to(self.device)
-        self.d_instances, self.d_cameras = as_bytes(self.h_instances), as_bytes(self.h_cameras)
+        instances = np.zeros(n, _cam.INSTANCE_DTYPE)
+        instances["label"] = labels
+        self.num_meshes = 0
+        self.cameras = self._set_records(instances, table.host_scene_begin, cameras, table.num_scenes, table.device)
 
 
 def _volume_camera_arguments(table: DeviceScenes, cameras, H, W, visible, level, t_min, min_step, relax, max_steps):
@@ -2472,18 +2443,12 @@ def render_volumes(table: DeviceScenes, cameras, H: int, W: int, visible=None, l
     t, inst, normal, steps = out
     for x, name, dtype, shape in ((t, "out[0]", torch.float64, (S, H, W)), (inst, "out[1]", torch.int32, (S, H, W)),
                                   (normal, "out[2]", torch.float64, (S, H, W, 3)), (steps, "out[3]", torch.int32, (S, H, W))):
-        if x is None and name in ("out[2]", "out[3]"):
-            continue
-        if not isinstance(x, torch.Tensor):
-            raise _lib.OmgHipError(f"{name} must be a tensor")
-        _need(x, dtype, name)
-        if x.device != dev or tuple(x.shape) != shape:
-            raise _lib.OmgHipError(f"{name} must be {list(shape)} on {dev}, got {tuple(x.shape)} on {x.device}")
+        if x is not None or name in ("out[0]", "out[1]"):
+            _tensor(x, name, dtype, shape, dev)
     vp = C.c_void_p
     h_begin = np.ascontiguousarray(table.host_scene_begin, np.int32)
     with torch.cuda.device(dev):
-        d_cameras = torch.from_numpy(h_cameras).to(dev)
-        d_visible = None if h_visible is None else torch.from_numpy(h_visible).to(dev)
+        d_cameras, d_visible = _upload(h_cameras, dev), None if h_visible is None else _upload(h_visible, dev)
         n = len(table.host_objects)
         check(_lib.lib().omgx_render_volumes(_ptr(table.objects) if n else None, vp(table.host_objects.ctypes.data) if n else None, n,
                                              _ptr(table.scene_begin), vp(h_begin.ctypes.data), S, _ptr(table.pool) if table.pool.numel() else None,
@@ -2491,9 +2456,7 @@ def render_volumes(table: DeviceScenes, cameras, H: int, W: int, visible=None, l
                                              _ptr(d_visible), None if h_visible is None else vp(h_visible.ctypes.data), H, W, float(level),
                                              float(t_min), float(min_step), float(relax), int(max_steps), _ptr(t), _ptr(inst), _ptr(normal),
                                              _ptr(steps), _stream()), "omgx_render_volumes")
-        for x in (d_cameras, d_visible):
-            if x is not None:
-                x.record_stream(torch.cuda.current_stream(dev))
+        _release(dev, d_cameras, d_visible)
     return t, inst, normal, steps
 
 
@@ -2533,7 +2496,7 @@ def _camera_records(cameras, dev):
     h = np.ascontiguousarray(cameras).reshape(-1)
     if h.dtype != _cam.CAMERA_DTYPE:
         raise _lib.OmgHipError("cameras must be camera.CAMERA_DTYPE records or a CameraBatch")
-    return torch.from_numpy(np.frombuffer(h.tobytes(), np.uint8).copy()).to(dev), h
+    return _record_bytes(h, dev), h
 
 
 def render_spheres(spheres: RobotSpheres, link_poses: torch.Tensor, cameras, config_of_view, H: int, W: int, pad: float = 0.0,
@@ -2546,17 +2509,14 @@ def render_spheres(spheres: RobotSpheres, link_poses: torch.Tensor, cameras, con
     waits for the stream).  cull=False walks every sphere in every wave: the same bits."""
     from . import robot_filter as _rf
     H, W = _image_size(H, W)
-    _need(link_poses, torch.float64, "link_poses")
-    if link_poses.dim() != 4 or tuple(link_poses.shape[1:]) != (10, 4, 4) or link_poses.device != spheres.device:
-        raise _lib.OmgHipError(f"link_poses must be [C,10,4,4] on {spheres.device}, got {tuple(link_poses.shape)} on {link_poses.device}")
+    _tensor(link_poses, "link_poses", torch.float64, (None, 10, 4, 4), spheres.device)
     dev, N, Cn, vp = spheres.device, spheres.N, int(link_poses.shape[0]), C.c_void_p
     d_cam, h_cam = _camera_records(cameras, dev)
     V = len(h_cam)
     h_cfg = np.ascontiguousarray(np.asarray(config_of_view, np.int64).reshape(-1), np.int32)
     h_poses = np.ascontiguousarray(link_poses.cpu().numpy())
+    _nonneg_finite(t_min=t_min)
     try:  # (the specification's own checks, as this module's error; nothing has touched the device's memory yet)
-        if not (np.isfinite(float(t_min)) and float(t_min) >= 0):
-            raise ValueError("t_min must be finite and not negative")
         _rf.camera_spheres(h_poses, np.zeros((0, 4)), np.zeros(0, np.int64), h_cam, h_cfg, pad)
     except ValueError as e:
         raise _lib.OmgHipError(str(e)) from None
@@ -2564,7 +2524,7 @@ def render_spheres(spheres: RobotSpheres, link_poses: torch.Tensor, cameras, con
     which = torch.empty((V, H, W), dtype=torch.int32, device=dev)
     cam_spheres = torch.empty((V, N, 4), dtype=torch.float64, device=dev)
     with torch.cuda.device(dev):
-        d_cfg = torch.from_numpy(h_cfg).to(dev)
+        d_cfg = _upload(h_cfg, dev)
         check(_lib.lib().omgx_render_spheres(_ptr(spheres.local) if N else None, vp(spheres.h_local.ctypes.data) if N else None,
                                              _ptr(spheres.link) if N else None, vp(spheres.h_link.ctypes.data) if N else None, N,
                                              _ptr(link_poses) if Cn else None, vp(h_poses.ctypes.data) if Cn else None, Cn,
@@ -2572,8 +2532,7 @@ def render_spheres(spheres: RobotSpheres, link_poses: torch.Tensor, cameras, con
                                              vp(h_cfg.ctypes.data) if V else None, V, H, W, float(pad), float(t_min), int(bool(cull)),
                                              _ptr(cam_spheres) if V and N else None, _ptr(t_near) if V else None, _ptr(which) if V else None,
                                              _stream()), "omgx_render_spheres")
-        for x in (d_cfg, d_cam):
-            x.record_stream(torch.cuda.current_stream(dev))
+        _release(dev, d_cfg, d_cam)
     return t_near, which, cam_spheres
 
 
@@ -2591,19 +2550,12 @@ def clear_robot(state: torch.Tensor, state_begin, volumes, views, view_range, de
     _need(depth, torch.float64, "depth")
     dev, vp = depth.device, C.c_void_p
     (V, H, W), M = (int(d) for d in depth.shape), batch.M
-    _need(t_near, torch.float64, "t_near")
-    if t_near.device != dev or tuple(t_near.shape) != (V, H, W):
-        raise _lib.OmgHipError(f"t_near must be {[V, H, W]} on {dev}, got {tuple(t_near.shape)} on {t_near.device}")
-    _need(cam_spheres, torch.float64, "cam_spheres")
-    if cam_spheres.device != dev or cam_spheres.dim() != 3 or cam_spheres.shape[0] != V or cam_spheres.shape[2] != 4:
-        raise _lib.OmgHipError(f"cam_spheres must be [{V},N,4] on {dev}, got {tuple(cam_spheres.shape)} on {cam_spheres.device}")
+    _tensor(t_near, "t_near", torch.float64, (V, H, W), dev), _tensor(cam_spheres, "cam_spheres", torch.float64, (V, None, 4), dev)
     N = int(cam_spheres.shape[1])
     h_sph = np.ascontiguousarray(cam_spheres.cpu().numpy() if h_cam_spheres is None else h_cam_spheres, np.float64)
     if h_sph.shape != (V, N, 4) or not np.isfinite(h_sph).all() or (h_sph[:, :, 3] < 0).any():
         raise _lib.OmgHipError("a sphere is not finite or has a negative radius")
-    _need(state, torch.uint8, "state")
-    if state.device != dev:
-        raise _lib.OmgHipError(f"state must be on {dev}, got {state.device}")
+    _tensor(state, "state", torch.uint8, None, dev)
     with torch.cuda.device(dev):
         d_views, d_range = _upload(h_views, dev), _upload(h_range, dev)
         check(_lib.lib().omgx_clear_robot(*batch.on(dev).volume_args(), _ptr(d_views) if V else None, vp(h_views.ctypes.data) if V else None, V,

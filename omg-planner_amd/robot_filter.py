@@ -43,8 +43,7 @@ def _cameras(cameras):
         raise ValueError("cameras must be camera.CAMERA_DTYPE records")
     cameras = cameras.reshape(-1)
     k = np.stack([cameras[n] for n in ("fx", "fy", "cx", "cy")], -1).reshape(-1, 4)
-    if not (np.isfinite(k).all() and np.isfinite(cameras["world_from_cam"]).all()) or (k[:, :2] == 0).any():
-        raise ValueError("a camera is not finite or has a focal length of zero")
+    _cam.check_camera_rows(np.concatenate([k, cameras["world_from_cam"].reshape(-1, 12)], 1))
     return cameras, k
 
 

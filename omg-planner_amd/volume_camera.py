@@ -43,13 +43,11 @@ def check_scalars(level, t_min, min_step, relax, max_steps) -> None:
 def check_table(objects, scene_begin, pool_elems: int, cameras, visible):
     """The records, ranges, cameras and flags of render_volumes (ValueError) -> (objects, scene_begin int64 [S+1], cameras
     [S,16], visible bool [n]).  Only the visible objects of the scenes' ranges are looked at."""
-    from . import scenes as _sc
+    from . import camera as _cam, scenes as _sc
     objects = np.asarray(objects)
     if objects.dtype != _sc.OBJECT_DTYPE or objects.ndim != 1:
         raise ValueError("objects must be a 1-d array of scenes.OBJECT_DTYPE records")
-    cameras = np.asarray(cameras, np.float64)
-    if cameras.ndim != 2 or cameras.shape[1] != 16:
-        raise ValueError(f"cameras must be [S,16], got {cameras.shape}")
+    cameras = _cam.check_camera_rows(cameras)
     begin = np.asarray(scene_begin, np.int64).reshape(-1)
     S, n = len(cameras), len(objects)
     if len(begin) != S + 1 or begin[0] < 0 or (np.diff(begin) < 0).any() or begin[-1] > n:
@@ -60,8 +58,6 @@ def check_table(objects, scene_begin, pool_elems: int, cameras, visible):
         vis = np.asarray(visible).reshape(-1) != 0
         if len(vis) != n:
             raise ValueError(f"visible must have one flag per record ({n}), got {len(vis)}")
-    if not np.isfinite(cameras).all() or (cameras[:, :2] == 0).any():
-        raise ValueError("a camera is not finite or has a focal length of zero")
     at = np.arange(int(begin[0]), int(begin[-1]))
     at = at[vis[at]]  # the visible records of the scenes, all at once: a table has hundreds
     r = objects[at]

@@ -39,7 +39,7 @@ def draw(rng):
     link = rng.integers(0, 10, N)
     poses = np.stack([np.stack([random_rigid(rng, 0.15) for _ in range(10)]) for _ in range(Cn)])
     cfg = rng.integers(0, Cn, V)
-    cams, views = np.zeros(V, camera.CAMERA_DTYPE), np.zeros((V, 16))
+    rows, views = np.zeros((V, 16)), np.zeros((V, 16))
     for v in range(V):
         world_from_cam = random_rigid(rng, 0.0)
         if N and rng.random() < 0.3:  # on a sphere's centre: inside it unless its radius is 0
@@ -49,9 +49,9 @@ def draw(rng):
             world_from_cam[:3, 3] = -world_from_cam[:3, 2] * rng.uniform(0.2, 0.8) + rng.normal(scale=0.03, size=3)
         f = float(rng.uniform(0.5, 2.0) * max(H, W))
         k = (f, f * rng.uniform(0.8, 1.25), (W - 1) / 2 + rng.normal(), (H - 1) / 2 + rng.normal())
-        cams["fx"][v], cams["fy"][v], cams["cx"][v], cams["cy"][v] = k
-        cams["world_from_cam"][v] = world_from_cam[:3].ravel()
+        rows[v] = np.concatenate([k, world_from_cam[:3].ravel()])
         views[v] = fusion.view_rows(k, np.linalg.inv(world_from_cam))  # (the grid frame is the world frame)
+    cams = camera.camera_records(rows)
     volumes, begin, at = [], [], int(rng.integers(0, 5))
     for _ in range(M):
         dims = tuple(int(d) for d in (rng.integers(1, 41, 3) if rng.random() < 0.5 else rng.integers(1, 9, 3)))

@@ -21,12 +21,7 @@ def camera_records(cam_from_world, intrinsics):
     from omg_planner_amd import camera
     cfw = np.asarray(cam_from_world, np.float64).reshape(-1, 4, 4)
     k = np.broadcast_to(np.asarray(intrinsics, np.float64), (len(cfw), 4))
-    rec = np.zeros(len(cfw), camera.CAMERA_DTYPE)
-    for v in range(len(cfw)):
-        row = camera.camera_rows(k[v], cfw[v])
-        rec["fx"][v], rec["fy"][v], rec["cx"][v], rec["cy"][v] = row[:4]
-        rec["world_from_cam"][v] = row[4:]
-    return rec
+    return camera.camera_records(np.array([camera.camera_rows(k[v], cfw[v]) for v in range(len(cfw))]).reshape(-1, 16))
 
 
 # ---------------------------------------------------------------------------------------------------------------------

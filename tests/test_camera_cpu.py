@@ -246,7 +246,7 @@ extern "C" void host_render(const double* verts, const int32_t* faces, const int
     for (int r = 0; r < H; ++r)
         for (int c = 0; c < W; ++c) {
             double dx, dy;
-            camera_pixel_dir(r, c, camera[0], camera[1], camera[2], camera[3], dx, dy);
+            image_pixel_dir(r, c, camera[0], camera[1], camera[2], camera[3], dx, dy);
             double best = __builtin_inf();
             int32_t bi = -1, bf = -1;
             for (int i = 0; i < n_inst; ++i) {
@@ -276,7 +276,7 @@ extern "C" int host_cloud(const rec* inst, int n_inst, const double* camera, int
         const int32_t label = (i >= 0 && i < n_inst) ? inst[i].label : -1;
         if (!camera_pixel_kept(i, n_inst, label, cls)) continue;
         double dx, dy;
-        camera_pixel_dir(p / W, p % W, camera[0], camera[1], camera[2], camera[3], dx, dy);
+        image_pixel_dir(p / W, p % W, camera[0], camera[1], camera[2], camera[3], dx, dy);
         camera_world_point(camera + 4, t[p], dx, dy, points + 3 * n++);
     }
     return n;

@@ -322,3 +322,37 @@ def test_seventy_scenes_in_one_render(dev):
         torch.cuda.synchronize()
         assert len(flat) > 0 and begin.tolist() == np.concatenate([[0], np.cumsum([len(w) for w in want])]).tolist(), cls
         assert np.array_equal(points.cpu().numpy().view(np.int64), flat.view(np.int64)), cls
+
+
+def partial_tiles_case():
+    """One box before two cameras of 17 x 33 pixels (2 x 3 tiles, partial both ways): in view 0 it lies over the corner where four
+    tiles meet, in view 1 over the image's last row and last column -> (scene dict, the specification's images)."""
+    from omg_planner_amd import camera as cam
+    H, W = 17, 33
+    intr = [(30.0, 28.0, 16.0, 8.0), (26.0, 30.0, 14.5, 9.25)]
+    views = [(intr[0], CC.EYE, [(0, MC.pose((0.2, 0.1, -0.3), CC.at_pixel(intr[0], H, W, 16.0 / H, 16.0 / W, 0.3)), 0)]),
+             (intr[1], CC.EYE, [(0, MC.pose((-0.1, 0.3, 0.2), CC.at_pixel(intr[1], H, W, 15.0 / H, 30.0 / W, 0.25)), 1)])]
+    sc = CC.build([CC.BOX], views, H, W)
+    want = cam.render_depth(sc["meshes"], sc["instances"], sc["inst_begin"], sc["cameras"], H, W)
+    hit = want[1] >= 0
+    assert all(hit[0, r, c] for r in (15, 16) for c in (15, 16)) and hit[1, 16].any() and hit[1, :, 32].any()  # across the tiles' borders
+    assert all(h.any() and not h.all() for h in hit) and not hit[1, 16].all() and not hit[1, :, 32].all()
+    return sc, want
+
+
+def test_partial_tiles_of_two_views_equal_the_specification(dev):
+    """The smallest launch in which a wrong tile map or a wrong clamp of the lanes outside the image shows: 17 x 33 pixels and two
+    views of one box.  Depth as bits, instance and face equal camera.render_depth with and without the cull, and the cloud of
+    pixel_clouds on the same images equals camera.pixel_clouds as bits."""
+    from omg_planner_amd import camera as cam, ops
+    sc, want = partial_tiles_case()
+    b = ops.CameraBatch(sc["meshes"], sc["instances"], sc["inst_begin"], sc["cameras"], device=dev)
+    for cull in (True, False):
+        got = ops.render_depth(b, sc["H"], sc["W"], cull=cull)
+        assert got[0].shape == (2, 17, 33) and _same(got, want), cull
+    for cls in (-1, 1):
+        spec = cam.pixel_clouds(want[0], want[1], CC.labels(sc), sc["inst_begin"], sc["cameras"], cls)
+        points, begin = ops.pixel_clouds(b, got[0], got[1], cls)
+        torch.cuda.synchronize()
+        assert len(spec[1]) > 0 and begin.tolist() == [0, len(spec[0]), len(spec[0]) + len(spec[1])], cls
+        assert np.array_equal(points.cpu().numpy().view(np.int64), np.concatenate(spec).view(np.int64)), cls

@@ -365,3 +365,47 @@ def test_a_short_seeded_fuzz_run(dev):
     fuzz = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(fuzz)
     assert fuzz.main(trials=fuzz.SMOKE_TRIALS, seed=fuzz.SMOKE_SEED) == 0
+
+
+def partial_tiles_case():
+    """Two spheres on link 0 (at the identity: local is the world) before two cameras of 17 x 33 pixels (2 x 3 tiles, partial both
+    ways): in view 0 the large one lies over the corner where four tiles meet, in view 1 over the image's last row and last column
+    -> dict(local, link, link_poses, rows [2,16], cameras, config_of_view, cam_spheres, t_near, sphere: the specification's)."""
+    from omg_planner_amd import camera, robot_filter as rf
+    local, link = np.array([(0.0, 0.0, 0.5, 0.08), (-0.07, -0.05, 0.4, 0.03)]), np.zeros(2, np.int64)
+    poses, cfg = np.tile(np.eye(4), (1, 10, 1, 1)), np.zeros(2, np.int64)
+    rows = np.stack([camera.camera_rows((30.0, 28.0, 16.0, 16.0), np.eye(4)), camera.camera_rows((26.0, 30.0, 31.0, 15.5), np.eye(4))])
+    cameras = camera.camera_records(rows)
+    cam_spheres = rf.camera_spheres(poses, local, link, cameras, cfg, 0.01)
+    t_near, sphere = rf.render_spheres(cam_spheres, cameras, 17, 33, 1e-6)
+    hit = sphere >= 0
+    assert all(hit[0, r, c] for r in (15, 16) for c in (15, 16)) and hit[1, 16].any() and hit[1, :, 32].any()  # across the tiles' borders
+    assert all(h.any() and not h.all() for h in hit) and not hit[1, 16].all() and not hit[1, :, 32].all() and (sphere == 1).any()
+    return dict(local=local, link=link, link_poses=poses, rows=rows, cameras=cameras, config_of_view=cfg, cam_spheres=cam_spheres, t_near=t_near,
+                sphere=sphere)
+
+
+def test_partial_tiles_of_two_views_equal_the_specification(dev):
+    """The smallest launch in which a wrong tile map or a wrong clamp of the lanes outside the image shows: 17 x 33 pixels and two
+    views of two spheres.  cam_spheres, t_near and sphere equal robot_filter.py byte for byte with and without the cull, from
+    camera records and from a CameraBatch's own; with an instance per sphere in that batch the cloud of pixel_clouds on the same
+    images equals camera.pixel_clouds as bits."""
+    from omg_planner_amd import camera, ops
+    from tests import mesh_cases as MC
+    c = partial_tiles_case()
+    spheres = ops.RobotSpheres(c["local"], c["link"], device=dev)
+    poses = torch.from_numpy(c["link_poses"]).to(dev)
+    instances = np.zeros(4, camera.INSTANCE_DTYPE)
+    instances["label"] = labels = [0, 1, 0, 1]  # (the instance image is the sphere image: sphere k of a view is its instance k)
+    batch = ops.CameraBatch([MC.box_mesh(MC.BOX_HALF)], instances, [0, 2, 4], c["rows"], device=dev)
+    for cameras in (c["cameras"], batch):
+        for cull in (True, False):
+            t_near, which, cs = ops.render_spheres(spheres, poses, cameras, c["config_of_view"], 17, 33, pad=0.01, t_min=1e-6, cull=cull)
+            torch.cuda.synchronize()
+            assert _same(cs, c["cam_spheres"]) and _same(t_near, c["t_near"]) and _same(which, c["sphere"]), cull
+    for cls in (-1, 1):
+        spec = camera.pixel_clouds(c["t_near"], c["sphere"], labels, [0, 2, 4], c["rows"], cls)
+        points, begin = ops.pixel_clouds(batch, t_near, which, cls)
+        torch.cuda.synchronize()
+        assert len(spec[0]) > 0 and begin.tolist() == [0, len(spec[0]), len(spec[0]) + len(spec[1])], cls
+        assert np.array_equal(points.cpu().numpy().view(np.int64), np.concatenate(spec).view(np.int64)), cls

@@ -243,3 +243,42 @@ def test_a_short_seeded_fuzz_run(dev):
     fuzz = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(fuzz)
     assert fuzz.main(trials=fuzz.SMOKE_TRIALS, seed=fuzz.SMOKE_SEED) == 0
+
+
+def partial_tiles_case():
+    """The 8^3 sphere as the one object of two scenes, before two cameras of 17 x 33 pixels (2 x 3 tiles, partial both ways): in view
+    0 it lies over the corner where four tiles meet, in view 1 over the image's last row and last column -> (objects, scene_begin,
+    pool, cameras, arguments, the specification's images)."""
+    from omg_planner_amd import camera, volume_camera as vc
+    objects, _, pool, delta = VC.sphere_table(8)
+    assert tuple(objects["dim"][0]) == (8, 8, 8)
+    objects, begin = np.concatenate([objects, objects]), np.array([0, 1, 2], np.int32)
+    cfw = np.eye(4)
+    cfw[:3, 3] = -VC.SPHERE_EYE
+    cams = np.stack([camera.camera_rows((50.0, 46.0, 16.0, 16.0), cfw), camera.camera_rows((44.0, 50.0, 31.0, 15.5), cfw)])
+    args = dict(min_step=delta / 16, max_steps=256, relax=1.0)
+    want = vc.render_volumes(objects, begin, pool, cams, 17, 33, **args)
+    hit = want[1] >= 0
+    assert all(hit[0, r, c] for r in (15, 16) for c in (15, 16)) and hit[1, 16].any() and hit[1, :, 32].any()  # across the tiles' borders
+    assert all(h.any() and not h.all() for h in hit) and not hit[1, 16].all() and not hit[1, :, 32].all()
+    return objects, begin, pool, cams, args, want
+
+
+def test_partial_tiles_of_two_views_equal_the_specification(dev):
+    """The smallest launch in which a wrong tile map or a wrong clamp of the lanes outside the image shows: 17 x 33 pixels and two
+    views of one 8^3 volume.  Depth and normal as bits, object and steps equal volume_camera.render_volumes, and the cloud of
+    pixel_clouds on the same images equals camera.pixel_clouds as bits."""
+    from omg_planner_amd import camera, ops
+    objects, begin, pool, cams, args, want = partial_tiles_case()
+    table = _table(dev, objects, begin, pool)
+    got = ops.render_volumes(table, cams, 17, 33, want_normals=True, want_steps=True, **args)
+    torch.cuda.synchronize()
+    assert got[0].shape == (2, 17, 33) and VC.same_images(_host(got), want)
+    labels = [1, 0]
+    batch = ops.VolumeCameraBatch(table, cams, labels)
+    for cls in (-1, 1):
+        spec = camera.pixel_clouds(want[0], want[1], labels, table.host_scene_begin, cams, cls)
+        points, at = ops.pixel_clouds(batch, got[0], got[1], cls)
+        torch.cuda.synchronize()
+        assert len(spec[0]) > 0 and at.tolist() == [0, len(spec[0]), len(spec[0]) + len(spec[1])], cls
+        assert np.array_equal(points.cpu().numpy().view(np.int64), np.concatenate(spec).view(np.int64)), cls
