@@ -1298,6 +1298,63 @@ int omgx_clear_robot(const omgx_mesh* volumes, const omgx_mesh* h_volumes, int32
                      int32_t num_spheres, double near, double tol, int32_t cull, uint8_t* state, int64_t state_elems, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * (23) omgx_depth_condition, omgx_depth_normals: a sensor's frames to the clean depth images sections 14 to 22 read
+ * Stands in for: nothing.  The reference's perception entry (omg/core.py:826-867) renders noise-free images and never meets a
+ * sensor's frame: uint16 millimetres with 0 for "no return", axial noise that grows with range, flying pixels between
+ * foreground and background at silhouettes, junk at grazing angles.  omg-planner_amd/sensor.py (condition_depth, depth_normals)
+ * is the specification; all arithmetic is float64 without contraction, + - * / and comparisons (sqrt in the normals), every
+ * operation rounded on its own, and the results have the specification's bits.  New entry points only: omgx_abi_version()
+ * stays 14.
+ *
+ * omgx_depth_condition: ONE launch for V images [V][H][W], a workgroup of OMGX_CAMERA_PIXELS_PER_WORKGROUP threads per 16 x 16
+ *   pixel tile, a thread per pixel, gridDim.y the view.  in_kind OMGX_SENSOR_UINT16: z = (double)raw * scale;
+ *   OMGX_SENSOR_FLOAT64: z as given.  A pixel has a RETURN if z_min <= z <= z_max (NaN, +-inf, 0 and negatives have none;
+ *   z_min > 0).  tau(z) = (t0 + t1*z) + t2*(z*z).  A pixel p with a return is FLYING if fewer than min_support of its 8
+ *   neighbours q (inside the image) have a return with d = z(q) - z(p), d <= tau(z(p)) and -d <= tau(z(p)).  The others with a
+ *   return SURVIVE and are filtered over the (2R+1)^2 window, the taps q in row-major order (table[k], k = 0, 1, ...):
+ *     rho = range_scale * tau(z(p));  x = (z(q) - z(p)) / rho;  u = 1 - x*x;  w = table[k] * (u*u) if q survives and u > 0, else 0
+ *     num = num + w * z(q);  den = den + w;        depth_out = num / den if den > 0, else z(p);  with R == 0: z(p) itself
+ *   depth_out [V][H][W] double: 0.0 where the pixel does not survive (what every reader takes as "no information");
+ *   flags [V][H][W] uint8: OMGX_SENSOR_KEPT, OMGX_SENSOR_NO_RETURN or OMGX_SENSOR_FLYING.  The tile's z with a halo of R + 1 is
+ *   staged in LDS.  `table` is on the device, h_table the same on the host: (2R+1)^2 doubles, finite, >= 0, the centre > 0.
+ * omgx_depth_normals: ONE launch for V conditioned images (a pixel is THERE if z > 0) with the intrinsics rows [V][4] =
+ *   fx, fy, cx, cy.  P = (dx*z, dy*z, z) with section 14's ray.  A neighbour is usable if it is inside the image, there, and
+ *   within tau(z(p)) of z(p) as above.  a = P(right) - P(left) if both are usable, else the one-sided difference with P(p) in
+ *   place of the other; b = P(down) - P(up) alike; no normal if a or b has no usable neighbour.
+ *     m = a x b = (a1*b2 - a2*b1, a2*b0 - a0*b2, a0*b1 - a1*b0);  s = (m0*P0 + m1*P1) + m2*P2;  nn = (m0*m0 + m1*m1) + m2*m2
+ *     no normal unless (s > 0 or s < 0) and nn > 0;  m = -m if s > 0;  n = m / sqrt(nn)
+ *     cos = -((n0*P0 + n1*P1) + n2*P2) / sqrt((P0*P0 + P1*P1) + P2*P2);  GRAZING if cos < cos_min
+ *   The normal is in the camera's frame, of unit length, and faces the camera, as normal_out of section 21.
+ *   normals [V][H][W][3]: zeros without a normal or where grazing; depth_out: 0.0 where grazing or nothing is there, else the
+ *   input's bits; flags_out: OMGX_SENSOR_KEPT, OMGX_SENSOR_KEPT | OMGX_SENSOR_NO_NORMAL, OMGX_SENSOR_GRAZING, and where nothing is
+ *   there flags_in's value (OMGX_SENSOR_NO_RETURN if that is 0 or flags_in is NULL); flags_out may be flags_in; cosine
+ *   [V][H][W] or NULL: cos of the kept pixels with a normal, else 0.0.  Every element is written by one thread; the tile's
+ *   depths with a halo of 1 pass through LDS.
+ * ALL checks are made on the host before any HIP call.  OMGX_ERR_INVALID: a null pointer that a positive count needs, a
+ * negative count, H or W < 1, an in_kind that is neither; scale, z_min, z_max, range_scale, cos_min, t0, t1 or t2 not finite,
+ * scale <= 0, z_min <= 0, z_min > z_max, range_scale <= 0, t0, t1 or t2 < 0; min_support outside [0, 8]; radius < 0; a table
+ * entry not finite or < 0, a centre of 0; an intrinsics field not finite, fx or fy zero; depth_out (normals, cosine) sharing a
+ * byte with depth_in.  OMGX_ERR_UNSUPPORTED: radius > OMGX_SENSOR_MAX_RADIUS, more than 65535 views or 2^23 tiles,
+ * num_views * H * W > 2^31 - 1.  num_views == 0 returns OMGX_OK and launches nothing.
+ * ------------------------------------------------------------------------------------------- */
+#define OMGX_SENSOR_MAX_RADIUS 7
+#define OMGX_SENSOR_UINT16 0
+#define OMGX_SENSOR_FLOAT64 1
+#define OMGX_SENSOR_KEPT 0
+#define OMGX_SENSOR_NO_RETURN 1
+#define OMGX_SENSOR_FLYING 2
+#define OMGX_SENSOR_GRAZING 3
+#define OMGX_SENSOR_NO_NORMAL 8 /* a bit beside OMGX_SENSOR_KEPT                                   */
+int omgx_depth_condition(const void* depth_in /* [V][H][W] uint16 or double */, int32_t in_kind, double scale, int32_t num_views,
+                         int32_t H, int32_t W, double z_min, double z_max, double t0, double t1, double t2, int32_t min_support,
+                         int32_t radius, const double* table /* [(2R+1)^2] */, const double* h_table, double range_scale,
+                         double* depth_out, uint8_t* flags, void* stream);
+int omgx_depth_normals(const double* depth_in, const uint8_t* flags_in /* or NULL */, const double* intrinsics /* [V][4] */,
+                       const double* h_intrinsics, int32_t num_views, int32_t H, int32_t W, double t0, double t1, double t2,
+                       double cos_min, double* normals /* [V][H][W][3] */, double* depth_out, uint8_t* flags_out,
+                       double* cosine /* or NULL */, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Diagnostics
  * ------------------------------------------------------------------------------------------- */
 const char* omgx_last_error(void); /* thread-local text of the last OMGX_ERR_LAUNCH               */

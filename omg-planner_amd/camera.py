@@ -14,7 +14,7 @@ with dx = (c - cx) / fx, dy = (r - cy) / fy, dz = 1, so the hit parameter t is t
 Instance: one (mesh, pose, label), see INSTANCE_DTYPE and instance_records.
 
 Everything specified is plain numpy float64 with every dot product written (x*x' + y*y') + z*z', so that the device can equal
-the bits.  Not part of the contract: colour, textures, lighting, a far plane, noise.  The robot's own links in a real image: robot_filter.py.
+the bits.  Not part of the contract: colour, textures, lighting, a far plane, noise (a sensor's frames become such images in sensor.py).  The robot's own links in a real image: robot_filter.py.
 """
 from __future__ import annotations
 
@@ -210,15 +210,41 @@ def scene_records(scenes, meshes, cam_from_world, intrinsics):
 
 class Observation:
     """observe_scenes' result: the images on the device (t [S,H,W] float64, inst and face [S,H,W] int32) and the batch;
-    observe_volumes' has no face image and may have normals [S,H,W,3] float64."""
+    observe_volumes' has no face image and may have normals [S,H,W,3] float64; conditioned's has normals and the sensor flags
+    [S,H,W] uint8; observe_frames' has no instances at all (inst and face are -1 everywhere)."""
 
-    def __init__(self, batch, t, inst, face, normals=None):
-        self.batch, self.t, self.inst, self.face, self.normals = batch, t, inst, face, normals
+    def __init__(self, batch, t, inst, face, normals=None, flags=None):
+        self.batch, self.t, self.inst, self.face, self.normals, self.flags = batch, t, inst, face, normals, flags
+
+    def _needs_instances(self, what: str) -> None:
+        if getattr(self.batch, "frames_only", False):
+            raise _lib.OmgHipError(f"{what} needs an instance image, and an observation built from sensor frames alone (observe_frames) has none")
+
+    def conditioned(self, tau, cos_min: float = 0.0, scale: float = 1.0, z_min: float = 1e-3, z_max: float = 1e3, frames=None, **filter):
+        """A new Observation on the same batch with the images conditioned as a sensor's frames (ops.condition_depth, then
+        ops.depth_normals: two launches, no host sync; sensor.py is the specification): t is 0.0 where there is no return, a flying
+        pixel or a grazing angle (cos < cos_min) and the bilateral filter's value elsewhere; inst and face are -1 on the dropped
+        pixels, so that pixel_clouds emits no point at depth 0; normals [S,H,W,3] in the camera's frame, facing the camera (what
+        observe_volumes' normals are); flags [S,H,W] uint8 (sensor.KEPT ...).  frames: None for self.t itself (float64, +inf is
+        no return), or the sensor's [S,H,W] uint16 or float64 device tensor in its place (z = raw * scale for uint16).  tau =
+        (t0, t1, t2); filter: min_support, radius, table, sigma_px, range_scale of ops.condition_depth."""
+        import torch
+        from . import ops
+        source = self.t if frames is None else frames
+        if tuple(source.shape) != tuple(self.t.shape):
+            raise _lib.OmgHipError(f"frames must be {list(self.t.shape)}, as the observation's images, got {list(source.shape)}")
+        depth, flags = ops.condition_depth(source, scale, z_min, z_max, tau, **filter)
+        normals, t, flags, _ = ops.depth_normals(depth, self.intrinsics().reshape(-1, 4), tau, cos_min, flags=flags)
+        dropped = ~(t > 0)
+        inst = torch.where(dropped, torch.full_like(self.inst, -1), self.inst).contiguous()
+        face = None if self.face is None else torch.where(dropped, torch.full_like(self.face, -1), self.face).contiguous()
+        return Observation(self.batch, t, inst, face, normals, flags)
 
     def clouds(self, cls: int):
         """S contiguous float64 [N_s,3] device tensors in the world frame (what ops.point_cloud_sdf takes): class 0 is the
         target, 1 everything else, < 0 every hit."""
         from . import ops
+        self._needs_instances("clouds")
         points, begin = ops.pixel_clouds(self.batch, self.t, self.inst, cls)
         return [points[int(begin[s]): int(begin[s + 1])] for s in range(len(begin) - 1)]
 
@@ -267,6 +293,8 @@ class Observation:
         image m the one of pair m's scene, the view rows [n,16], view_range [n,2] = (m, 1), the target's pixels as a bool mask
         [n,H,W] or None)."""
         import torch
+        if target_free:
+            self._needs_instances("target_free")
         pairs = np.asarray(pairs, np.int64).reshape(-1, 2)
         views = self.view_rows(table, pairs)
         free_mask = None
@@ -364,6 +392,34 @@ def observe_scenes(scenes, meshes, cam_from_world, intrinsics, H: int, W: int, c
     batch = ops.CameraBatch(pool, instances, inst_begin, cameras, device=device)
     t, inst, face = ops.render_depth(batch, H, W, cull=cull)
     return Observation(batch, t, inst, face)
+
+
+def observe_frames(frames, scale: float, cam_from_world, intrinsics, tau, cos_min: float = 0.0, z_min: float = 1e-3, z_max: float = 1e3,
+                   device="cuda:0", **filter) -> Observation:
+    """An Observation from sensor frames ALONE: frames [S,H,W], uint16 (z = raw * scale, 0 is no return) or float64 (z as given), a
+    device tensor or a host array (uploaded), one per camera, conditioned on the device (Observation.conditioned, which documents
+    tau, cos_min, z_min, z_max and filter).  cam_from_world: [4,4] or [S,4,4]; intrinsics: (fx, fy, cx, cy) or [S,4].  Its batch
+    (ops.FrameBatch) has the cameras and no instances; inst and face are -1 everywhere; normals and flags are filled.
+    What works on it: segment_obstacles, fit_supports, support_planes, robot_view, view_rows, intrinsics, conditioned, and
+    fuse_obstacles / integrate_obstacles with target_free=False.  What needs an instance image and raises: clouds, and
+    fuse_obstacles / integrate_obstacles with target_free=True.  It does not call the planner."""
+    import torch
+    from . import ops
+    if not isinstance(frames, torch.Tensor):
+        frames = np.ascontiguousarray(frames)
+        if frames.dtype not in (np.uint16, np.float64):
+            raise _lib.OmgHipError(f"frames must be uint16 or float64, got {frames.dtype}")
+        frames = torch.from_numpy(frames).to(device)
+    if frames.dim() != 3:
+        raise _lib.OmgHipError(f"frames must be [S,H,W], got {tuple(frames.shape)}")
+    S = int(frames.shape[0])
+    cfw = np.broadcast_to(np.asarray(cam_from_world, np.float64), (S, 4, 4))
+    intr = np.broadcast_to(np.asarray(intrinsics, np.float64), (S, 4))
+    cameras = np.stack([camera_rows(intr[s], cfw[s]) for s in range(S)]) if S else np.zeros((0, 16))
+    batch = ops.FrameBatch(cameras, device=frames.device)
+    none = torch.full(tuple(frames.shape), -1, dtype=torch.int32, device=frames.device)
+    blank = Observation(batch, torch.zeros(tuple(frames.shape), dtype=torch.float64, device=frames.device), none, none)
+    return blank.conditioned(tau, cos_min, scale, z_min, z_max, frames=frames.contiguous(), **filter)
 
 
 def table_object_poses(table) -> np.ndarray:

@@ -2627,3 +2627,96 @@ def _robot_step(robot: "RobotView | None", depth: torch.Tensor, views, view_rang
         return clear_robot(state, state_begin, volumes, views, view_range, depth, near, robot.t_near, robot.cam_spheres, robot.tol,
                            h_cam_spheres=robot.h_cam_spheres)
     return filtered, clear
+
+
+def _sensor_table(radius, table, sigma_px, dev):
+    """(R, the spatial table on the host, the same on dev): the caller's, or a Gaussian of sigma_px pixels through numpy."""
+    from . import sensor as _sn
+    try:
+        R, h_table = _sn.check_table(_sn.gaussian_table(radius, sigma_px) if table is None else table, radius)
+    except ValueError as e:
+        raise _lib.OmgHipError(str(e)) from None
+    return R, h_table, _upload(h_table, dev)
+
+
+def condition_depth(frames: torch.Tensor, scale: float, z_min: float, z_max: float, tau, min_support: int = 3, radius: int = 3, table=None,
+                    sigma_px: float = 2.0, range_scale: float = 3.0, out=None):
+    """A sensor's frames as clean depth images, V views in ONE launch (omgx_depth_condition; sensor.condition_depth is the
+    specification: the same float64 bit for bit, the same flags) -> (depth [V,H,W] float64: 0.0 where there is no return or a flying
+    pixel, the bilateral filter of the rest; flags [V,H,W] uint8: sensor.KEPT, NO_RETURN, FLYING).  frames [V,H,W]: a contiguous
+    uint16 device tensor (z = raw * scale) or a float64 one (z as given: a rendered image, +inf as no return); tau = (t0, t1, t2):
+    the noise scale (t0 + t1*z) + t2*z*z; table: the (2*radius+1)^2 spatial weights on the host, or None for a Gaussian of sigma_px
+    pixels (sensor.gaussian_table).  out: None or (depth, flags) written IN PLACE; depth may not be `frames`."""
+    from . import sensor as _sn
+    if not isinstance(frames, torch.Tensor) or frames.dtype not in (torch.uint16, torch.float64):
+        raise _lib.OmgHipError("frames must be a uint16 or float64 tensor [V,H,W]")
+    _tensor(frames, "frames", frames.dtype, (None, None, None), frames.device)
+    dev, (V, H, W) = frames.device, (int(d) for d in frames.shape)
+    if V:
+        _image_size(H, W)
+    try:
+        _sn.check_condition(np.zeros((0, 1, 1), np.uint16), scale, z_min, z_max, tau, min_support, 0, [1.0], range_scale)
+        t0, t1, t2 = _sn.check_tau(tau)
+    except ValueError as e:
+        raise _lib.OmgHipError(str(e)) from None
+    if out is None:
+        out = (torch.empty((V, H, W), dtype=torch.float64, device=dev), torch.empty((V, H, W), dtype=torch.uint8, device=dev))
+    depth, flags = _tensor(out[0], "out[0]", torch.float64, (V, H, W), dev), _tensor(out[1], "out[1]", torch.uint8, (V, H, W), dev)
+    with torch.cuda.device(dev):
+        R, h_table, d_table = _sensor_table(radius, table, sigma_px, dev)
+        check(_lib.lib().omgx_depth_condition(_ptr(frames) if V else None, _sn.UINT16 if frames.dtype == torch.uint16 else _sn.FLOAT64, float(scale),
+                                              V, H, W, float(z_min), float(z_max), t0, t1, t2, int(min_support), R, _ptr(d_table),
+                                              C.c_void_p(h_table.ctypes.data), float(range_scale), _ptr(depth) if V else None,
+                                              _ptr(flags) if V else None, _stream()), "omgx_depth_condition")
+        _release(dev, d_table)
+    return depth, flags
+
+
+def depth_normals(depth: torch.Tensor, intrinsics, tau, cos_min: float = 0.0, flags: "torch.Tensor | None" = None, want_cosine: bool = False,
+                  out=None):
+    """Normal maps of V conditioned depth images in ONE launch (omgx_depth_normals; sensor.depth_normals is the specification: the
+    same float64 bit for bit) -> (normals [V,H,W,3] float64: unit, in the camera's frame, facing the camera as render_volumes' are,
+    zeros without one; depth_out [V,H,W]: depth with the grazing pixels (cos < cos_min) set to 0.0; flags [V,H,W] uint8: sensor.KEPT,
+    KEPT | NO_NORMAL, GRAZING, or what `flags` says where nothing is there; cosine [V,H,W] or None).  depth: a contiguous float64
+    device tensor, a pixel is there if > 0; intrinsics [V,4] on the host: fx, fy, cx, cy (Observation.intrinsics); tau as
+    condition_depth takes it; flags: condition_depth's, or None.  out: None or (normals, depth_out, flags_out, cosine or None)
+    written IN PLACE; flags_out may be `flags`, depth_out may not be `depth`."""
+    from . import sensor as _sn
+    _tensor(depth, "depth", torch.float64, (None, None, None), depth.device if isinstance(depth, torch.Tensor) else None)
+    dev, (V, H, W) = depth.device, (int(d) for d in depth.shape)
+    if V:
+        _image_size(H, W)
+    try:
+        _, h_k, (t0, t1, t2), cos_min, _ = _sn.check_normals(np.zeros((V, 1, 1)), intrinsics, tau, cos_min, None)
+    except ValueError as e:
+        raise _lib.OmgHipError(str(e)) from None
+    if flags is not None:
+        _tensor(flags, "flags", torch.uint8, (V, H, W), dev)
+    if out is None:
+        out = (torch.empty((V, H, W, 3), dtype=torch.float64, device=dev), torch.empty((V, H, W), dtype=torch.float64, device=dev),
+               torch.empty((V, H, W), dtype=torch.uint8, device=dev), torch.empty((V, H, W), dtype=torch.float64, device=dev) if want_cosine else None)
+    normals, depth_out, flags_out, cosine = out
+    _tensor(normals, "out[0]", torch.float64, (V, H, W, 3), dev), _tensor(depth_out, "out[1]", torch.float64, (V, H, W), dev)
+    _tensor(flags_out, "out[2]", torch.uint8, (V, H, W), dev)
+    if cosine is not None:
+        _tensor(cosine, "out[3]", torch.float64, (V, H, W), dev)
+    with torch.cuda.device(dev):
+        d_k = _upload(h_k, dev)
+        check(_lib.lib().omgx_depth_normals(_ptr(depth) if V else None, _ptr(flags) if V else None, _ptr(d_k) if V else None,
+                                            C.c_void_p(h_k.ctypes.data) if V else None, V, H, W, t0, t1, t2, cos_min, _ptr(normals) if V else None,
+                                            _ptr(depth_out) if V else None, _ptr(flags_out) if V else None, _ptr(cosine) if V else None,
+                                            _stream()), "omgx_depth_normals")
+        _release(dev, d_k)
+    return normals, depth_out, flags_out, cosine
+
+
+class FrameBatch(CameraBatch):
+    """The batch of an observation made of sensor frames alone (camera.observe_frames): the cameras [S,16] (camera.camera_rows) as
+    host and device records, and no instance, no mesh: every scene's instance range is empty."""
+    frames_only = True
+
+    def __init__(self, cameras, device="cuda:0"):
+        from . import camera as _cam
+        self.num_meshes = 0
+        cameras = np.asarray(cameras, np.float64)
+        self.cameras = self._set_records(np.zeros(0, _cam.INSTANCE_DTYPE), np.zeros(len(cameras) + 1, np.int64), cameras, None, torch.device(device))
