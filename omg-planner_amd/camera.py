@@ -325,14 +325,9 @@ class Observation:
         volume are in that object's frame, so target_pairs[n] should stand at the same pose.  free_mask: bool [n,H,W], the pixels
         that count as background (explained_mask of the known objects: the support); robot as fuse_obstacles takes it, so that
         the arm is no component.  -> (radius, records [n,8], Components)."""
-        import torch
-        obstacle_pairs = np.asarray(obstacle_pairs, np.int64).reshape(-1, 2)
-        views = self.view_rows(table, obstacle_pairs)
-        depth = self.t[torch.from_numpy(obstacle_pairs[:, 0].copy()).to(self.t.device)].contiguous()
-        ranges = np.stack([np.arange(len(obstacle_pairs)), np.ones(len(obstacle_pairs), np.int64)], -1)
+        obstacle_pairs, depth, views, ranges, _ = self._obstacle_views(table, obstacle_pairs, target_free=False)
         return table.segment_obstacles(target_pairs, obstacle_pairs, depth, views, ranges, layouts, band, near, reach, seeds, min_nodes,
                                        connectivity, margin, free_mask, robot=None if robot is None else robot.take(obstacle_pairs[:, 0]))
-
 
     def intrinsics(self) -> np.ndarray:
         """[S,4] float64: fx, fy, cx, cy of every scene's camera, from the batch's host records."""

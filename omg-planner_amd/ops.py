@@ -389,6 +389,21 @@ class DeviceScenes:
             raise IndexError(f"scene {scene} has {hi - lo} objects")
         return lo + obj
 
+    def _rows(self, pairs, unique=None) -> list:
+        """The record rows of the (scene, obj) `pairs`.  unique: None, or the error to raise for a pair that is named twice."""
+        rows = [self._index(int(s), int(o)) for s, o in np.asarray(pairs, np.int64).reshape(-1, 2)]
+        if unique is not None and len(set(rows)) != len(rows):
+            raise unique("a (scene, obj) pair is named twice")
+        return rows
+
+    def _writer_rows(self, pairs, layouts):
+        """What an obstacle writer starts with -> (the pairs' rows, the layouts as a list): one layout per pair, no pair twice."""
+        self._changing(volumes=True)
+        pairs, layouts = np.asarray(pairs, np.int64).reshape(-1, 2), list(layouts)
+        if len(layouts) != len(pairs) or not len(pairs):
+            raise _lib.OmgHipError(f"{len(pairs)} pairs need as many layouts, and at least one")
+        return self._rows(pairs, unique=_lib.OmgHipError), layouts
+
     def _record_ptr(self, idx: int) -> C.c_void_p:
         return C.c_void_p(self.objects.data_ptr() + idx * self.host_objects.dtype.itemsize)
 
@@ -424,9 +439,7 @@ class DeviceScenes:
         poses = np.asarray(poses, np.float64).reshape(-1, 4, 4)
         if len(poses) != len(pairs):
             raise ValueError(f"{len(pairs)} pairs but {len(poses)} poses")
-        idx = np.array([self._index(int(s), int(o)) for s, o in pairs], np.int64)
-        if len(np.unique(idx)) != len(idx):
-            raise ValueError("a (scene, obj) pair is named twice")
+        idx = np.array(self._rows(pairs, unique=ValueError), np.int64)
         if not len(idx):
             return
         inv = np.stack([_sc.se3_inverse(P)[:3, :4] for P in poses]).reshape(-1, 12).astype(np.float32)
@@ -441,9 +454,7 @@ class DeviceScenes:
         Sizing the reserve: one extra volume per object whose cloud extents grow from frame to frame (a slot that is outgrown
         is reused by the next volume that fits it), plus one per object that shares its volume and will be changed."""
         self._changing(volumes=True)
-        n = int(np.prod(shape))
-        off = self._slots.offer(self._index(scene, obj), n)
-        return self.pool[off: off + n].view(tuple(int(d) for d in shape))
+        return self._pool_view(self._slots.offer(self._index(scene, obj), int(np.prod(shape))), shape)
 
     def replace_grid(self, scene: int, obj: int, grid: torch.Tensor, origin, delta: float, fit: str = "device") -> None:
         """Give an object a new volume that is already on the device: grid [X,Y,Z] float32 (a view from grid_slot: used in place;
@@ -457,14 +468,16 @@ class DeviceScenes:
         _need(grid, torch.float32, "grid")
         if grid.dim() != 3:
             raise _lib.OmgHipError("grid must be [X,Y,Z]")
-        idx = self._index(scene, obj)
+        self._replace(self._index(scene, obj), grid, origin, delta, fit)
+
+    def _replace(self, idx: int, grid: torch.Tensor, origin, delta: float, fit: str) -> None:
         shape = tuple(int(d) for d in grid.shape)
         n = int(np.prod(shape))
         pend = self._slots.pending.get(idx)
         if pend is not None and n <= pend[1] and grid.data_ptr() == self.pool.data_ptr() + 4 * pend[0]:
             slot = grid  # the view grid_slot handed out, filled in place
         else:
-            slot = self.grid_slot(scene, obj, shape)
+            slot = self._pool_view(self._slots.offer(idx, n), shape)
             slot.copy_(grid)
         rec = self.host_objects[idx]
         rec["grid_offset"] = self._slots.commit(idx)
@@ -485,6 +498,24 @@ class DeviceScenes:
                                                   lo.ctypes.data_as(vp), hi.ctypes.data_as(vp), float(rec["epsilon"]), float(rec["clearance"]),
                                                   _ptr(self._scratch), _stream()), "omgx_fit_influence_region")
 
+    def _offer(self, rows, layouts):
+        """A slot of the pool for the next volume of every record row -> the layouts (origin [3], delta, dims [3]) as surface_records takes
+        them: voxel centres, at the slots' offsets.  A writer refuses what it can refuse BEFORE this, launches into the pool, then _adopt."""
+        return [(origin, delta, "centre", dims, self._slots.offer(i, int(np.prod(dims)))) for i, (origin, delta, dims) in zip(rows, layouts)]
+
+    def _adopt(self, rows, volumes) -> None:  # the offered slots, written by now, become the rows' volumes, fitted on the device
+        for i, (origin, delta, _, dims, off) in zip(rows, volumes):
+            self._replace(i, self._pool_view(off, dims), origin, float(delta), "device")
+
+    def _pool_view(self, off: int, dims) -> torch.Tensor:
+        dims = tuple(int(d) for d in dims)
+        return self.pool[off: off + int(np.prod(dims))].view(dims)
+
+    def volume(self, scene: int, obj: int) -> torch.Tensor:
+        """The object's volume as it lies in the pool: a float32 [X,Y,Z] view, from the host mirror's offset and dims."""
+        rec = self.host_objects[self._index(scene, obj)]
+        return self._pool_view(int(rec["grid_offset"]), rec["dim"])
+
     def surface_records(self, indices):
         """The volumes of the objects `indices` (rows of the record table) as omgx_mesh records for omgx_surface_count /
         omgx_surface_gather: origin = the record's lo, its delta and dim, voxel centres, out_offset = its grid_offset in the pool,
@@ -500,10 +531,7 @@ class DeviceScenes:
         from the pool (ops.surface_meshes: nothing is uploaded but the records) -> (verts [V,3] float64 and faces [F,3] int32 on the
         device, vert_rows [n,2] and face_rows [n,2] = (begin, count) per pair, open_edges [n]; host int64).  Objects that share a
         volume (share_grids) are extracted once and name the same rows.  Coordinates are in the object's own frame, like its volume."""
-        if pairs is None:
-            idx = list(range(len(self.host_objects)))
-        else:
-            idx = [self._index(int(s), int(o)) for s, o in np.asarray(pairs, np.int64).reshape(-1, 2)]
+        idx = list(range(len(self.host_objects))) if pairs is None else self._rows(pairs)
         rec, first, which = self.host_objects, {}, []
         for i in idx:
             key = (int(rec["grid_offset"][i]), rec["dim"][i].tobytes(), rec["lo"][i].tobytes(), rec["delta"][i].tobytes())
@@ -529,26 +557,15 @@ class DeviceScenes:
         the same cameras see it): the pixels it explains are set to 0.0, no information, before the carve, and clear_robot frees
         the arm's nodes between the carve and the transform (_robot_step).  Returns the radius."""
         from . import fusion as _fu
-        self._changing(volumes=True)
-        pairs = np.asarray(pairs, np.int64).reshape(-1, 2)
-        layouts = list(layouts)
-        if len(layouts) != len(pairs) or not len(pairs):
-            raise _lib.OmgHipError(f"{len(pairs)} pairs need as many layouts, and at least one")
-        if len({self._index(int(s), int(o)) for s, o in pairs}) != len(pairs):
-            raise _lib.OmgHipError("a (scene, obj) pair is named twice")
+        rows, layouts = self._writer_rows(pairs, layouts)
         _nonneg_finite(reach=reach)
         # everything that can be refused is refused here, before grid_slot offers a slot: the radius, the layouts, the views
-        _carve_arguments([(origin, delta, "centre", dims) for origin, delta, dims in layouts], views, view_range, depth, band, near, None)
+        _, views = _carve_arguments([(origin, delta, "centre", dims) for origin, delta, dims in layouts], views, view_range, depth, band, near, None)
         radius = _fusion_radius(max(_fu.obstacle_radius(reach, float(delta)) for _, delta, _ in layouts))
-        depth, clear = _robot_step(robot, _masked_depth(depth, free_mask), views, view_range, near)
-        slots, volumes = [], []
-        for (s, o), (origin, delta, dims) in zip(pairs, layouts):
-            slot = self.grid_slot(int(s), int(o), tuple(int(d) for d in dims))
-            slots.append(slot)
-            volumes.append((origin, delta, "centre", dims, (slot.data_ptr() - self.pool.data_ptr()) // 4))
-        fuse_views(volumes, views, view_range, depth, band, near, radius, unknown_occupied, out=self.pool, clear=clear)
-        for (s, o), (origin, delta, _), slot in zip(pairs, layouts, slots):
-            self.replace_grid(int(s), int(o), slot, origin, float(delta), fit="device")
+        depth, clear = _robot_step(robot, _masked_depth(depth, free_mask), views, None, near)
+        volumes = self._offer(rows, layouts)
+        fuse_views(volumes, views, None, depth, band, near, radius, unknown_occupied, out=self.pool, clear=clear)
+        self._adopt(rows, volumes)
         return radius
 
     def integrate_obstacles(self, pairs, tsdf_volumes: "TsdfVolumes | None", depth: torch.Tensor, views, view_range, layouts, trunc: float,
@@ -565,19 +582,13 @@ class DeviceScenes:
         grid_slot's slots, which become the objects' volumes through replace_grid(fit="device").  Everything that can be
         refused is refused before a slot is offered.  Returns (radius, the TsdfVolumes)."""
         from . import fusion as _fu
-        self._changing(volumes=True)
-        pairs = np.asarray(pairs, np.int64).reshape(-1, 2)
-        layouts = list(layouts)
-        if len(layouts) != len(pairs) or not len(pairs):
-            raise _lib.OmgHipError(f"{len(pairs)} pairs need as many layouts, and at least one")
-        if len({self._index(int(s), int(o)) for s, o in pairs}) != len(pairs):
-            raise _lib.OmgHipError("a (scene, obj) pair is named twice")
+        rows, layouts = self._writer_rows(pairs, layouts)
         _nonneg_finite(reach=reach)
         min_weight = _tsdf_positive("min_weight", min_weight)
         volumes = [(origin, delta, "centre", dims) for origin, delta, dims in layouts]
-        _, _, _, _, trunc, wmax = _tsdf_arguments(volumes, views, view_range, depth, trunc, near, weights, wmax, None)
+        _, views, _, trunc, wmax = _tsdf_arguments(volumes, views, view_range, depth, trunc, near, weights, wmax, None)
         radius = _fusion_radius(max(_fu.obstacle_radius(reach, float(delta)) for _, delta, _ in layouts))
-        depth, clear = _robot_step(robot, _masked_depth(depth, free_mask), views, view_range, near)
+        depth, clear = _robot_step(robot, _masked_depth(depth, free_mask), views, None, near)
         if depth.device != self.pool.device:
             raise _lib.OmgHipError(f"depth must be on {self.pool.device}, got {depth.device}")
         if tsdf_volumes is None:
@@ -590,12 +601,10 @@ class DeviceScenes:
                 raise _lib.OmgHipError("tsdf_volumes were started with other layouts, or another trunc, near or wmax")
             if tsdf_volumes.device != depth.device:
                 raise _lib.OmgHipError(f"tsdf_volumes are on {tsdf_volumes.device}, depth on {depth.device}")
-        slots = [self.grid_slot(int(s), int(o), tuple(int(d) for d in dims)) for (s, o), (_, _, dims) in zip(pairs, layouts)]
-        tsdf_volumes.integrate(depth, views, view_range, weights)
-        tsdf_volumes.signed(radius, unknown_occupied, min_weight, out=self.pool, offsets=[(slot.data_ptr() - self.pool.data_ptr()) // 4 for slot in slots],
-                            clear=clear)
-        for (s, o), (origin, delta, _), slot in zip(pairs, layouts, slots):
-            self.replace_grid(int(s), int(o), slot, origin, float(delta), fit="device")
+        placed = self._offer(rows, layouts)
+        tsdf_volumes.integrate(depth, views, None, weights)
+        tsdf_volumes.signed(radius, unknown_occupied, min_weight, out=self.pool, offsets=[v[4] for v in placed], clear=clear)
+        self._adopt(rows, placed)
         return radius, tsdf_volumes
 
     def segment_obstacles(self, target_pairs, obstacle_pairs, depth: torch.Tensor, views, view_range, layouts, band: float, near: float,
@@ -619,38 +628,32 @@ class DeviceScenes:
         seeds = np.asarray(seeds, np.float64).reshape(-1, 3)
         if not n or len(tp) != n or len(op) != n or len(seeds) != n:
             raise _lib.OmgHipError(f"{n} layouts need as many target pairs, obstacle pairs and seeds, and at least one")
-        if len({self._index(int(s), int(o)) for s, o in np.concatenate([tp, op])}) != 2 * n:
-            raise _lib.OmgHipError("a (scene, obj) pair is named twice")
+        rows = self._rows(np.concatenate([tp, op]), unique=_lib.OmgHipError)  # the targets' rows, then the obstacles'
         _nonneg_finite(reach=reach)
         if not np.isfinite(seeds).all() or int(min_nodes) < 1 or (margin is not None and int(margin) < 0):
             raise _lib.OmgHipError("seeds must be finite, min_nodes at least 1 and margin not negative")
         _segment_arguments(1, connectivity)
         volumes = [(origin, delta, "centre", dims) for origin, delta, dims in layouts]
-        _carve_arguments(volumes, views, view_range, depth, band, near, None)
+        batch, views = _carve_arguments(volumes, views, view_range, depth, band, near, None)  # (one batch of each for every stage)
         radius = _fusion_radius(max(_fu.obstacle_radius(reach, float(delta)) for _, delta, _ in layouts))
         margin = radius + 1 if margin is None else int(margin)
-        depth, clear = _robot_step(robot, _masked_depth(depth, free_mask), views, view_range, near)
-        state, begin = carve_views(volumes, views, view_range, depth, band, near)
+        depth, clear = _robot_step(robot, _masked_depth(depth, free_mask), views, None, near)
+        state, _ = carve_views(batch, views, None, depth, band, near)
         if clear is not None:
-            clear(state, begin, volumes)
-        comps = label_components(state, begin, volumes, 1, connectivity)
+            clear(state, None, batch)
+        comps = label_components(state, None, batch, 1, connectivity)
         try:  # (a scene without a component of min_nodes nodes is refused here: no slot has been offered yet)
             ranks = [_sg.pick_component(comps.of(m), _sg.point_to_index(volumes[m], seeds[m]), min_nodes) for m in range(n)]
         except ValueError as e:
             raise _lib.OmgHipError(str(e)) from None
-        rows = [int(comps.comp_begin[m]) + ranks[m] for m in range(n)]
-        crops = [_sg.crop_layout(volumes[m], comps.records[rows[m]], margin) for m in range(n)]
-        outs, picks, slots = [], [], []
-        for m in range(n):
-            for (s, o), (origin, delta, dims, first), mode in ((tp[m], crops[m], 0), (op[m], tuple(layouts[m]) + ((0, 0, 0),), 1)):
-                slot = self.grid_slot(int(s), int(o), tuple(int(d) for d in dims))
-                slots.append((int(s), int(o), slot, origin, float(delta)))
-                outs.append((origin, delta, "centre", dims, (slot.data_ptr() - self.pool.data_ptr()) // 4))
-                picks.append((m,) + tuple(first) + (rows[m], mode, 0, 0))
+        chosen = [int(comps.comp_begin[m]) + ranks[m] for m in range(n)]
+        crops = [c for m in range(n) for c in (_sg.crop_layout(layouts[m], comps.records[chosen[m]], margin), tuple(layouts[m]) + ((0, 0, 0),))]
+        picks = [(k // 2,) + tuple(first) + (chosen[k // 2], k % 2, 0, 0) for k, (_, _, _, first) in enumerate(crops)]
+        rows = [r for both in zip(rows[:n], rows[n:]) for r in both]  # (per scene: the target's crop in mode 0, then the whole layout in mode 1)
+        outs = self._offer(rows, [c[:3] for c in crops])
         component_volumes(state, comps, picks, outs, radius, True, out=self.pool)
-        for s, o, slot, origin, delta in slots:
-            self.replace_grid(s, o, slot, origin, delta, fit="device")
-        return radius, comps.records[rows].copy(), comps
+        self._adopt(rows, outs)
+        return radius, comps.records[chosen].copy(), comps
 
     def plane_obstacles(self, pairs, planes, layouts) -> None:
         """The half-space volumes of fitted supports as the volumes of the (scene, obj) `pairs`, written straight into the pool:
@@ -659,22 +662,11 @@ class DeviceScenes:
         layouts: one (origin [3], delta, dims [3]) per pair, voxel centres, in the object's frame.  grid_slot, ONE launch
         (plane_volumes), then replace_grid(fit="device") object by object, as fuse_obstacles does it; everything that can be
         refused is refused before a slot is offered."""
-        self._changing(volumes=True)
-        pairs = np.asarray(pairs, np.int64).reshape(-1, 2)
-        layouts = list(layouts)
-        if len(layouts) != len(pairs) or not len(pairs):
-            raise _lib.OmgHipError(f"{len(pairs)} pairs need as many layouts, and at least one")
-        if len({self._index(int(s), int(o)) for s, o in pairs}) != len(pairs):
-            raise _lib.OmgHipError("a (scene, obj) pair is named twice")
+        rows, layouts = self._writer_rows(pairs, layouts)
         _plane_volume_arguments([(origin, delta, "centre", dims) for origin, delta, dims in layouts], planes)
-        slots, volumes = [], []
-        for (s, o), (origin, delta, dims) in zip(pairs, layouts):
-            slot = self.grid_slot(int(s), int(o), tuple(int(d) for d in dims))
-            slots.append(slot)
-            volumes.append((origin, delta, "centre", dims, (slot.data_ptr() - self.pool.data_ptr()) // 4))
+        volumes = self._offer(rows, layouts)
         plane_volumes(volumes, planes, out=self.pool)
-        for (s, o), (origin, delta, _), slot in zip(pairs, layouts, slots):
-            self.replace_grid(int(s), int(o), slot, origin, float(delta), fit="device")
+        self._adopt(rows, volumes)
 
     def sync_host(self) -> np.ndarray:
         """Bring the host mirror of the records up to date with the device (one small copy; tests, oracle comparisons)."""
@@ -1447,7 +1439,25 @@ def surface_mesh(grid: torch.Tensor, origin, delta, sample: str = "centre", leve
     return verts, faces, int(open_edges[0])
 
 
-class _VolumeBatch:
+class _HostBatch:
+    """Host arrays of a launch that go to a device once each, when a launch first needs them there.  _caches: one dict per array,
+    device -> upload; on(dev) names the device that the arguments point into."""
+    _dev = None
+
+    def on(self, dev):
+        self._dev = torch.device(dev)
+        return self
+
+    def _device(self, cache, host):  # the pointer to `host` on the device in use; None for an empty array, which is not uploaded
+        if len(host) and self._dev not in cache:
+            cache[self._dev] = _upload(host, self._dev)
+        return _ptr(cache.get(self._dev))
+
+    def release(self, *scratch) -> None:  # after a launch: the uploads, and the caller's scratch tensors, are in use by the current stream
+        _release(self._dev, *(cache.get(self._dev) for cache in self._caches), *scratch)
+
+
+class _VolumeBatch(_HostBatch):
     """The volumes of a launch over a ragged batch, checked on the host before any tensor is touched: rec (omgx_mesh records), nodes
     (int64 [M]), begin (state_begin int64 [M]) and M.  volumes: what surface_records takes (the prefix table is the same: 256 nodes
     per workgroup), or [] for an empty launch; a layout without its fifth field, the element offset in the pool, lies behind the
@@ -1473,7 +1483,7 @@ class _VolumeBatch:
         self.begin = np.cumsum(self.nodes) - self.nodes if state_begin is None else np.ascontiguousarray(state_begin, np.int64).reshape(-1)
         if len(self.begin) != self.M:
             raise _lib.OmgHipError(f"state_begin must have one offset per volume ({self.M}), got {len(self.begin)}")
-        self._d_rec, self._d_begin, self._dev = {}, {} if like is None else like._d_begin, None  # uploads per device, the device in use
+        self._caches = self._d_rec, self._d_begin = {}, {} if like is None else like._d_begin
 
     @classmethod
     def of(cls, volumes, state_begin=None) -> "_VolumeBatch":
@@ -1488,16 +1498,6 @@ class _VolumeBatch:
         """Elements of the pool that the volumes reach to, 1 without any: what sizes a new pool."""
         return max([int(r.out_offset) + int(n) for r, n in zip(self.rec, self.nodes)], default=1)
 
-    def on(self, dev) -> "_VolumeBatch":
-        """The device that the arguments below point into: the records and state_begin are uploaded when first asked for there."""
-        self._dev = torch.device(dev)
-        return self
-
-    def _device(self, cache, host):
-        if self.M and self._dev not in cache:
-            cache[self._dev] = _upload(host, self._dev)
-        return _ptr(cache.get(self._dev))
-
     def host_args(self):
         """(h_volumes, num_volumes) of an entry point; no pointer for an empty batch."""
         return (C.cast(self.rec, C.c_void_p) if self.M else None, self.M)
@@ -1510,15 +1510,40 @@ class _VolumeBatch:
         """(state_begin, h_state_begin) of an entry point."""
         return (self._device(self._d_begin, self.begin), C.c_void_p(self.begin.ctypes.data) if self.M else None)
 
-    def release(self, *scratch) -> None:
-        """After the last launch: the uploads, and the caller's scratch tensors, are in use by the current stream."""
-        _release(self._dev, self._d_rec.get(self._dev), self._d_begin.get(self._dev), *scratch)
 
+class _ViewBatch(_HostBatch):
+    """The views of a launch, checked on the host before any tensor is touched: h_views (float64 [V,16], fusion.view_rows), h_range
+    (view_range, int32 [M,2]: first view and count per volume; set by of), V and the images' (H, W).  depth is only asked for its shape."""
 
-def _fusion_volumes(volumes, state_begin):
-    """(records, node counts, state_begin int64 [M]) of a fusion launch: the host half of a _VolumeBatch."""
-    batch = _VolumeBatch(volumes, state_begin)
-    return batch.rec, batch.nodes, batch.begin
+    def __init__(self, views, depth):
+        if not isinstance(depth, torch.Tensor) or depth.dim() != 3:
+            raise _lib.OmgHipError("depth must be a tensor [V,H,W]")
+        self.V, self.H, self.W = (int(d) for d in depth.shape)
+        self.h_views, self.h_range = np.ascontiguousarray(views, np.float64).reshape(-1, 16), None
+        if len(self.h_views) != self.V:
+            raise _lib.OmgHipError(f"{len(self.h_views)} views but {self.V} images")
+        if not np.isfinite(self.h_views).all() or (self.h_views[:, :2] == 0).any():
+            raise _lib.OmgHipError("a view is not finite or has a focal length of zero")
+        self._caches = self._d_views, self._d_range = {}, {}
+
+    @classmethod
+    def of(cls, views, view_range, depth, M: int) -> "_ViewBatch":
+        """The batch of views [V,16] and view_range [M,2] for depth [V,H,W] and M volumes.  A batch in the place of `views` passes
+        through with its ranges and its uploads (view_range is not read), if its V, H, W and M are the call's."""
+        self = views if isinstance(views, cls) else cls(views, depth)
+        if self.h_range is None:
+            h_range = np.asarray(view_range, np.int64).reshape(-1, 2)
+            if len(h_range) != M or (h_range < 0).any() or (h_range.sum(1) > self.V).any():
+                raise _lib.OmgHipError(f"view_range must be [{M},2] inside [0, {self.V}]")
+            self.h_range = np.ascontiguousarray(h_range, np.int32)
+        if len(self.h_range) != M or not isinstance(depth, torch.Tensor) or tuple(depth.shape) != (self.V, self.H, self.W):
+            raise _lib.OmgHipError(f"these views are for {len(self.h_range)} volumes and depth [{self.V},{self.H},{self.W}]")
+        return self
+
+    def view_args(self):
+        """(views, h_views, num_views, view_range, h_view_range) of an entry point; no pointer for an empty array."""
+        return (self._device(self._d_views, self.h_views), C.c_void_p(self.h_views.ctypes.data) if self.V else None, self.V,
+                self._device(self._d_range, self.h_range), C.c_void_p(self.h_range.ctypes.data) if len(self.h_range) else None)
 
 
 def _upload(a: np.ndarray, dev) -> torch.Tensor:
@@ -1545,23 +1570,13 @@ def _fusion_radius(radius) -> int:
 
 
 def _carve_arguments(volumes, views, view_range, depth, band, near, state_begin):
-    """The host side of a carve launch, checked before anything touches the device -> (the _VolumeBatch, views
-    float64 [V,16], view_range int32 [M,2]).  depth is only asked for its shape."""
-    if not isinstance(depth, torch.Tensor) or depth.dim() != 3:
-        raise _lib.OmgHipError("depth must be a tensor [V,H,W]")
-    V = int(depth.shape[0])
-    h_views = np.ascontiguousarray(views, np.float64).reshape(-1, 16)
-    if len(h_views) != V:
-        raise _lib.OmgHipError(f"{len(h_views)} views but {V} images")
-    if not np.isfinite(h_views).all() or (h_views[:, :2] == 0).any():
-        raise _lib.OmgHipError("a view is not finite or has a focal length of zero")
+    """The host side of a carve launch, checked before anything touches the device, in this order: depth's shape and the views,
+    band and near, the volumes, view_range -> (the _VolumeBatch, the _ViewBatch).  Batches pass through."""
+    views = views if isinstance(views, _ViewBatch) else _ViewBatch(views, depth)
     if not (np.isfinite(float(band)) and np.isfinite(float(near))):
         raise _lib.OmgHipError("band and near must be finite")
     batch = _VolumeBatch.of(volumes, state_begin)
-    h_range = np.asarray(view_range, np.int64).reshape(-1, 2)
-    if len(h_range) != batch.M or (h_range < 0).any() or (h_range.sum(1) > V).any():
-        raise _lib.OmgHipError(f"view_range must be [{batch.M},2] inside [0, {V}]")
-    return batch, h_views, np.ascontiguousarray(h_range, np.int32)
+    return batch, _ViewBatch.of(views, view_range, depth, batch.M)
 
 
 def carve_views(volumes, views, view_range, depth: torch.Tensor, band: float, near: float, state: "torch.Tensor | None" = None,
@@ -1569,29 +1584,26 @@ def carve_views(volumes, views, view_range, depth: torch.Tensor, band: float, ne
     """The states (0 free, 1 surface, 2 unknown) of the nodes of M volumes from V depth views in ONE launch (omgx_carve_views;
     fusion.carve_views is the specification: the same bytes) -> (state uint8 on the device, state_begin [M] int64 numpy): volume
     m's node L at state[state_begin[m] + L].  volumes: what surface_records takes (the pool offset is not used here); views
-    [V,16] float64 on the host (fusion.view_rows); view_range [M,2] host integers (first view, count; ranges may overlap);
+    [V,16] float64 on the host (fusion.view_rows; or a _ViewBatch, which brings its view_range); view_range [M,2] host integers (first view, count; ranges may overlap);
     depth [V,H,W]: a contiguous float64 device tensor (render_depth's t), +inf as background.  state / state_begin: None -> a new
     buffer that reaches to the end of the last volume, filled with 2 (unknown) where no volume lies, as the specification's; or
     the caller's, written IN PLACE (elements outside every range are not touched).
     merge: the flags start from what `state` holds, so that carving the views A and merging the views B equals carving both.
     The host arguments are checked first, then the tensors: a refused call has touched nothing."""
     from . import fusion as _fu
-    batch, h_views, h_range = _carve_arguments(volumes, views, view_range, depth, band, near, state_begin)
+    batch, vb = _carve_arguments(volumes, views, view_range, depth, band, near, state_begin)
     if state is None and merge:
         raise _lib.OmgHipError("merge needs the state of an earlier call")
     _need(depth, torch.float64, "depth")
-    dev, vp = depth.device, C.c_void_p
-    (V, H, W), M = (int(d) for d in depth.shape), batch.M
+    dev = depth.device
     if state is None:
         state = torch.full((max(batch.end(), 1),), _fu.UNKNOWN, dtype=torch.uint8, device=dev)
     _tensor(state, "state", torch.uint8, None, dev)
     with torch.cuda.device(dev):
-        d_views, d_range = _upload(h_views, dev), _upload(h_range, dev)
-        check(_lib.lib().omgx_carve_views(*batch.on(dev).volume_args(), _ptr(d_views) if V else None, vp(h_views.ctypes.data) if V else None, V,
-                                          _ptr(d_range) if M else None, vp(h_range.ctypes.data) if M else None, *batch.begin_args(),
-                                          _ptr(depth) if V else None, H, W, float(band), float(near), int(bool(merge)), _ptr(state),
-                                          int(state.numel()), _stream()), "omgx_carve_views")
-        batch.release(d_views, d_range)
+        check(_lib.lib().omgx_carve_views(*batch.on(dev).volume_args(), *vb.on(dev).view_args(), *batch.begin_args(), _ptr(depth) if vb.V else None,
+                                          vb.H, vb.W, float(band), float(near), int(bool(merge)), _ptr(state), int(state.numel()), _stream()),
+              "omgx_carve_views")
+        batch.release(), vb.release()
     return state, batch.begin
 
 
@@ -1624,10 +1636,11 @@ def fuse_views(volumes, views, view_range, depth: torch.Tensor, band: float, nea
     as distance_transform returns it.  The radius is checked before the carve launch.  clear: None, or a step between the two
     halves, clear(state, state_begin, volumes), that changes the state bytes in place (_robot_step)."""
     radius = _fusion_radius(radius)
-    state, begin = carve_views(volumes, views, view_range, depth, band, near)
+    batch, vb = _carve_arguments(volumes, views, view_range, depth, band, near, None)  # (one batch of each: uploaded once for all stages)
+    state, _ = carve_views(batch, vb, None, depth, band, near)
     if clear is not None:
-        clear(state, begin, volumes)
-    return distance_transform(state, begin, volumes, radius, unknown_occupied, out)
+        clear(state, None, batch)
+    return distance_transform(state, None, batch, radius, unknown_occupied, out)
 
 
 def _tsdf_positive(name: str, x, may_be_inf: bool = False) -> float:
@@ -1642,13 +1655,13 @@ def _tsdf_arguments(volumes, views, view_range, depth, trunc, near, weights, wma
     """The host side of an integrate launch, checked before anything touches the device: _carve_arguments' result and
     (weights float64 [V] or None, trunc, wmax)."""
     trunc, wmax = _tsdf_positive("trunc", trunc), _tsdf_positive("wmax", wmax, True)
-    batch, h_views, h_range = _carve_arguments(volumes, views, view_range, depth, 0.0, near, state_begin)
+    batch, vb = _carve_arguments(volumes, views, view_range, depth, 0.0, near, state_begin)
     h_w = None
     if weights is not None:
         h_w = np.ascontiguousarray(weights, np.float64).reshape(-1)
-        if len(h_w) != len(h_views) or not np.isfinite(h_w).all() or (h_w < 0).any():
-            raise _lib.OmgHipError(f"weights must be {len(h_views)} finite numbers >= 0")
-    return batch, h_views, h_range, h_w, trunc, wmax
+        if len(h_w) != vb.V or not np.isfinite(h_w).all() or (h_w < 0).any():
+            raise _lib.OmgHipError(f"weights must be {vb.V} finite numbers >= 0")
+    return batch, vb, h_w, trunc, wmax
 
 
 def _tsdf_pair(tsdf, weight, dev=None):
@@ -1668,27 +1681,23 @@ def tsdf_integrate(volumes, views, view_range, depth: torch.Tensor, trunc: float
     tsdf / weight: None -> new buffers that reach to the end of the last volume, zero where no volume lies; or the caller's,
     written IN PLACE.  merge: the pairs start from what the buffers hold (a further frame), otherwise from (0, 0).
     The host arguments are checked first, then the tensors: a refused call has touched nothing."""
-    batch, h_views, h_range, h_w, trunc, wmax = _tsdf_arguments(volumes, views, view_range, depth, trunc, near, weights, wmax, state_begin)
+    batch, vb, h_w, trunc, wmax = _tsdf_arguments(volumes, views, view_range, depth, trunc, near, weights, wmax, state_begin)
     if (tsdf is None) != (weight is None):
         raise _lib.OmgHipError("tsdf and weight come together")
     if tsdf is None and merge:
         raise _lib.OmgHipError("merge needs the pairs of an earlier call")
     _need(depth, torch.float64, "depth")
-    dev, vp = depth.device, C.c_void_p
-    (V, H, W), M = (int(d) for d in depth.shape), batch.M
+    dev, V = depth.device, vb.V
     if tsdf is None:
         n = max(batch.end(), 1)
         tsdf, weight = torch.zeros(n, dtype=torch.float32, device=dev), torch.zeros(n, dtype=torch.float32, device=dev)
     _tsdf_pair(tsdf, weight, dev)
     with torch.cuda.device(dev):
-        d_views, d_range = _upload(h_views, dev), _upload(h_range, dev)
         d_w = _upload(h_w, dev) if h_w is not None and V else None
-        check(_lib.lib().omgx_tsdf_integrate(*batch.on(dev).volume_args(), _ptr(d_views) if V else None, vp(h_views.ctypes.data) if V else None, V,
-                                             _ptr(d_range) if M else None, vp(h_range.ctypes.data) if M else None, *batch.begin_args(),
-                                             _ptr(depth) if V else None, H, W, _ptr(d_w), vp(h_w.ctypes.data) if d_w is not None else None, trunc,
-                                             float(near), wmax, int(bool(merge)), _ptr(tsdf), _ptr(weight), int(tsdf.numel()), _stream()),
-              "omgx_tsdf_integrate")
-        batch.release(d_views, d_range, d_w)
+        check(_lib.lib().omgx_tsdf_integrate(*batch.on(dev).volume_args(), *vb.on(dev).view_args(), *batch.begin_args(), _ptr(depth) if V else None,
+                                             vb.H, vb.W, _ptr(d_w), C.c_void_p(h_w.ctypes.data) if d_w is not None else None, trunc, float(near), wmax,
+                                             int(bool(merge)), _ptr(tsdf), _ptr(weight), int(tsdf.numel()), _stream()), "omgx_tsdf_integrate")
+        batch.release(d_w), vb.release()
     return tsdf, weight, batch.begin
 
 
@@ -1805,7 +1814,7 @@ class Components:
     def __init__(self, labels, counts, comp_begin, records, d_records, rec, begin, select, connectivity):
         self.labels, self.counts, self.comp_begin, self.records, self.d_records = labels, counts, comp_begin, records, d_records
         self.rec, self.begin, self.select, self.connectivity = rec, begin, select, connectivity
-        self._batch = None  # label_components': its uploads serve component_states too
+        self._batch = self._d_comp = None  # label_components' batch and comp_begin on the device: they serve component_states too
 
     def of(self, m: int) -> np.ndarray:
         """The records of volume m, in rank order."""
@@ -1853,7 +1862,7 @@ def label_components(state: torch.Tensor, state_begin, volumes, select: int = 1,
         records = d_records.cpu().numpy()
         batch.release(ws, d_comp)
     comps = Components(labels, h_counts, comp_begin, records, d_records, rec, begin, select, connectivity)
-    comps._batch = batch
+    comps._batch, comps._d_comp = batch, d_comp
     return comps
 
 
@@ -1892,7 +1901,7 @@ def component_states(state: torch.Tensor, components: Components, picks, out_vol
         if K == 0:
             return out, ob
         src, comp_begin = (components._batch or _VolumeBatch(components.rec, components.begin)).on(dev), components.comp_begin
-        d_comp, d_picks = _upload(comp_begin, dev), _upload(h_picks, dev)
+        d_comp, d_picks = _upload(comp_begin, dev) if components._d_comp is None else components._d_comp, _upload(h_picks, dev)
         check(_lib.lib().omgx_component_states(_ptr(state), int(state.numel()), *src.begin_args(), *src.volume_args(), _ptr(components.labels),
                                                _ptr(d_comp), vp(comp_begin.ctypes.data), _ptr(components.d_records), int(components.d_records.shape[0]),
                                                _ptr(d_picks), vp(h_picks.ctypes.data), *outs.on(dev).volume_args(), *outs.begin_args(), _ptr(out),
@@ -1907,8 +1916,9 @@ def component_volumes(state: torch.Tensor, components: Components, picks, out_vo
     (output k at the element offset of its layout: the SDF pool, for instance).  The radius and the picks are checked before
     the first launch."""
     radius = _fusion_radius(radius)
-    cropped, ob = component_states(state, components, picks, out_volumes)
-    return distance_transform(cropped, ob, out_volumes, radius, unknown_occupied, out)
+    _, outs = _component_arguments(components, picks, out_volumes, None)  # (one batch of the outputs for both stages)
+    cropped, _ = component_states(state, components, picks, outs)
+    return distance_transform(cropped, None, outs, radius, unknown_occupied, out)
 
 
 class PlaneFit:
@@ -2353,9 +2363,8 @@ def register_clouds(scenes: DeviceScenes, pairs, poses0, points: torch.Tensor, r
         raise _lib.OmgHipError(f"stride must be >= 1 and max_passes in [0, {_reg.MAX_PASSES}], got {stride} and {max_passes}")
     if not (np.isfinite(float(trunc)) and float(trunc) > 0 and np.isfinite(float(lambda0)) and float(lambda0) > 0):
         raise _lib.OmgHipError("trunc and lambda0 must be finite and positive")
-    pairs = np.asarray(pairs, np.int64).reshape(-1, 2)
-    M = len(pairs)
-    h_index = np.ascontiguousarray([scenes._index(int(s), int(o)) for s, o in pairs], np.int32).reshape(M)
+    h_index = np.ascontiguousarray(scenes._rows(pairs), np.int32)
+    M = len(h_index)
     h_ranges = np.asarray(ranges, np.int64).reshape(-1, 2)
     if len(h_ranges) != M:
         raise _lib.OmgHipError(f"ranges must be [{M},2], got {h_ranges.shape}")
@@ -2544,12 +2553,11 @@ def clear_robot(state: torch.Tensor, state_begin, volumes, views, view_range, de
     the images BEFORE filter_depth); t_near [V,H,W] and cam_spheres [V,N,4]: render_spheres' for the same views.  h_cam_spheres:
     cam_spheres on the host, if the caller has them; otherwise they are downloaded once for the checks.  cull=False stages every
     sphere for every run of nodes: the same bytes."""
-    batch, h_views, h_range = _carve_arguments(volumes, views, view_range, depth, 0.0, near, state_begin)
+    batch, vb = _carve_arguments(volumes, views, view_range, depth, 0.0, near, state_begin)
     if not np.isfinite(float(tol)):
         raise _lib.OmgHipError("near and tol must be finite")
     _need(depth, torch.float64, "depth")
-    dev, vp = depth.device, C.c_void_p
-    (V, H, W), M = (int(d) for d in depth.shape), batch.M
+    dev, vp, V, H, W = depth.device, C.c_void_p, vb.V, vb.H, vb.W
     _tensor(t_near, "t_near", torch.float64, (V, H, W), dev), _tensor(cam_spheres, "cam_spheres", torch.float64, (V, None, 4), dev)
     N = int(cam_spheres.shape[1])
     h_sph = np.ascontiguousarray(cam_spheres.cpu().numpy() if h_cam_spheres is None else h_cam_spheres, np.float64)
@@ -2557,13 +2565,11 @@ def clear_robot(state: torch.Tensor, state_begin, volumes, views, view_range, de
         raise _lib.OmgHipError("a sphere is not finite or has a negative radius")
     _tensor(state, "state", torch.uint8, None, dev)
     with torch.cuda.device(dev):
-        d_views, d_range = _upload(h_views, dev), _upload(h_range, dev)
-        check(_lib.lib().omgx_clear_robot(*batch.on(dev).volume_args(), _ptr(d_views) if V else None, vp(h_views.ctypes.data) if V else None, V,
-                                          _ptr(d_range) if M else None, vp(h_range.ctypes.data) if M else None, *batch.begin_args(),
-                                          _ptr(depth) if V else None, _ptr(t_near) if V else None, H, W, _ptr(cam_spheres) if V and N else None,
+        check(_lib.lib().omgx_clear_robot(*batch.on(dev).volume_args(), *vb.on(dev).view_args(), *batch.begin_args(), _ptr(depth) if V else None,
+                                          _ptr(t_near) if V else None, H, W, _ptr(cam_spheres) if V and N else None,
                                           vp(h_sph.ctypes.data) if V and N else None, N, float(near), float(tol), int(bool(cull)), _ptr(state),
                                           int(state.numel()), _stream()), "omgx_clear_robot")
-        batch.release(d_views, d_range)
+        batch.release(), vb.release()
     return state
 
 

@@ -152,13 +152,11 @@ def plan_observed(model, scenes, obs, obstacles, layouts, band: float, near: flo
     table = ops.DeviceScenes.from_scenes(scenes, cfg.layer_kwargs(), device=dev, share_grids=False, reserve_voxels=reserve)
     radius, records, _ = obs.segment_obstacles(table, tp, op, layouts, band, near, reach, seeds, min_nodes, connectivity, margin, free_mask,
                                                 robot=robot)
-    host = table.sync_host()
-    for s, (origin, delta, dims) in enumerate(layouts):
+    for s, (origin, delta, _) in enumerate(layouts):
         crop = _sg.crop_layout((origin, delta), records[s], radius + 1 if margin is None else int(margin))
         # (origins and delta as the host knows them in float64, not the records' float32 limits)
-        for (_, o), (org, n) in ((tp[s], (crop[0], crop[2])), (op[s], (np.asarray(origin, np.float64), tuple(int(d) for d in dims)))):
-            off = int(host[table._index(s, o)]["grid_offset"])
-            scenes[s].objects[o].sdf = _sc.SdfGrid(table.pool[off: off + int(np.prod(n))].view(n).cpu().numpy(), org, float(delta))
+        for (_, o), org in ((tp[s], crop[0]), (op[s], np.asarray(origin, np.float64))):
+            scenes[s].objects[o].sdf = _sc.SdfGrid(table.volume(s, o).cpu().numpy(), org, float(delta))
     plans, sets, meshes = plan_volumes(model, scenes, starts, cfg, device=device, **plan_kwargs)
     return plans, sets, meshes, records
 
@@ -177,16 +175,13 @@ def plan_on_unknown_support(model, scenes, obs, obstacles, supports, layouts, su
     -> (GraspPlans, grasp poses, meshes, the chosen records [S,8], the ops.PlaneFit)."""
     from . import scenes as _sc
     dev = torch.device(device)
-    S = len(scenes)
     sp = [(s, int(o)) for s, o in enumerate(supports)]
     fit, mask = obs.fit_supports(triples, tol, up_world, cos_min, refine, skip=None if robot is None else robot.mask)
     table = ops.DeviceScenes.from_scenes(scenes, cfg.layer_kwargs(), device=dev, share_grids=False,
                                          reserve_voxels=sum(int(np.prod(dims)) for _, _, dims in support_layouts))
     table.plane_obstacles(sp, obs.support_planes(table, sp, fit), support_layouts)
-    host = table.sync_host()
-    for (s, o), (origin, delta, dims) in zip(sp, support_layouts):
-        off, n = int(host[table._index(s, o)]["grid_offset"]), tuple(int(d) for d in dims)
-        scenes[s].objects[o].sdf = _sc.SdfGrid(table.pool[off: off + int(np.prod(n))].view(n).cpu().numpy(), np.asarray(origin, np.float64), float(delta))
+    for (s, o), (origin, delta, _) in zip(sp, support_layouts):
+        scenes[s].objects[o].sdf = _sc.SdfGrid(table.volume(s, o).cpu().numpy(), np.asarray(origin, np.float64), float(delta))
     plans, sets, meshes, records = plan_observed(model, scenes, obs, obstacles, layouts, band, near, reach, seeds, min_nodes, starts, cfg, connectivity,
                                                  margin, free_mask=mask, device=device, robot=robot, **plan_kwargs)
     return plans, sets, meshes, records, fit

@@ -475,14 +475,15 @@ def test_wrapper_checks_without_gpu():
     with pytest.raises(E, match="dims >= 1"):
         ops.distance_transform(state, None, [vols[0][:3] + ((4, 4, -1), 0)], 3)
     # layouts without an offset lie back to back; the states do by default
-    rec, nodes, begin = ops._fusion_volumes([((0.0, 0.0, 0.0), 0.01, "centre", (2, 2, 2)), ((0.0, 0.0, 0.0), 0.01, "node", (1, 2, 3)),
-                                             ((0.0, 0.0, 0.0), 0.01, "node", (3, 1, 1), 100)], None)
-    assert [r.out_offset for r in rec] == [0, 8, 100] and nodes.tolist() == [8, 6, 3] and begin.tolist() == [0, 8, 14]
-    assert [len(x) for x in ops._fusion_volumes([], None)] == [0, 0, 0]
+    b = ops._VolumeBatch([((0.0, 0.0, 0.0), 0.01, "centre", (2, 2, 2)), ((0.0, 0.0, 0.0), 0.01, "node", (1, 2, 3)),
+                          ((0.0, 0.0, 0.0), 0.01, "node", (3, 1, 1), 100)], None)
+    assert [r.out_offset for r in b.rec] == [0, 8, 100] and b.nodes.tolist() == [8, 6, 3] and b.begin.tolist() == [0, 8, 14]
+    b = ops._VolumeBatch([], None)
+    assert [len(x) for x in (b.rec, b.nodes, b.begin)] == [0, 0, 0]
     with pytest.raises(E):
-        ops._fusion_volumes([((0.0, 0.0, 0.0), 0.01, "centre")], None)
+        ops._VolumeBatch([((0.0, 0.0, 0.0), 0.01, "centre")], None)
     with pytest.raises(E, match="one offset per volume"):
-        ops._fusion_volumes(vols, [0, 1])
+        ops._VolumeBatch(vols, [0, 1])
 
 
 # ---------------------------------------------------------------------------------------------------------------------

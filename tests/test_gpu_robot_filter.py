@@ -170,6 +170,14 @@ class _Panda:
         st = fusion.carve_views([RC.PANDA_VOLUME], table_views, [(0, 1)], depth, FC.BAND, FC.NEAR)
         return rf.clear_states(st, [RC.PANDA_VOLUME], table_views, [(0, 1)], self.t_arm, FC.NEAR, self.t_near, self.cs, RC.PANDA_TOL) if filtered else st
 
+    def spec_fused(self, table_views, radius):
+        """The specification's volume of fuse_obstacles(robot=) for the object at RC.PANDA_POSE: computed once for the tests that read it."""
+        from omg_planner_amd import fusion
+        if getattr(self, "_fused", None) is None:
+            self._fused = (table_views.copy(), radius, fusion.signed_volume(self.spec_states(table_views).reshape(32, 32, 32), 0.01, radius, True))
+        assert np.array_equal(self._fused[0], table_views) and self._fused[1] == radius
+        return self._fused[2]
+
 
 @pytest.fixture(scope="module")
 def panda(dev):
@@ -235,7 +243,7 @@ def test_fuse_obstacles_with_the_arm_in_the_image(dev, panda):
     radius = panda.obs.fuse_obstacles(table, pairs, layouts, FC.BAND, FC.NEAR, reach=0.1, robot=panda.view)
     torch.cuda.synchronize()
     assert radius == FC.RADIUS and not table._slots.pending
-    want = fusion.signed_volume(panda.spec_states(views).reshape(32, 32, 32), 0.01, radius, True)
+    want = panda.spec_fused(views, radius)
     got = _pool(table, 0, n).cpu().numpy().reshape(32, 32, 32)
     assert np.array_equal(got.view(np.uint32), FC.bits(want))
     i = panda.centre_nodes
@@ -252,6 +260,20 @@ def test_fuse_obstacles_with_the_arm_in_the_image(dev, panda):
     raw = fusion.signed_volume(panda.spec_states(views, filtered=False).reshape(32, 32, 32), 0.01, radius, True)
     got = _pool(table, 0, n).cpu().numpy().reshape(32, 32, 32)
     assert np.array_equal(got.view(np.uint32), FC.bits(raw)) and (got[i[:, 0], i[:, 1], i[:, 2]] < 0).any()
+
+
+def test_fuse_obstacles_with_the_arm_sends_four_small_arrays_to_the_device(dev, panda, monkeypatch):
+    """One fuse_obstacles(robot=) call uploads four host arrays, each once: the records at the slots' offsets, state_begin, the views
+    and view_range, which the carve, the clear and the transform share.  The pool holds the bits of the test above."""
+    from omg_planner_amd import ops
+    n, uploads, real_upload = 32 ** 3, [], ops._upload
+    table = _table(dev, 4 * n)
+    views = panda.obs.view_rows(table, [(0, 0)])
+    monkeypatch.setattr(ops, "_upload", lambda a, to: (uploads.append(bytes(a)), real_upload(a, to))[1])
+    radius = panda.obs.fuse_obstacles(table, [(0, 0)], [RC.PANDA_LAYOUT], FC.BAND, FC.NEAR, reach=0.1, robot=panda.view)
+    torch.cuda.synchronize()
+    assert len(uploads) == 4 and len(set(uploads)) == 4 and not table._slots.pending
+    assert np.array_equal(_pool(table, 0, n).cpu().numpy().reshape(32, 32, 32).view(np.uint32), FC.bits(panda.spec_fused(views, radius)))
 
 
 def test_integrate_obstacles_over_two_frames_with_the_arm_moved(dev, panda):

@@ -591,7 +591,8 @@ def test_wrapper_checks_without_gpu():
         ops.label_components(state, None, vols)
     with pytest.raises(E, match="components must be"):
         ops.component_states(state, None, [], [])
-    rec, _, begin = ops._fusion_volumes(vols, None)
+    batch = ops._VolumeBatch(vols, None)
+    rec, begin = batch.rec, batch.begin
     comps = ops.Components(torch.zeros(64, dtype=torch.int32), np.array([2]), np.array([0, 2]), np.zeros((2, 8), np.int32),
                            torch.zeros((2, 8), dtype=torch.int32), rec, begin, 1, 6)
     assert comps.of(0).shape == (2, 8)
