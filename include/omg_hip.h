@@ -1355,6 +1355,61 @@ int omgx_depth_normals(const double* depth_in, const uint8_t* flags_in /* or NUL
                        double* cosine /* or NULL */, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * (24) omgx_sphere_clearance, omgx_self_clearance: the arm's spheres against a scene table's volumes and against one another
+ * Stands in for: nothing.  The reference's only evidence that a plan is free is CHOMP's own hinge at the waypoints
+ * (OMGX_INFO_COLLIDE).  Here the arm is the N spheres of section 22 (local [N][4], link [N], in the frames of link_poses
+ * [B][10][4][4] of omgx_forward_kinematics) at B configurations, each standing in one scene of a scene table.
+ * omg-planner_amd/clearance.py (world_spheres, sphere_clearance, self_clearance) is the specification; all arithmetic is float64
+ * without contraction, dot products as (a*x + b*y) + c*z, + - * /, sqrt and comparisons only, rejections as negated comparisons
+ * (NaN falls on the "no" side), and the results have the specification's bits.  New entry points only: omgx_abi_version() stays 14.
+ *
+ * omgx_sphere_clearance: ONE launch for B configurations of S scenes; a workgroup of 256 threads per 4 configurations, a wave per
+ *   configuration, the sphere table through LDS in chunks of OMGX_ROBOT_SPHERE_CHUNK once per workgroup.  Configuration b stands
+ *   in scene scene_of_config[b], which owns the records [scene_begin[s], scene_begin[s+1]); record k (local to the scene) is USED
+ *   when visible[scene_begin[s] + k] != 0, or with visible == NULL when its `disabled` is 0.  Sphere n:
+ *     P = link_poses[b][link[n]];  w_k = ((P[k][0]*p0 + P[k][1]*p1) + P[k][2]*p2) + P[k][3];  world_out[b][n] = (w0, w1, w2, r_n)
+ *   and against a used record, with Q = pose_inv widened to float64 and section 21's interpolant v:
+ *     q_a = ((Q[4a]*w0 + Q[4a+1]*w1) + Q[4a+2]*w2) + Q[4a+3];  u_a = (q_a - (double)lo_a) * inv_delta - 0.5
+ *     c_a = u_a clamped as section 21 clamps it (!(u >= 0): 0;  u > dim_a - 1: dim_a - 1);  x_a = u_a - c_a
+ *     e = sqrt((x0*x0 + x1*x1) + x2*x2) / inv_delta;  the pair contributes iff e <= beyond;  d = v(c) - e
+ *     candidates: d - r_n for clear;  d - (r_n + pad[b][link[n]]) for margin
+ *   A candidate replaces the best iff it is < the best, or == the best with a smaller (n, k); NaN never wins; when nothing
+ *   contributes the result is (+inf, -1, -1).  Outside the grid d is a Lipschitz lower bound, inside e is exactly 0 and d = v.
+ *   clear, margin [B] double; clear_sphere, clear_object, margin_sphere, margin_object [B] int32.  pad [B][10] (device only: it is
+ *   computed there) or NULL: then margin, margin_sphere and margin_object must be NULL too, and otherwise none of them.
+ *   world_out [B][N][4] or NULL.  cull != 0: a wave skips a record that none of its 64 spheres reaches (one ballot of
+ *   e <= beyond); a sphere that does not reach contributes nothing, so the cull changes no bit; cull == 0 proves it.
+ *   link_poses and pad are not checked (they are outputs of the device): whatever they hold, the grid coordinate is clamped
+ *   before any address is formed, and NaN contributes nothing.
+ * omgx_self_clearance: ONE launch, a workgroup per configuration, the spheres world [B][N][4] (world_out above) in LDS.  Over
+ *   i < j with pairs[link[i]][link[j]] != 0 (pairs [10][10] uint8, device):
+ *     dx = c_i - c_j;  dist = sqrt((dx0*dx0 + dx1*dx1) + dx2*dx2);  cand = dist - ((r_i + pad_i) + (r_j + pad_j))
+ *   with pad_n = pad[b][link[n]] (0 with pad == NULL); the same replace rule on (i, j); self_clear [B] double, sphere_i, sphere_j
+ *   [B] int32, (+inf, -1, -1) without a pair.
+ * `objects`, `scene_begin`, `visible`, `scene_of_config`, `local`, `link` are on the device, h_* the same on the host; ALL checks
+ * are made on the host copies before any HIP call.  OMGX_ERR_INVALID: a null pointer that a positive count needs (visible and
+ * h_visible both or neither), a negative count, `beyond` not finite or negative, a sphere field not finite, a negative radius, a
+ * link outside [0, OMGX_NUM_LINKS), scene_of_config outside [0, num_scenes), scene_begin not ascending inside [0, num_objects],
+ * a used record of a scene with a dim < 2, inv_delta not finite or not > 0, or a grid that leaves [0, pool_elems).
+ * OMGX_ERR_UNSUPPORTED: more than OMGX_ROBOT_MAX_SPHERES spheres; more than OMGX_CLEARANCE_MAX_SELF for omgx_self_clearance.
+ * num_configs == 0 returns OMGX_OK and launches nothing; num_spheres == 0 writes (+inf, -1, -1) rows.  No atomics; every element
+ * is written by one thread.
+ * ------------------------------------------------------------------------------------------- */
+#define OMGX_CLEARANCE_MAX_SELF 1024
+int omgx_sphere_clearance(const omgx_object* objects, const omgx_object* h_objects, int32_t num_objects,
+                          const int32_t* scene_begin, const int32_t* h_scene_begin, int32_t num_scenes,
+                          const float* pool, int64_t pool_elems, const uint8_t* visible /* [num_objects] or NULL */,
+                          const uint8_t* h_visible, const int32_t* scene_of_config /* [B] */, const int32_t* h_scene_of_config,
+                          int32_t num_configs, const double* link_poses /* [B][10][16] */, const double* local /* [N][4] */,
+                          const double* h_local, const int32_t* link /* [N] */, const int32_t* h_link, int32_t num_spheres,
+                          const double* pad /* [B][10] or NULL */, double beyond, int32_t cull, double* clear, int32_t* clear_sphere,
+                          int32_t* clear_object, double* margin, int32_t* margin_sphere, int32_t* margin_object,
+                          double* world_out /* [B][N][4] or NULL */, void* stream);
+int omgx_self_clearance(const double* world /* [B][N][4] */, int32_t num_configs, const int32_t* link /* [N] */, const int32_t* h_link,
+                        int32_t num_spheres, const uint8_t* pairs /* [10][10] */, const double* pad /* [B][10] or NULL */,
+                        double* self_clear, int32_t* sphere_i, int32_t* sphere_j, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Diagnostics
  * ------------------------------------------------------------------------------------------- */
 const char* omgx_last_error(void); /* thread-local text of the last OMGX_ERR_LAUNCH               */

@@ -677,6 +677,68 @@ class DeviceScenes:
         """The scenes as they are on the device now, as a host SceneBatch (records + pool copied back): for oracle checks."""
         return _sc.SceneBatch(self.sync_host().copy(), self.host_scene_begin.copy(), self.pool[: self.pool_used].cpu().numpy())
 
+    def plan_clearance(self, spheres: "RobotSpheres", robot_blob, P: int, traj: torch.Tensor, substeps: int, slack: float = 0.0,
+                       beyond: float = 0.1, visible=None, pairs=None, rho=None, scene_of_plan=None, cull: bool = True) -> "PlanClearance":
+        """Are the plans traj [S',n,9] free of this table's volumes, at the waypoints and between them?  clearance.py is the
+        specification (its docstring says what the certificate means and what `slack` states): dense_configs with K = substeps,
+        ONE forward_kinematics call, ONE sphere_clearance launch with the pads of clearance.sample_pads, with `pairs` [10,10] ONE
+        self_clearance launch with the same pads, then clearance.plan_report in torch: the same bits throughout, and no host
+        sync on the way.  Plan s stands in scene scene_of_plan[s] (host integers; default: plan s in scene s, S' = num_scenes).
+        visible: one flag per record or None (the enabled records).  rho [10,9]: clearance.reach_table (default: the one
+        spheres.reach_table() computed).  Ordered on torch's current stream."""
+        dev = self.device
+        _tensor(traj, "traj", torch.float64, (None, None, 9), dev)
+        S, n = int(traj.shape[0]), int(traj.shape[1])
+        K = int(substeps)
+        rho = getattr(spheres, "rho", None) if rho is None else rho
+        if rho is None:
+            raise _lib.OmgHipError("rho is needed for the certificate: clearance.reach_table, or spheres.reach_table(model) once")
+        rho = np.ascontiguousarray(rho, np.float64)
+        if rho.shape != (10, 9) or not np.isfinite(rho).all() or (rho < 0).any():
+            raise _lib.OmgHipError("rho must be [10,9], finite and not negative")
+        if K < 1 or n < 1:
+            raise _lib.OmgHipError(f"substeps and the number of waypoints must be >= 1, got {K} and {n}")
+        _nonneg_finite(slack=slack, beyond=beyond)
+        sop = np.arange(S) if scene_of_plan is None else np.asarray(scene_of_plan, np.int64).reshape(-1)
+        if len(sop) != S or (S and (sop.min() < 0 or sop.max() >= self.num_scenes)):
+            raise _lib.OmgHipError(f"scene_of_plan must be {S} scenes in [0, {self.num_scenes})")
+        T = (n - 1) * K + 1
+        q = dense_configs(traj, K)
+        d_rho = _upload(rho, dev)
+        dq = (traj[:, 1:] - traj[:, :-1]).abs()  # clearance.segment_halves, operation for operation
+        length = d_rho[:, 0] * dq[:, :, 0:1]
+        for j in range(1, 9):
+            length = length + d_rho[:, j] * dq[:, :, j:j + 1]
+        half = (length / torch.full((1,), float(K), dtype=torch.float64, device=dev)) * 0.5  # (a tensor as divisor: dense_configs says why)
+        pad = torch.zeros((S, T, 10), dtype=torch.float64, device=dev)  # clearance.sample_pads
+        if n > 1:
+            pad[:, :-1] = half.repeat_interleave(K, dim=1)
+            way = half.clone()
+            way[:, 1:] = torch.maximum(half[:, 1:], half[:, :-1])
+            pad[:, 0:-1:K] = way
+            pad[:, -1] = half[:, -1]
+        pad = pad + float(slack)
+        poses = forward_kinematics(robot_blob, P, q.reshape(S * T, 9), want_joint_info=False)[0] if S else q.new_empty((0, 10, 4, 4))
+        out = sphere_clearance(self, spheres, poses, np.repeat(sop, T), visible=visible, pad=pad.reshape(S * T, 10), beyond=beyond, cull=cull,
+                               want_world=pairs is not None)
+        clear, margin = out[0].reshape(S, T), out[3].reshape(S, T)
+        own = (None, None, None) if pairs is None else tuple(x.reshape(S, T) for x in self_clearance(out[6], spheres, pairs, pad=pad.reshape(S * T, 10)))
+        r_max = float(spheres.h_local[:, 3].max()) if spheres.N else 0.0
+        if n > 1:  # clearance.plan_report
+            seg = torch.minimum(margin[:, :-1].reshape(S, n - 1, K).amin(dim=2), margin[:, K::K][:, : n - 1])
+            certified = (seg > 0.0) & ((r_max + half.amax(dim=2)) + float(slack) <= float(beyond))
+            whole = certified.all(dim=1)
+        else:
+            seg, certified = margin[:, :0], torch.zeros((S, 0), dtype=torch.bool, device=dev)
+            whole = (margin[:, 0] > 0.0) & (r_max + float(slack) <= float(beyond))
+        hit = clear < 0.0
+        collides = hit.any(dim=1)
+        first = torch.where(collides, hit.to(torch.uint8).argmax(dim=1), torch.full_like(collides, -1, dtype=torch.int64))
+        return PlanClearance(K=K, q=q, clear=clear, clear_sphere=out[1].reshape(S, T), clear_object=out[2].reshape(S, T), margin=margin,
+                             margin_sphere=out[4].reshape(S, T), margin_object=out[5].reshape(S, T), self_clear=own[0], self_i=own[1],
+                             self_j=own[2], half=half, segment_margin=seg, certified=certified, min_clearance=clear.amin(dim=1),
+                             collides=collides, first_hit=first, plan_certified=whole)
+
 
 def robot_blob(model, device="cuda:0") -> torch.Tensor:
     return torch.from_numpy(model.blob()).to(device)
@@ -2496,6 +2558,15 @@ class RobotSpheres:
             raise _lib.OmgHipError("radius must be a scalar or one value per link") from None
         return cls(np.concatenate([pts.reshape(-1, 3), r.reshape(-1, 1)], 1), np.repeat(np.arange(10), pts.shape[1]), device)
 
+    def reach_table(self, model, finger_travel: "float | None" = None) -> np.ndarray:
+        """clearance.reach_table for these spheres -> rho [10,9], kept as self.rho for DeviceScenes.plan_clearance.  finger_travel:
+        default the larger of the fingers' joint limits."""
+        from . import clearance as _cl
+        if finger_travel is None:
+            finger_travel = float(max(np.abs(model.joint_lower_limit[0, 7:]).max(), np.abs(model.joint_upper_limit[0, 7:]).max()))
+        self.rho = _cl.reach_table(model, self.h_local, self.h_link, finger_travel)
+        return self.rho
+
 
 def _camera_records(cameras, dev):
     """(device records, host records) of a CameraBatch or of camera.CAMERA_DTYPE records on the host."""
@@ -2726,3 +2797,138 @@ class FrameBatch(CameraBatch):
         self.num_meshes = 0
         cameras = np.asarray(cameras, np.float64)
         self.cameras = self._set_records(np.zeros(0, _cam.INSTANCE_DTYPE), np.zeros(len(cameras) + 1, np.int64), cameras, None, torch.device(device))
+
+
+def dense_configs(traj: torch.Tensor, K: int) -> torch.Tensor:
+    """clearance.dense_configs on the device (the same bits): traj [S,n,9] float64 -> q [S,(n-1)*K+1,9].  Sample i*K + k is
+    a + (b - a) * (k / K), every operation rounded on its own (plain operators: no addcmul, no lerp); k = 0 and the last sample are
+    the waypoints themselves."""
+    if not isinstance(traj, torch.Tensor) or traj.dim() != 3 or traj.shape[2] != 9 or traj.dtype != torch.float64:
+        raise _lib.OmgHipError("traj must be a float64 tensor [S,n,9]")
+    S, n, K = int(traj.shape[0]), int(traj.shape[1]), int(K)
+    if K < 1 or n < 1:
+        raise _lib.OmgHipError(f"K and the number of waypoints must be >= 1, got {K} and {n}")
+    q = torch.empty((S, (n - 1) * K + 1, 9), dtype=torch.float64, device=traj.device)
+    a, b = traj[:, :-1, None, :], traj[:, 1:, None, :]
+    # (a tensor divided by a tensor: dividing by a Python number may be done as a product with its reciprocal, which rounds otherwise)
+    w = (torch.arange(K, dtype=torch.float64, device=traj.device) / torch.full((K,), float(K), dtype=torch.float64, device=traj.device)).reshape(1, 1, K, 1)
+    seg = (b - a) * w
+    seg = a + seg
+    seg[:, :, 0, :] = traj[:, :-1]
+    q[:, :-1] = seg.reshape(S, (n - 1) * K, 9)
+    q[:, -1] = traj[:, -1]
+    return q
+
+
+def sphere_clearance(table: DeviceScenes, spheres: RobotSpheres, link_poses: torch.Tensor, scene_of_config, visible=None, pad=None,
+                     beyond: float = 0.1, cull: bool = True, want_world: bool = False):
+    """The clearance of B configurations of the arm from the volumes of their scenes, in ONE launch, straight from the records and
+    the pool as they stand on the device (omgx_sphere_clearance; clearance.world_spheres and sphere_clearance are the
+    specification: the same bits) -> (clear [B] float64, clear_sphere [B] int32, clear_object [B] int32, margin, margin_sphere,
+    margin_object (None with pad=None), world [B,N,4] float64 or None).  link_poses [B,10,4,4]: a float64 device tensor
+    (forward_kinematics), not downloaded; scene_of_config [B] host integers; visible: one flag per record of the table, or None
+    (the records whose `disabled` is 0); pad [B,10]: a float64 device tensor or None; beyond: how far outside a grid its volume
+    still speaks.  The host mirror is used for the checks of dims and offsets only.  cull=False walks every record in every wave:
+    the same bits.  Ordered on torch's current stream."""
+    from . import clearance as _cl
+    dev, N, vp = table.device, spheres.N, C.c_void_p
+    _tensor(link_poses, "link_poses", torch.float64, (None, 10, 4, 4), dev)
+    B = int(link_poses.shape[0])
+    h_cfg = np.ascontiguousarray(np.asarray(scene_of_config, np.int64).reshape(-1), np.int32)
+    S, n = table.num_scenes, len(table.host_objects)
+    h_begin = np.ascontiguousarray(table.host_scene_begin, np.int32)
+    _nonneg_finite(beyond=beyond)
+    if len(h_cfg) != B or (B and (h_cfg.min() < 0 or h_cfg.max() >= S)):
+        raise _lib.OmgHipError(f"scene_of_config must be {B} scenes in [0, {S})")
+    if spheres.device != dev:
+        raise _lib.OmgHipError(f"the spheres are on {spheres.device}, the table on {dev}")
+    if pad is not None:
+        _tensor(pad, "pad", torch.float64, (B, 10), dev)
+    try:  # (the specification's own checks of the table, as this module's error; nothing has touched the device's memory yet)
+        _cl.check_table(table.host_objects, h_begin, int(table.pool.numel()), visible)
+        h_visible = None if visible is None else np.ascontiguousarray(np.asarray(visible).reshape(-1) != 0, np.uint8)
+    except ValueError as e:
+        raise _lib.OmgHipError(str(e)) from None
+    if h_visible is not None and not n:
+        h_visible = None  # (flags for no records at all are no flags: an empty tensor has no address to pass beside the host's)
+    f64 = lambda: torch.empty((B,), dtype=torch.float64, device=dev)
+    i32 = lambda: torch.empty((B,), dtype=torch.int32, device=dev)
+    clear, cs, co = f64(), i32(), i32()
+    margin, ms, mo = (f64(), i32(), i32()) if pad is not None else (None, None, None)
+    world = torch.empty((B, N, 4), dtype=torch.float64, device=dev) if want_world else None
+    with torch.cuda.device(dev):
+        d_cfg, d_visible = _upload(h_cfg, dev) if B else None, None if h_visible is None else _upload(h_visible, dev)
+        check(_lib.lib().omgx_sphere_clearance(_ptr(table.objects) if n else None, vp(table.host_objects.ctypes.data) if n else None, n,
+                                               _ptr(table.scene_begin), vp(h_begin.ctypes.data), S, _ptr(table.pool) if table.pool.numel() else None,
+                                               int(table.pool.numel()), _ptr(d_visible), None if h_visible is None else vp(h_visible.ctypes.data),
+                                               _ptr(d_cfg), vp(h_cfg.ctypes.data) if B else None, B, _ptr(link_poses) if B else None,
+                                               _ptr(spheres.local) if N else None, vp(spheres.h_local.ctypes.data) if N else None,
+                                               _ptr(spheres.link) if N else None, vp(spheres.h_link.ctypes.data) if N else None, N,
+                                               _ptr(pad) if B else None, float(beyond), int(bool(cull)), _ptr(clear) if B else None,
+                                               _ptr(cs) if B else None, _ptr(co) if B else None, _ptr(margin) if B else None, _ptr(ms) if B else None,
+                                               _ptr(mo) if B else None, _ptr(world) if B and N else None, _stream()), "omgx_sphere_clearance")
+        _release(dev, d_cfg, d_visible)
+    return clear, cs, co, margin, ms, mo, world
+
+
+def default_self_pairs(fingers_touch: bool = True) -> np.ndarray:
+    """pairs [10,10] uint8 for self_clearance: the links whose spheres are held against one another.  A link is not held
+    against itself, its neighbour in the chain (they share a joint), or, from link 6 on, anything rigidly fixed to it: the hand
+    (7) on link 6 and the fingers (8, 9) on the hand.  fingers_touch: the two fingers may meet (they close on an object)."""
+    pairs = np.zeros((10, 10), np.uint8)
+    for i in range(10):
+        for j in range(i + 1, 10):
+            pairs[i, j] = pairs[j, i] = j - i >= 2 and i < 6
+    pairs[8, 9] = pairs[9, 8] = 0 if fingers_touch else 1
+    return pairs
+
+
+def self_clearance(world: torch.Tensor, spheres: RobotSpheres, pairs, pad=None):
+    """The smallest gap between two spheres of each of B configurations, in ONE launch (omgx_self_clearance;
+    clearance.self_clearance is the specification: the same bits) -> (self_clear [B] float64, i [B] int32, j [B] int32).  world
+    [B,N,4]: sphere_clearance's (want_world=True); pairs [10,10] host flags: which links are held against which; pad [B,10]: a
+    float64 device tensor or None.  At most clearance.MAX_SELF spheres."""
+    dev, N, vp = spheres.device, spheres.N, C.c_void_p
+    _tensor(world, "world", torch.float64, (None, N, 4), dev)
+    B = int(world.shape[0])
+    h_pairs = np.ascontiguousarray(np.asarray(pairs) != 0, np.uint8)
+    if h_pairs.shape != (10, 10):
+        raise _lib.OmgHipError(f"pairs must be [10,10], got {h_pairs.shape}")
+    if N > _lib.CONSTANTS["OMGX_CLEARANCE_MAX_SELF"]:
+        raise _lib.OmgHipError(f"self_clearance takes at most {_lib.CONSTANTS['OMGX_CLEARANCE_MAX_SELF']} spheres, got {N}")
+    if pad is not None:
+        _tensor(pad, "pad", torch.float64, (B, 10), dev)
+    out = torch.empty((B,), dtype=torch.float64, device=dev)
+    wi, wj = torch.empty((B,), dtype=torch.int32, device=dev), torch.empty((B,), dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        d_pairs = _upload(h_pairs, dev)
+        check(_lib.lib().omgx_self_clearance(_ptr(world) if B and N else None, B, _ptr(spheres.link) if N else None,
+                                             vp(spheres.h_link.ctypes.data) if N else None, N, _ptr(d_pairs), _ptr(pad) if B else None,
+                                             _ptr(out) if B else None, _ptr(wi) if B else None, _ptr(wj) if B else None, _stream()),
+              "omgx_self_clearance")
+        _release(dev, d_pairs)
+    return out, wi, wj
+
+
+class PlanClearance:
+    """What DeviceScenes.plan_clearance returns (device tensors; clearance.py names every field).  Per sample [S,T], T = (n-1)*K+1:
+    q [S,T,9]; clear, clear_sphere, clear_object; margin, margin_sphere, margin_object; self_clear, self_i, self_j (None without
+    pairs).  Per segment [S,n-1]: half [S,n-1,10], segment_margin, certified.  Per plan [S]: min_clearance, collides, first_hit
+    (a sample index or -1), plan_certified.  K: the samples per segment."""
+    SAMPLE = ("clear", "clear_sphere", "clear_object", "margin", "margin_sphere", "margin_object", "self_clear", "self_i", "self_j")
+    FILL = dict(q=0.0, clear=float("inf"), margin=float("inf"), self_clear=float("inf"), half=0.0, segment_margin=float("inf"), certified=False,
+                min_clearance=float("inf"), collides=False, first_hit=-1, plan_certified=False)  # (every index: -1)
+
+    def __init__(self, **fields):
+        self.__dict__.update(fields)
+
+    def scattered(self, S: int, rows: torch.Tensor) -> "PlanClearance":
+        """The same report over S plans with this one's plans at `rows`; the other rows say nothing: +inf, -1, False."""
+        out = {}
+        for name, x in self.__dict__.items():
+            if not isinstance(x, torch.Tensor):
+                out[name] = x
+                continue
+            full = torch.full((S,) + tuple(x.shape[1:]), self.FILL.get(name, -1), dtype=x.dtype, device=x.device)
+            out[name] = full.index_copy_(0, rows, x)
+        return PlanClearance(**out)

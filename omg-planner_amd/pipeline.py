@@ -185,3 +185,37 @@ def plan_on_unknown_support(model, scenes, obs, obstacles, supports, layouts, su
     plans, sets, meshes, records = plan_observed(model, scenes, obs, obstacles, layouts, band, near, reach, seeds, min_nodes, starts, cfg, connectivity,
                                                  margin, free_mask=mask, device=device, robot=robot, **plan_kwargs)
     return plans, sets, meshes, records, fit
+
+
+def check_plans(model, table, plans: GraspPlans, spheres, substeps: int, skip_targets: bool = True, fingers_touch: bool = True, targets=None,
+                **kw) -> "ops.PlanClearance":
+    """Are the plans free of the scenes they were planned in, or of a newer table of the same scenes, at the waypoints and between
+    them?  DeviceScenes.plan_clearance (clearance.py says what is computed and what a certificate means) on the rows with
+    plans.planned -> ops.PlanClearance over all S rows; a row that was not planned says nothing (+inf, -1, False).
+
+    table: an ops.DeviceScenes of the S scenes; spheres: ops.RobotSpheres on the links of forward_kinematics; substeps: samples per
+    segment.  The used records are the enabled ones (`disabled` 0 in the table's host mirror), minus each scene's target when
+    skip_targets is set: a grasp ends at the target, so its last samples touch it.  targets: one object index per scene, or the
+    scenes themselves (their target_idx); needed with skip_targets and to tell which object the plan's end touches.  The arm's own
+    links are held against one another by ops.default_self_pairs(fingers_touch) unless pairs= is given (pairs=False: not at all).
+    A grasped object is the caller's to add: its spheres go on link 7 of `spheres` (one sphere set for all scenes: per-scene sets
+    are not supported).  kw: plan_clearance's slack, beyond, rho, cull; without rho, spheres.reach_table(model) is used."""
+    S = table.num_scenes
+    if plans.traj.shape[0] != S or len(plans.planned) != S:
+        raise ValueError(f"the table has {S} scenes, the plans {plans.traj.shape[0]}")
+    visible = table.host_objects["disabled"] == 0
+    if skip_targets:
+        if targets is None:
+            raise ValueError("skip_targets needs targets: one object index per scene, or the scenes")
+        for s, t in enumerate(targets):
+            visible[table._index(s, int(getattr(t, "target_idx", t)))] = False
+    pairs = kw.pop("pairs", None)
+    pairs = ops.default_self_pairs(fingers_touch) if pairs is None else None if pairs is False else pairs
+    if kw.get("rho") is None and getattr(spheres, "rho", None) is None:
+        spheres.reach_table(model)
+    idx = np.flatnonzero(np.asarray(plans.planned, bool))
+    sel = torch.from_numpy(idx).to(table.device)
+    robot = plans.engine.robot if getattr(plans.engine, "robot", None) is not None else ops.robot_blob(model, table.device)
+    out = table.plan_clearance(spheres, robot, model.points_per_link, plans.traj.index_select(0, sel).contiguous(), substeps,
+                               visible=visible.astype(np.uint8), pairs=pairs, scene_of_plan=idx, **kw)
+    return out if len(idx) == S else out.scattered(S, sel)
