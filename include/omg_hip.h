@@ -1410,6 +1410,61 @@ int omgx_self_clearance(const double* world /* [B][N][4] */, int32_t num_configs
                         double* self_clear, int32_t* sphere_i, int32_t* sphere_j, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * (25) omgx_track_cameras: live depth frames aligned to the model's rendering, camera poses out
+ * Stands in for: nothing.  The reference has no tracker: its perception entry (omg/core.py:826-867) is given exact camera
+ * poses.  Sections 14 to 24 take cam_from_world as exact too; a camera known from kinematics or from the frame before is off by
+ * millimetres to centimetres, and a TSDF integrated from such poses smears.  This is projective point-to-plane ICP of V live
+ * frames (section 23's depth and normals) against V model renderings (section 21's depth and outward normals), one camera per
+ * view.  omg-planner_amd/tracking.py (track_cameras) is the specification; all arithmetic is float64 without contraction,
+ * + - * / and comparisons only, every operation rounded on its own, and the results have the specification's bits.  New entry
+ * points only: omgx_abi_version() stays 14.
+ *
+ * Per view: live_depth [H][W] (not > 0, or +inf: no information), live_normals [H][W][3] or NULL, model_depth [H][W] (+inf:
+ * background), model_normals [H][W][3], intrinsics fx, fy, cx, cy for both images, and T = the rows [R t] of
+ * model_cam_from_live_cam.  Pixel (r, c) is USED iff r % stride == 0 and c % stride == 0; used pixels are numbered row-major over
+ * the Hu x Wu used grid, Hu = (H - 1) / stride + 1.  Per used pixel, with section 14's ray (dx, dy):
+ *   VALID: z > 0 and z < +inf, and with live normals (m0*m0 + m1*m1) + m2*m2 > 0
+ *   P = (dx*z, dy*z, z);  Q_a = ((R[a][0]*P0 + R[a][1]*P1) + R[a][2]*P2) + t_a;  FRONT: Q2 > 0
+ *   ua = (fx*(Q0/Q2) + cx) + 0.5, ub = (fy*(Q1/Q2) + cy) + 0.5; inside iff 0 <= ua < W and 0 <= ub < H, in double, before any
+ *   conversion;  cm = (int)ua, rm = (int)ub;  THERE: zq = model_depth[rm][cm] > 0 and < +inf, n = model_normals[rm][cm], n.n > 0
+ *   M = (dx'*zq, dy'*zq, zq) with the ray of (rm, cm);  e = Q - M;  NEAR: (e0*e0 + e1*e1) + e2*e2 <= dist_max*dist_max
+ *   COMPATIBLE (live normals only): mr = R m, (mr0*n0 + mr1*n1) + mr2*n2 >= cos_min
+ *   an inlier passes all of them:  res = (n0*e0 + n1*e1) + n2*e2;  g = R^T n;  j = (g, P x g)
+ * and adds j_a*j_b (a <= b), j_a*res, res*res to 28 sums and 1 to the count; a VALID pixel that is no inlier adds
+ * dist_max*dist_max to the cost (sum 27); any other pixel adds nothing.  The sums' shape: chunks of
+ * OMGX_TRACK_PIXELS_PER_WORKGROUP used pixels; lane l of 256 adds its chunk's pixels l, l + 256, ... from +0.0; the lanes are
+ * summed as section 15 sums them (x[l] += x[l + s], s = 32 ... 1 inside a wave, then ((w0 + w1) + w2) + w3); the chunk totals
+ * are added left to right, beginning with chunk 0's.  The loop around the passes is section 15's, with its 6 x 6 solve, its
+ * pose update (t' = t + R xi_v, R' = R C(xi_w / 2)), its constants and its stats row; the status bits are OMGX_REGISTER_*.
+ *
+ * A pass is a launch of its own (a frame has 10^5 pixels, not 10^2 points) and the loop's state lives in the workspace:
+ * k_track_init (a block per view), then max_passes + 1 times k_track_pass (grid (chunks, V), 256 threads, 8 used pixels per
+ * lane, one row of 32 doubles per (view, chunk)) and k_track_step (a wave per view: the chunk rows added, the loop's turn, and
+ * poses_out / stats_out written exactly once, at the turn the view stops).  Everything is enqueued on `stream` without a host
+ * sync; a finished view costs a workgroup that returns at once; the stream's order is the only barrier.  No atomics; every
+ * element is written by one thread.
+ * poses0 [V][12] (device, never downloaded); poses_out [V][12] may be poses0; stats_out [V][OMGX_TRACK_STATS]: cost at poses0,
+ * final cost, inliers at poses0, final inliers, accepted trials, trials run, final lambda, status.  With max_passes == 0 or
+ * fewer than six inliers poses_out has poses0's bits.  A NaN or an infinity in poses0 or in an image needs no check: it fails the
+ * comparisons above.  `intrinsics` [V][4] is on the device, h_intrinsics the same on the host.
+ * ALL checks are made on the host before any HIP call.  OMGX_ERR_INVALID: a null pointer that a positive count needs, a negative
+ * count, H or W < 1, stride < 1, dist_max or lambda0 not finite or not > 0, cos_min NaN, max_passes outside
+ * [0, OMGX_TRACK_MAX_PASSES], an intrinsics field not finite, fx or fy zero, workspace_bytes below omgx_track_workspace_bytes,
+ * poses_out, stats_out or the workspace sharing a byte with an input or with one another (poses_out == poses0 excepted).
+ * OMGX_ERR_UNSUPPORTED: more than 65535 views or 2^23 tiles, num_views * H * W > 2^31 - 1.  num_views == 0 returns OMGX_OK and
+ * launches nothing.  omgx_track_workspace_bytes returns the bytes, 0 for no view, or the same error codes.
+ * ------------------------------------------------------------------------------------------- */
+#define OMGX_TRACK_PIXELS_PER_WORKGROUP 2048
+#define OMGX_TRACK_MAX_PASSES 64
+#define OMGX_TRACK_STATS 8
+int64_t omgx_track_workspace_bytes(int32_t num_views, int32_t H, int32_t W, int32_t stride);
+int omgx_track_cameras(const double* intrinsics /* [V][4] */, const double* h_intrinsics, const double* live_depth /* [V][H][W] */,
+                       const double* live_normals /* [V][H][W][3] or NULL */, const double* model_depth, const double* model_normals,
+                       int32_t num_views, int32_t H, int32_t W, int32_t stride, const double* poses0 /* [V][12] */, double dist_max,
+                       double cos_min, double lambda0, double step_tol, int32_t max_passes, void* workspace, int64_t workspace_bytes,
+                       double* poses_out, double* stats_out, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Diagnostics
  * ------------------------------------------------------------------------------------------- */
 const char* omgx_last_error(void); /* thread-local text of the last OMGX_ERR_LAUNCH               */

@@ -351,6 +351,52 @@ class Observation:
         fit = ops.fit_planes(intr, self.t, triples, tol, skip=skip, up=up, cos_min=cos_min, min_nn=min_nn, refine=refine)
         return fit, ops.plane_mask(intr, self.t, fit.planes, tol, skip=skip)
 
+    def cam_from_world(self) -> np.ndarray:
+        """[S,4,4] float64: the inverse (np.linalg.inv) of every scene's world_from_cam as the batch's host records hold it."""
+        rows = np.asarray(self.batch.h_cameras["world_from_cam"], np.float64).reshape(-1, 3, 4)
+        return np.stack([np.linalg.inv(np.vstack([w, [0.0, 0.0, 0.0, 1.0]])) for w in rows]) if len(rows) else np.zeros((0, 4, 4))
+
+    def tracked(self, table, poses0=None, rounds: int = 1, skip=(), level: float = 0.0, min_inliers: int = 100, min_share: float = 0.5, **track):
+        """The cameras of an observation made of sensor frames (observe_frames) corrected against the scene table: per round the
+        table's volumes are ray-cast at the current cameras (observe_volumes with normals: the model), the frames are aligned to
+        it (ops.track_cameras with self.t and self.normals; tracking.py is the specification), poses [S,12], stats [S,8] and the
+        VALID pixel counts are downloaded once, and on the host tracking.accepted_mask (min_inliers, min_share) decides which
+        views take tracking.compose's camera; a rejected view keeps the camera it had.  poses0 serves the first round, later
+        rounds start from identity.  skip, level: observe_volumes'; track: stride, dist_max, cos_min, lambda0, step_tol,
+        max_passes of ops.track_cameras.  -> (a new Observation with the same images on a new ops.FrameBatch with the corrected
+        cameras, which integrate_obstacles, fuse_obstacles, segment_obstacles, fit_supports and robot_view take as any other;
+        TrackResult: poses and stats of the last round, cam_from_world [S,4,4], accepted [S]: in any round).  It calls no planner."""
+        import torch
+        from . import ops, tracking
+        if not getattr(self.batch, "frames_only", False):
+            raise _lib.OmgHipError("tracked is for observations made of sensor frames (observe_frames): the instance records of a rendered "
+                                   "observation are tied to the camera they were built for, and moving it would leave them stale")
+        if int(rounds) < 1:
+            raise _lib.OmgHipError(f"rounds must be >= 1, got {rounds}")
+        S, H, W = (int(d) for d in self.t.shape)
+        intr, cfw = self.intrinsics().reshape(S, 4), self.cam_from_world()
+        stride = int(track.get("stride", 1))
+        if stride < 1:
+            raise _lib.OmgHipError("stride must be >= 1")
+        there = (self.t > 0) & (self.t < float("inf"))
+        if self.normals is not None:
+            m = self.normals
+            there &= (m[..., 0] * m[..., 0] + m[..., 1] * m[..., 1]) + m[..., 2] * m[..., 2] > 0
+        valid = there[:, ::stride, ::stride].reshape(S, -1).sum(1).to(torch.float64)  # tracking.valid_pixels, on the device
+        accepted = np.zeros(S, bool)
+        poses = stats = None
+        for k in range(int(rounds)):
+            model = observe_volumes(table, cfw, intr, H, W, level=level, skip=skip, want_normals=True)
+            d_poses, d_stats = ops.track_cameras(self.t, self.normals, model.t, model.normals, intr, poses0 if k == 0 else None, **track)
+            both = torch.cat([d_poses, d_stats, valid[:, None]], 1).cpu().numpy()  # one download
+            poses, stats = np.ascontiguousarray(both[:, :12]), np.ascontiguousarray(both[:, 12:20])
+            mask = tracking.accepted_mask(stats, min_inliers, min_share, both[:, 20])
+            cfw = np.stack([tracking.compose(poses[s], cfw[s]) if mask[s] else cfw[s] for s in range(S)]) if S else cfw
+            accepted |= mask
+        cameras = np.stack([camera_rows(intr[s], cfw[s]) for s in range(S)]) if S else np.zeros((0, 16))
+        obs = Observation(ops.FrameBatch(cameras, device=self.t.device), self.t, self.inst, self.face, self.normals, self.flags)
+        return obs, TrackResult(poses=poses, cam_from_world=cfw, stats=stats, accepted=accepted)
+
     def support_planes(self, table, pairs, fit) -> np.ndarray:
         """The fitted planes [n,4] in the frames of the (scene, obj) `pairs` of an ops.DeviceScenes (what
         DeviceScenes.plane_obstacles takes): pair (s, o) gets the plane of scene s moved by planes.plane_to_frame with
@@ -366,6 +412,14 @@ class Observation:
             world_from_cam = np.vstack([np.asarray(cams["world_from_cam"][s], np.float64).reshape(3, 4), [0.0, 0.0, 0.0, 1.0]])
             out[m] = _pl.plane_to_frame(h_planes[s], np.linalg.inv(poses[table._index(int(s), int(o))]) @ world_from_cam)
         return out
+
+
+class TrackResult:
+    """Observation.tracked's account, on the host: poses [S,12] (the rows [R t] of model_cam_from_live_cam) and stats [S,8] of the
+    last round, cam_from_world [S,4,4]: the cameras of the returned observation, accepted [S] bool."""
+
+    def __init__(self, poses, cam_from_world, stats, accepted):
+        self.poses, self.cam_from_world, self.stats, self.accepted = poses, cam_from_world, stats, accepted
 
 
 def explained_mask(t, t_known, tol: float):
@@ -395,7 +449,8 @@ def observe_frames(frames, scale: float, cam_from_world, intrinsics, tau, cos_mi
     device tensor or a host array (uploaded), one per camera, conditioned on the device (Observation.conditioned, which documents
     tau, cos_min, z_min, z_max and filter).  cam_from_world: [4,4] or [S,4,4]; intrinsics: (fx, fy, cx, cy) or [S,4].  Its batch
     (ops.FrameBatch) has the cameras and no instances; inst and face are -1 everywhere; normals and flags are filled.
-    What works on it: segment_obstacles, fit_supports, support_planes, robot_view, view_rows, intrinsics, conditioned, and
+    What works on it: tracked (its cameras corrected against a scene table), segment_obstacles, fit_supports, support_planes, robot_view,
+    view_rows, intrinsics, conditioned, and
     fuse_obstacles / integrate_obstacles with target_free=False.  What needs an instance image and raises: clouds, and
     fuse_obstacles / integrate_obstacles with target_free=True.  It does not call the planner."""
     import torch

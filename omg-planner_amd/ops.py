@@ -2799,6 +2799,77 @@ class FrameBatch(CameraBatch):
         self.cameras = self._set_records(np.zeros(0, _cam.INSTANCE_DTYPE), np.zeros(len(cameras) + 1, np.int64), cameras, None, torch.device(device))
 
 
+def track_workspace_bytes(V: int, H: int, W: int, stride: int = 1) -> int:
+    """The bytes track_cameras needs as its workspace for V views of H x W (omgx_track_workspace_bytes)."""
+    nbytes = int(_lib.lib().omgx_track_workspace_bytes(int(V), int(H), int(W), int(stride)))
+    if nbytes < 0:
+        check(nbytes, "omgx_track_workspace_bytes")
+    return nbytes
+
+
+def track_cameras(live_depth: torch.Tensor, live_normals: "torch.Tensor | None", model_depth: torch.Tensor, model_normals: torch.Tensor, intrinsics,
+                  poses0=None, stride: int = 1, dist_max: float = 0.05, cos_min: float = 0.7, lambda0: float = 2.0 ** -10, step_tol: float = 1e-6,
+                  max_passes: int = 12, workspace: "torch.Tensor | None" = None, out=None):
+    """Align V live depth frames to V model renderings by projective point-to-plane ICP (omgx_track_cameras; tracking.track_cameras
+    is the specification: the same float64 bit for bit) -> (poses [V,12]: the rows [R t] of model_cam_from_live_cam, stats [V,8]:
+    registration's columns) float64 on the device.  live_depth [V,H,W] (not > 0: no information) and live_normals [V,H,W,3] or None
+    (depth_normals' outputs), model_depth [V,H,W] (+inf: background) and model_normals [V,H,W,3] (render_volumes' t and normal):
+    contiguous float64 device tensors; intrinsics [V,4] on the host: fx, fy, cx, cy of both images; poses0 [V,12]: a float64
+    device tensor (never downloaded), a host array (uploaded), or None: identity.  One init launch and max_passes + 1 times a pass
+    and a step launch on torch's current stream, no host sync: a view that has stopped costs workgroups that return at once.
+    workspace: None or a uint8 device tensor of at least track_workspace_bytes(V, H, W, stride); out: None or (poses, stats)
+    written IN PLACE; out[0] may be poses0."""
+    from . import tracking as _tr
+    # what does not depend on where a tensor lies comes first: the scalars and the shapes
+    try:
+        _tr.check_scalars(stride, dist_max, cos_min, lambda0, step_tol, max_passes)
+    except ValueError as e:
+        raise _lib.OmgHipError(str(e)) from None
+    if not isinstance(live_depth, torch.Tensor) or live_depth.dim() != 3:
+        raise _lib.OmgHipError(f"live_depth must be a tensor [V,H,W], got {tuple(getattr(live_depth, 'shape', ()))}")
+    V, H, W = (int(d) for d in live_depth.shape)
+    if V:
+        _image_size(H, W)
+    images = [("live_depth", live_depth, (V, H, W)), ("model_depth", model_depth, (V, H, W)), ("model_normals", model_normals, (V, H, W, 3))]
+    if live_normals is not None:
+        images.append(("live_normals", live_normals, (V, H, W, 3)))
+    for name, t, shape in images:
+        if not isinstance(t, torch.Tensor) or tuple(t.shape) != shape:
+            raise _lib.OmgHipError(f"{name} must be a tensor {list(shape)}, got {list(getattr(t, 'shape', ()))}")
+    h_k = np.ascontiguousarray(intrinsics, np.float64)
+    if h_k.shape != (V, 4) or not np.isfinite(h_k).all() or (h_k[:, :2] == 0).any():
+        raise _lib.OmgHipError(f"intrinsics must be [{V},4], finite, with no focal length of zero")
+    dev = live_depth.device
+    if poses0 is None or not isinstance(poses0, torch.Tensor):
+        h_poses0 = np.ascontiguousarray(np.tile(_tr.IDENTITY, (V, 1)) if poses0 is None else poses0, np.float64)
+        if h_poses0.shape != (V, 12):
+            raise _lib.OmgHipError(f"poses0 must be [{V},12], got {h_poses0.shape}")
+        poses0 = torch.from_numpy(h_poses0) if dev.type == "cpu" else torch.from_numpy(h_poses0).to(dev)
+    if tuple(poses0.shape) != (V, 12):
+        raise _lib.OmgHipError(f"poses0 must be [{V},12], got {tuple(poses0.shape)}")
+    for name, t, shape in images:
+        _tensor(t, name, torch.float64, shape, dev)
+    _tensor(poses0, "poses0", torch.float64, (V, 12), dev)
+    if out is None:
+        out = (torch.empty((V, 12), dtype=torch.float64, device=dev), torch.empty((V, _tr.STATS), dtype=torch.float64, device=dev))
+    poses, stats = _tensor(out[0], "out[0]", torch.float64, (V, 12), dev), _tensor(out[1], "out[1]", torch.float64, (V, _tr.STATS), dev)
+    need = track_workspace_bytes(V, H, W, stride)
+    if workspace is None:
+        workspace = _workspace(need, dev)
+    _tensor(workspace, "workspace", torch.uint8, (None,), dev)
+    if workspace.numel() < need:
+        raise _lib.OmgHipError(f"workspace has {workspace.numel()} bytes, {need} are needed")
+    with torch.cuda.device(dev):
+        d_k = _upload(h_k, dev)
+        check(_lib.lib().omgx_track_cameras(_ptr(d_k) if V else None, C.c_void_p(h_k.ctypes.data) if V else None, _ptr(live_depth) if V else None,
+                                            _ptr(live_normals) if V else None, _ptr(model_depth) if V else None, _ptr(model_normals) if V else None,
+                                            V, H, W, int(stride), _ptr(poses0) if V else None, float(dist_max), float(cos_min), float(lambda0),
+                                            float(step_tol), int(max_passes), _ptr(workspace) if V else None, int(workspace.numel()),
+                                            _ptr(poses) if V else None, _ptr(stats) if V else None, _stream()), "omgx_track_cameras")
+        _release(dev, d_k)
+    return poses, stats
+
+
 def dense_configs(traj: torch.Tensor, K: int) -> torch.Tensor:
     """clearance.dense_configs on the device (the same bits): traj [S,n,9] float64 -> q [S,(n-1)*K+1,9].  Sample i*K + k is
     a + (b - a) * (k / K), every operation rounded on its own (plain operators: no addcmul, no lerp); k = 0 and the last sample are
